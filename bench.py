@@ -9,7 +9,9 @@ is quoted on: AND table, C=1, M=2^16, s=2^24 (src/benches/bench.rs `halo2_compar
 N > 1 (torch.distributed / RCCL, one process per GPU): each rank proves an independent batch of s lookups — the path
 partitions by proof, there is no data-path collective — so value = N*s*K / max-over-ranks time and scaling is "weak".
 
-One JSON line on rank 0.  Extra objects: roofline (dominant HBM-streaming kernel family, HIP events on the library's stream; `frac` = algorithmic
+One JSON line on rank 0.  A plain run sets up, warms up, times --steps proofs and prints the line (headline, `ms_per_step`, setup spans, library digests,
+multi_gpu); --dump-outputs DIR also writes the last timed proof as DIR/proof.npy (one float32 per byte).  Everything below is measured only with --full.
+Extra objects (--full): roofline (dominant HBM-streaming kernel family, HIP events on the library's stream; `frac` = algorithmic
 bytes / time / peak and `frac_traffic` = counter-measured HBM bytes / time / peak), roofline_bind_top (the kernel the north star names),
 roofline_msm (the MSM families: group additions of the reference's algorithm per second against the measured mixed-addition ceiling),
 dominant_family (largest family by time over ALL families), kernels (every kernel family: launches, ms, algorithmic GB/s),
@@ -66,8 +68,23 @@ def parse():
     p.add_argument("--slab-capacity", action="store_true", help="slab leg in capacity mode (lasso_host_set_capacity): per-rank high-water mark = the prover's live peak")
     p.add_argument("--no-bind-sweep", action="store_true", help="skip the kernel-level bind_top sweep (SURVEY 8(d): n in {2^24, 2^26, 2^28} x {1, 9} polynomials)")
     p.add_argument("--only-bind-sweep", action="store_true", help="run only the bind_top sweep and print its object (the command the rocprofv3 / PMC passes of profiles/r04_* wrap)")
+    p.add_argument("--full", action="store_true", help="also measure everything beside the headline: per-kernel profile and rooflines, concurrent proofs, bind_top sweep, "
+                                                        "CPU baseline with oracle parity, slab leg (the --no-* / --concurrent options select among them)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the proof of the last timed step as DIR/proof.npy (float32, one element per byte; rank 0)")
     p.add_argument("--slab-worker", default=None, help=argparse.SUPPRESS)   # internal: rank,world,device,shm_name — the slab leg's child process
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if not a.full:      # a plain run does only what the headline needs
+        a.no_prof = a.no_cpu_baseline = a.no_bind_sweep = a.no_slab_leg = True
+        a.concurrent = 0
+    return a
+
+
+def dump_outputs(d, proof):
+    """--dump-outputs: what a caller of the timed path receives — the serialized proof — one float32 per byte (exact), as DIR/proof.npy"""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "proof.npy"), np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
 
 
 def _oracle_run(orc, kind_id, c, log_m, log_r, log_s, threads, want_bytes):
@@ -571,7 +588,9 @@ def main():
     t_setup = time.time() - t0
     t0 = time.time(); dense = hp.densify(idx, log_m); dev_lib.lasso_sync(ctx); t_densify = time.time() - t0
     t0 = time.time(); comm = hp.commit(dense, gens); t_commit = time.time() - t0
-    t0 = time.time(); hp.commit(dense, gens); t_commit_warm = time.time() - t0      # the first call also pays first-use costs (kernel load, table faults)
+    t_commit_warm = None
+    if a.full:
+        t0 = time.time(); hp.commit(dense, gens); t_commit_warm = time.time() - t0      # the first call also pays first-use costs (kernel load, table faults)
 
     def barrier():
         dev_lib.lasso_sync(ctx)
@@ -595,6 +614,8 @@ def main():
     dev_lib.lasso_sync(ctx)
     elapsed = time.perf_counter() - t0
     barrier()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, proof)
 
     def family(kid, large):
         n = C.c_uint64(); ms = C.c_double(); b = C.c_double(); u = C.c_double()
@@ -636,7 +657,7 @@ def main():
                                       f"timed = SparsePolynomialEvaluationProof::prove with the densified representation resident in HBM",
                           "vs_baseline_reference": "2^24 AND lookups, C=1, SparsePoly.prove 35.3 s with rayon on an Apple M1 16 GB (reference's src/benches/m1_16gb_parallel_benches.log:439; BASELINE.md §1)",
                           "per_rank": ("one proof sharded over the ranks by low index bits (slab mode)" if slab else "one independent proof per rank") if world > 1 else "single proof",
-                          "proof_bytes": len(proof), "proof_sha256": __import__("hashlib").sha256(proof).hexdigest(), "distinct_proofs": len(set(digests)), "densify_s": round(t_densify, 3), "commit_s": round(t_commit, 3), "commit_warm_s": round(t_commit_warm, 3), "gens_setup_s": round(t_setup, 3), "gens_derive_s": round(t_derive, 3), "gens_tables_s": round(t_tables, 3),
+                          "proof_bytes": len(proof), "proof_sha256": __import__("hashlib").sha256(proof).hexdigest(), "distinct_proofs": len(set(digests)), "densify_s": round(t_densify, 3), "commit_s": round(t_commit, 3), "commit_warm_s": round(t_commit_warm, 3) if t_commit_warm is not None else None, "gens_setup_s": round(t_setup, 3), "gens_derive_s": round(t_derive, 3), "gens_tables_s": round(t_tables, 3),
                           "whole_bench_lookups_per_s": s / (t_densify + t_commit + ms_per_step / 1e3)}}
         out["lib_sha"] = lib_sha(a.curve)
         out["host"] = host_info()   # the metric depends on the host's share of the Fiat-Shamir chain: say what the host was

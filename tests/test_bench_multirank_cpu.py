@@ -19,7 +19,7 @@ def test_bench_gpus2_self_launch_prints_weak_and_slab(oracle):
     env = dict(os.environ, LASSO_PROVER_LIB=so, LASSO_DEVICE_LIB=so, OMP_NUM_THREADS="2")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--log-s", "8", "--log-m", "8", "--no-cpu-baseline", "--concurrent", "0",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--log-s", "8", "--log-m", "8", "--full", "--no-cpu-baseline", "--concurrent", "0",
            "--slab-kind", "range", "--slab-c", "2", "--slab-log-s", "7", "--slab-steps", "1", "--log-r", "12", "--slab-timeout", "240"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -181,6 +181,36 @@ def test_bench_world8_shard_proof_pooled_and_capacity(oracle):
         digests.append(out["config"].get("proof_sha256"))
     want = _oracle_digest(oracle, so, "range", 2, 8, 12, 10)
     assert digests[0] == digests[1] == want, (digests, want)
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_the_last_proof(oracle, tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` proves W + N times and prints the headline line only (every other leg is behind --full);
+    --dump-outputs writes the last timed proof, the same on every run with the same arguments and the oracle's bytes for that instance."""
+    import hashlib
+    so = build_mock_prover()
+    env = dict(os.environ, LASSO_PROVER_LIB=so, LASSO_DEVICE_LIB=so, OMP_NUM_THREADS="2", LASSO_TRACE="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-s", "8", "--log-m", "8", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert sum(1 for ln in res.stderr.splitlines() if ln.startswith("[trace] SparsePoly.prove:")) == 1 + 3     # warm-up + timed steps, nothing else
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "lookups/s" and out["higher_is_better"] is True and out["dtype"].startswith("u256")
+        assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] * 1e-3 / (1 << 8) - 1) < 1e-9
+        for k in ("kernels_one_profiled_step", "roofline", "roofline_msm", "concurrent_proofs", "bind_top_sweep", "cpu_baseline", "parity_checked", "slab_mode"):
+            assert k not in out, k
+        p = np.load(d / "proof.npy")
+        assert p.dtype == np.float32 and p.shape == (out["config"]["proof_bytes"],)
+        assert hashlib.sha256(p.astype(np.uint8).tobytes()).hexdigest() == out["config"]["proof_sha256"]
+        dumps.append(p)
+    assert np.array_equal(dumps[0], dumps[1])
+    assert out["config"]["proof_sha256"] == _oracle_digest(oracle, so, "and", 1, 8, 0, 8)
 
 
 def test_bench_world8_independent_proofs_line_is_self_describing():

@@ -18,6 +18,7 @@ r_tests_bn254() {  # tests_bn254 [k] [tag]: the entry-point cases on the BN254 l
 }
 r_bench() {        # bench <tag> [bench.py args...]: one bench.py run, JSON line kept, headline printed
   local tag="$1"; shift; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # the rooflines, per-family table, sweeps, parity and slab leg printed below are measured only under --full
   timeout 900 python bench.py "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err
   python - "$tag" <<'PY'
 import json, sys
@@ -41,11 +42,13 @@ PY
 }
 r_prof() {         # prof <tag> [bench.py args...]: rocprofv3 --kernel-trace --stats of a short bench run; csv files kept
   local tag="$1"; shift; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # the profiled run keeps its per-family table and its extra fully-bracketed step, which only --full measures
   (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o bench -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --concurrent 0 --no-slab-leg --no-bind-sweep "$@" > $ROOT/gpurun_out/$tag/bench_under_rocprof.json 2> $ROOT/gpurun_out/$tag/rocprof.err)
   find /tmp/prof_$tag -name '*stats.csv' -exec cp {} gpurun_out/$tag/ \; ; ls gpurun_out/$tag | head
 }
 r_pmc() {          # pmc <tag> [bench.py args...]: the two separate PMC passes (FETCH_SIZE, WRITE_SIZE; only --kernel-trace beside --pmc) + tools/pmc_summary.py
   local tag="$1"; shift; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # tools/pmc_summary.py reads `large_launches_timed`, which only --full measures
   for CTR in FETCH_SIZE WRITE_SIZE; do
     (cd /tmp && timeout 900 rocprofv3 --pmc $CTR --kernel-trace --output-format csv -d /tmp/pmc_${tag}_$CTR -o bench -- python $ROOT/bench.py --steps 1 --warmup 1 --no-cpu-baseline --concurrent 0 --no-slab-leg --no-bind-sweep "$@" > $ROOT/gpurun_out/$tag/bench_$CTR.json 2> $ROOT/gpurun_out/$tag/rocprof_$CTR.err)
     f=$(find /tmp/pmc_${tag}_$CTR -name '*counter_collection.csv' | head -1); [ -n "$f" ] && cp $f gpurun_out/$tag/bench_${CTR}_counter_collection.csv
@@ -68,6 +71,7 @@ r_memtable() {     # memtable <tag> [tools/slab_mem_table.py args...]
 }
 r_benv() {         # benv <tag> "<VAR=val VAR=val ...>" [bench.py args...]: r_bench under environment switches (A/B runs); the quick form of the bench (no CPU baseline / sweeps)
   local tag="$1" envs="$2"; shift 2; mkdir -p gpurun_out/$tag
+  set -- --full "$@"   # the roofline printed below is measured only under --full
   env $envs timeout 600 python bench.py --no-cpu-baseline --concurrent 0 --no-slab-leg --no-bind-sweep "$@" > gpurun_out/$tag/bench.json 2> gpurun_out/$tag/bench.err
   python - "$tag" "$envs" <<'PY'
 import json, sys
