@@ -54,13 +54,47 @@ enum lasso_strategy_kind { LASSO_AND = 0, LASSO_OR = 1, LASSO_XOR = 2, LASSO_LT 
    * EqPolynomial(tau_i).evals(), combine_lookups = the product of the C values, sumcheck degree C (to be confirmed against upstream).  Restated from that
    * description so that configs[4]'s shape runs under its own name; tau = C * log2(M) draws of F::rand from a fresh ark_std::test_rng() (the snapshot's trait has no
    * per-proof table parameter).  The tables hold field elements, so the integer shortcuts (lasso_materialize_subtable_u32, the *_u32 entry points) do not apply. */
-  LASSO_SPARK_UNCONFIRMED = 5 };
+  LASSO_SPARK_UNCONFIRMED = 5,
+  /* A CALLER-DEFINED strategy: the `SubtableStrategy` trait (src/subtables/mod.rs:31-93) as data.  The `lasso_strategy` is then the first member of a
+   * lasso_strategy_custom (below) and every entry point that takes a `const lasso_strategy*` reads the larger struct. */
+  LASSO_CUSTOM = 6 };
 typedef struct {
   int32_t kind;      /* lasso_strategy_kind */
   uint32_t c;        /* const generic C */
   uint32_t log_m;    /* log2 of const generic M */
   uint32_t log_r;    /* RangeCheckSubtableStrategy<LOG_R> only */
 } lasso_strategy;
+/* The caller's own tables and combine polynomial (kind = LASSO_CUSTOM).  Passed as `(const lasso_strategy*)&custom` wherever a strategy is taken: lasso_host_prove*,
+ * lasso_host_verify*, lasso_sumcheck_combine_round, lasso_combine_claim.  All pointers are HOST memory owned by the caller for the duration of the call.
+ *   materialize_subtables    -> num_subtables tables of 2^log_m entries, ALL as 32-bit integers (tables_u32; what every table of the reference holds) or ALL as field
+ *                               elements in memory form (tables_fr); exactly one of the two pointers is non-NULL.  The two device entry points do not read the tables.
+ *   evaluate_subtable_mle    -> nothing to write: the verifier evaluates the MLE of the table itself (a dot product with EqPolynomial(point).evals(), 2^log_m products).
+ *                               THE TABLES ARE PART OF THE STATEMENT: fixed by the strategy both sides agreed on, not chosen by the prover.
+ *   memory_to_subtable_index / memory_to_dimension_index -> memory_subtable[i] < num_subtables, memory_dimension[i] < c; NULL = the trait's defaults i % num_subtables and
+ *                               i / num_subtables (mod.rs:64-74), which require num_memories <= c * num_subtables.
+ *   combine_lookups          -> g(v) = sum_t coeff[t] * prod_{j in [term_start[t], term_start[t+1])} v[term_mem[j]]: a sparse polynomial in the num_memories values.  A memory may
+ *                               repeat inside a term (a power); a term without factors is a constant.  term_start[0] = 0, non-decreasing.
+ *   g_poly_degree            -> the longest term; the sumcheck degree is that + 1 (a constant g: 1) and at most LASSO_CUSTOM_MAX_DEGREE.
+ * If every term has exactly one factor g is linear and the prover takes the eq-weighted path of AND / OR / XOR / RangeCheck with the coefficients as weights (coefficients of
+ * a memory named twice add up; a memory named by no term has weight 0).
+ * A descriptor that breaks one of these rules is LASSO_ERR_INVALID with a message, before anything is launched. */
+#define LASSO_CUSTOM_MAX_TERMS 256
+#define LASSO_CUSTOM_MAX_FACTORS 2048
+#define LASSO_CUSTOM_MAX_DEGREE 17
+typedef struct {
+  lasso_strategy base;                 /* kind = LASSO_CUSTOM, c, log_m; log_r unused */
+  uint32_t num_subtables;
+  uint32_t num_memories;               /* 1 .. 32 */
+  const uint32_t* const* tables_u32;   /* num_subtables pointers, or NULL */
+  const lasso_fr* const* tables_fr;    /* num_subtables pointers, or NULL */
+  const uint32_t* memory_subtable;     /* num_memories entries, or NULL */
+  const uint32_t* memory_dimension;    /* num_memories entries, or NULL */
+  uint32_t num_terms;                  /* 1 .. LASSO_CUSTOM_MAX_TERMS */
+  uint32_t reserved;                   /* 0 */
+  const lasso_fr* coeff;               /* num_terms coefficients, memory form */
+  const uint32_t* term_start;          /* num_terms + 1 offsets into term_mem; term_start[num_terms] <= LASSO_CUSTOM_MAX_FACTORS */
+  const uint32_t* term_mem;            /* memory indices < num_memories */
+} lasso_strategy_custom;
 
 /* ---- context, memory ---------------------------------------------------------------------- */
 int32_t lasso_ctx_create(int32_t device, lasso_ctx** out);
@@ -236,6 +270,8 @@ int32_t lasso_sumcheck_linear_tail_begin(lasso_ctx* ctx, const lasso_fr* const* 
 /* One round of SumcheckInstanceProof::prove_arbitrary (src/subprotocols/sumcheck.rs:165-237) with
  * comb_func = S::combine_lookups_eq (src/subtables/mod.rs:53-57): out[x] = sum_i g(E_1..E_alpha)(x) * eq(x), x = 0..degree.
  * d_polys holds alpha = NUM_MEMORIES device pointers; d_eq is the eq polynomial. */
+/* kind = LASSO_CUSTOM: s points to a lasso_strategy_custom; degree = longest term + 1 (at least 1); any sparse g (k_combine_round_custom).  The packed term list is kept
+ * on the device between calls and uploaded again only when it changes. */
 int32_t lasso_sumcheck_combine_round(lasso_ctx* ctx, const lasso_strategy* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq,
                                      size_t n, uint32_t degree, lasso_fr* out);
 /* LT strategy, the prover's form of the degree-(C+1) round (lt.rs:62-71 inside sumcheck.rs:179-218).  In Horner form  g = LT_0 + EQ_0 (LT_1 + EQ_1 (... + EQ_{C-2} LT_{C-1}))  a round

@@ -145,6 +145,11 @@ void lasso_host_gen_random_point(size_t bits, lasso_fr* out);
  * that trips one of the reference's assert!s on shapes, returns -1 with the reason in lasso_host_last_error(). */
 int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strategy* strategy, size_t s, const lasso_fr* r, size_t r_len, const char* transcript_label,
                           const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok);
+/* Validate a strategy descriptor without proving anything: 0, or LASSO_ERR_INVALID (-1) with the reason in lasso_host_last_error().  For kind = LASSO_CUSTOM
+ * (include/lasso_hip.h lasso_strategy_custom, passed as (const lasso_strategy*)&custom) this is the check lasso_host_prove* / lasso_host_verify* make on entry: table pointers,
+ * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (2^log_m products per memory): THE TABLES ARE PART OF THE STATEMENT,
+ * fixed by the strategy prover and verifier agreed on — a verifier must never take them from the prover. */
+int32_t lasso_host_strategy_check(const lasso_strategy* strategy);
 /* Test support (not part of the reference's surface): prove_cubic_batched (sumcheck.rs:27-135, C = EqPolynomial(rand).evals()) on caller-supplied
  * arrays with a scripted eq point, for the degenerate points (rand_t = 0 or 1) no transcript produces.  A, B: k contiguous arrays of 2^ell elements.
  * out = 3 compressed coefficients per round, the ell challenges, the k final claims of A, the k of B (32-byte canonical scalars). */

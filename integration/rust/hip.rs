@@ -74,6 +74,48 @@ impl<F: PrimeField, const C: usize, const M: usize, const LOG_R_: usize> HipStra
   const LOG_R: u32 = LOG_R_ as u32;
 }
 
+// ---- caller-defined strategies: the `SubtableStrategy` trait as data (include/lasso_hip.h `lasso_strategy_custom`, INTEGRATION.md "Your own table")
+const _: () = assert!(std::mem::size_of::<lasso_strategy>() == 16 && std::mem::size_of::<lasso_strategy_custom>() == 88 && std::mem::align_of::<lasso_strategy_custom>() == 8);
+const _: () = assert!(LASSO_CUSTOM == 6 && LASSO_CUSTOM_MAX_TERMS == 256 && LASSO_CUSTOM_MAX_FACTORS == 2048 && LASSO_CUSTOM_MAX_DEGREE == 17);
+
+/// The tables of a caller-defined strategy: all small integers (what every table of the reference holds: the integer shortcuts apply) or all field elements.
+pub enum CustomTables<F: PrimeField> { U32(Vec<Vec<u32>>), Field(Vec<Vec<F>>) }
+
+/// Owns everything a `lasso_strategy_custom` points to; `as_strategy()` is what `lasso_host_prove_cb` / `lasso_host_verify_cb` take in place of `&S::descriptor()`.
+pub struct HipCustomStrategy<F: PrimeField> {
+  tables: CustomTables<F>, table_ptrs: Vec<*const c_void>, maps: Option<(Vec<u32>, Vec<u32>)>,
+  coeff: Vec<F>, term_start: Vec<u32>, term_mem: Vec<u32>,
+  desc: lasso_strategy_custom,
+}
+impl<F: PrimeField> HipCustomStrategy<F> {
+  /// `tables` = materialize_subtables(); `terms` = combine_lookups as (coefficient, memory indices) with g = sum coeff * prod vals[index] (g_poly_degree = the longest term);
+  /// `maps` = (memory_to_subtable_index, memory_to_dimension_index) per memory, None = the trait's defaults (mod.rs:64-74).  The library validates on every call
+  /// (`lasso_host_strategy_check` does so without proving).
+  pub fn new(c: usize, log_m: usize, num_memories: usize, tables: CustomTables<F>, terms: &[(F, Vec<usize>)], maps: Option<(Vec<u32>, Vec<u32>)>) -> Box<Self> {
+    let table_ptrs: Vec<*const c_void> = match &tables {
+      CustomTables::U32(t) => t.iter().map(|x| { assert_eq!(x.len(), 1 << log_m); x.as_ptr() as *const c_void }).collect(),
+      CustomTables::Field(t) => t.iter().map(|x| { assert_eq!(x.len(), 1 << log_m); x.as_ptr() as *const c_void }).collect(),
+    };
+    let mut term_start = vec![0u32]; let mut term_mem = Vec::new(); let mut coeff = Vec::new();
+    for (cf, mems) in terms { coeff.push(*cf); term_mem.extend(mems.iter().map(|&m| m as u32)); term_start.push(term_mem.len() as u32); }
+    let mut s = Box::new(Self { tables, table_ptrs, maps, coeff, term_start, term_mem, desc: unsafe { std::mem::zeroed() } });
+    let is_u32 = matches!(s.tables, CustomTables::U32(_));
+    s.desc = lasso_strategy_custom {
+      base: lasso_strategy { kind: LASSO_CUSTOM, c: c as u32, log_m: log_m as u32, log_r: 0 },
+      num_subtables: s.table_ptrs.len() as u32, num_memories: num_memories as u32,
+      tables_u32: if is_u32 { s.table_ptrs.as_ptr() as *const *const u32 } else { std::ptr::null() },
+      tables_fr: if is_u32 { std::ptr::null() } else { s.table_ptrs.as_ptr() as *const *const lasso_fr },
+      memory_subtable: s.maps.as_ref().map_or(std::ptr::null(), |m| m.0.as_ptr()), memory_dimension: s.maps.as_ref().map_or(std::ptr::null(), |m| m.1.as_ptr()),
+      num_terms: s.coeff.len() as u32, reserved: 0,
+      coeff: s.coeff.as_ptr() as *const lasso_fr, term_start: s.term_start.as_ptr(), term_mem: s.term_mem.as_ptr(),
+    };
+    chk(unsafe { lasso_host_strategy_check(s.as_strategy()) }, "lasso_host_strategy_check");
+    s
+  }
+  /// the `const lasso_strategy*` every entry point takes: a pointer to the descriptor's first member (the Box keeps it in place)
+  pub fn as_strategy(&self) -> *const lasso_strategy { &self.desc.base as *const lasso_strategy }
+}
+
 /// One device context + host prover (`lasso_host`).  One per prover thread; the library is not re-entrant on a context.
 pub struct HipProver {
   h: *mut lasso_host,

@@ -8,3 +8,4 @@ layer on a machine without the built extension or without a GPU raises.
 """
 from .device import Device, LassoError, load_device_library  # noqa: F401
 from .prover import HostProver, load_prover_library  # noqa: F401,E402
+from .custom import CustomStrategy, fr_words  # noqa: F401,E402

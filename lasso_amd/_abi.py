@@ -12,7 +12,14 @@ class Strategy(C.Structure):
     _fields_ = [("kind", i32), ("c", u32), ("log_m", u32), ("log_r", u32)]
 
 
-KINDS = {"and": 0, "or": 1, "xor": 2, "lt": 3, "range": 4, "spark": 5}   # "spark" = LASSO_SPARK_UNCONFIRMED (include/lasso_hip.h): not in the reference snapshot
+class StrategyCustom(C.Structure):
+    """include/lasso_hip.h lasso_strategy_custom: a caller-defined strategy; passed as a pointer to its first member (see lasso_amd.custom.CustomStrategy)"""
+    _fields_ = [("base", Strategy), ("num_subtables", u32), ("num_memories", u32), ("tables_u32", C.POINTER(vp)), ("tables_fr", C.POINTER(vp)),
+                ("memory_subtable", vp), ("memory_dimension", vp), ("num_terms", u32), ("reserved", u32), ("coeff", vp), ("term_start", vp), ("term_mem", vp)]
+
+
+KINDS = {"and": 0, "or": 1, "xor": 2, "lt": 3, "range": 4, "spark": 5, "custom": 6}   # "spark" = LASSO_SPARK_UNCONFIRMED (include/lasso_hip.h): not in the reference snapshot
+CUSTOM_MAX_TERMS, CUSTOM_MAX_FACTORS, CUSTOM_MAX_DEGREE = 256, 2048, 17
 K_BIND, K_CUBIC, K_COMBINE, K_EQ, K_GP, K_FINGERPRINT, K_DOT, K_MATVEC, K_MSM, K_MISC, K_MSM_DIRECT, K_COUNT = range(12)
 KERNEL_NAMES = ["bind_top(+fused linear round)", "sumcheck_cubic_round(+fused bind)", "sumcheck_combine", "eq_evals", "gp_build", "fingerprint", "multi_dot", "matvec_left", "msm_commit(bucket)", "misc", "msm_opening(direct)"]
 

@@ -85,6 +85,8 @@ struct lasso_ctx {
   double prof_units2[LASSO_K_COUNT] = {0}; double big_units2[LASSO_K_COUNT] = {0};   // MSM families: mixed additions the kernel itself issues at most (one per scalar digit it looks at)
   double prof_units3[LASSO_K_COUNT] = {0}; double big_units3[LASSO_K_COUNT] = {0};   // MSM families: mixed additions EXECUTED, counted by the kernels (only while every launch is bracketed: no LASSO_PROF_LARGE_ONLY)
   uint32_t* d_prof_counts = nullptr;
+  // caller-defined strategies (LASSO_CUSTOM): the packed term list of the last descriptor seen, on the device; uploaded again only when the packed bytes change
+  void* d_terms = nullptr; std::vector<uint8_t> terms_host;
   void* rccl_comm = nullptr; int rccl_world = 0; int rccl_rank = -1;   // slab mode's device-side exchange (lasso_rccl_*): an ncclComm_t bound to this context's device and stream
   // device memory held through this context (lasso_mem_stats): lasso_alloc'd buffers, the context's scratch / result buffers and the generator tables built with it
   std::unordered_map<void*, size_t> mem_sizes; uint64_t mem_live = 0, mem_peak = 0; std::mutex mem_mu;   // bases tables may be built from another host thread (ensure_tab8)
@@ -537,6 +539,7 @@ void lasso_ctx_destroy(lasso_ctx* c) {
   if (c->d_flags) (void)hipFree(c->d_flags);
   if (c->d_counters) (void)hipFree(c->d_counters);
   if (c->d_prof_counts) (void)hipFree(c->d_prof_counts);
+  if (c->d_terms) (void)hipFree(c->d_terms);
   (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -1129,6 +1132,82 @@ static int32_t make_strategy(lasso_ctx* c, const lasso_strategy* s, StrategyDev&
   }
   return 0;
 }
+// ---- caller-defined strategies (include/lasso_hip.h lasso_strategy_custom): validate, pack the term list for the two kernels, keep it on the device
+#include "../../include/lasso_custom_check.h"
+static_assert(LASSO_CUSTOM_TERMS == LASSO_CUSTOM_MAX_TERMS && LASSO_CUSTOM_FACTORS == LASSO_CUSTOM_MAX_FACTORS && LASSO_CUSTOM_MAX_DEGREE == 17, "custom strategy caps");
+static fr_t lt_pow32(uint32_t e, bool inverse);
+// Q = max(longest term, 1): the number of u * u products on the longest path of the round kernel (k_combine_round_custom explains the coefficients and the fold marks)
+static int32_t pack_custom_terms(lasso_ctx* c, const lasso_strategy_custom* s, uint32_t& Q) {
+  const char* why = custom_strategy_check(s, 0);
+  if (why) return fail(c, LASSO_ERR_INVALID, why);
+  if (!bind_device(c)) return fail(c, LASSO_ERR_HIP, "hipSetDevice failed for the context's device");
+  std::vector<uint8_t> buf(sizeof(CustomTermsDev), 0);
+  CustomTermsDev* T = (CustomTermsDev*)buf.data();
+  T->num_terms = s->num_terms; T->num_factors = s->term_start[s->num_terms];
+  Q = custom_strategy_degree(s); if (Q < 1) Q = 1;
+  uint32_t budget = 0;   // bound on |v| / p before the current term (poly_kernels.cuh: magnitude of v)
+  for (uint32_t t = 0; t < s->num_terms; t++) {
+    const uint32_t L = s->term_start[t + 1] - s->term_start[t];
+    T->term_start[t] = (uint16_t)s->term_start[t];
+    const fr_t cf = to_fr(s->coeff + t);
+    const bool one = fr_eq(cf, fr_one()), unit = one && L == Q && L >= 2;
+    // cf_t = coeff_t 32^(L + 1 - Q) (a constant term: 32^(1 - Q), the same formula); fr_mul also brings a non-canonical coefficient into [0, p)
+    const uint32_t up = L + 1 >= Q ? L + 1 - Q : 0, down = L + 1 >= Q ? 0 : Q - L - 1;
+    T->coeff_round[t] = fr_mul(cf, up ? lt_pow32(up, false) : lt_pow32(down, true));
+    T->coeff_claim[t] = fr_mul(cf, fr_one());
+    const uint32_t mag = L == 0 ? 1 : L == 1 ? 19 : L == 2 ? (unit ? 12 : 4) : L == 3 ? 3 : 2;
+    if (budget + mag > 23) { T->flags[t - 1] |= 4; budget = 2; }   // t >= 1 here: no single term exceeds 23
+    budget += mag;
+    T->flags[t] = (uint8_t)((unit ? 1 : 0) | (one && L >= 1 ? 2 : 0));
+  }
+  T->term_start[s->num_terms] = (uint16_t)s->term_start[s->num_terms];
+  for (uint32_t j = 0; j < T->num_factors; j++) T->term_mem[j] = (uint8_t)s->term_mem[j];
+  if (c->d_terms && buf == c->terms_host) return 0;
+  // a new term list: nothing of this context may still be reading the old one
+  if (c->ahead_active || c->lay_active || c->tail_active || c->pending) return fail(c, LASSO_ERR_INVALID, "custom strategy: a new term list cannot be uploaded while a launch of this context is outstanding");
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!c->d_terms) HIPCHK(c, dmalloc(c, &c->d_terms, sizeof(CustomTermsDev)));
+  c->terms_host.clear();
+  HIPCHK(c, hipMemcpy(c->d_terms, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  c->terms_host.swap(buf);
+  return 0;
+}
+// the round kernel by sumcheck degree: (bound on the degree, lanes per index, several terms).  One term: DISPATCH_LT's table (at most 6 points per lane, two state elements per
+// point); several terms: at most 4 points per lane (three state elements per point: k_combine_round_custom, "Registers")
+#define DISPATCH_CUSTOM(degree, multi, FN) do { if (!(multi)) { if ((degree) <= 2) { FN(2, 1, false); } else if ((degree) <= 3) { FN(3, 1, false); } else if ((degree) <= 5) { FN(5, 1, false); } else if ((degree) <= 9) { FN(9, 2, false); } else { FN(17, 3, false); } } \
+  else if ((degree) <= 2) { FN(2, 1, true); } else if ((degree) <= 3) { FN(3, 1, true); } else if ((degree) <= 5) { FN(5, 2, true); } else if ((degree) <= 7) { FN(7, 2, true); } else if ((degree) <= 11) { FN(11, 3, true); } else { FN(17, 5, true); } } while (0)
+static int32_t combine_round_custom(lasso_ctx* c, const lasso_strategy_custom* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, uint32_t degree, lasso_fr* out) {
+  uint32_t Q = 1; int32_t rc = pack_custom_terms(c, s, Q); if (rc) return rc;
+  REQUIRE(c, d_polys && d_eq && out && n >= 2 && (n & (n - 1)) == 0);
+  REQUIRE(c, degree == custom_strategy_degree(s) + 1);   // sumcheck_poly_degree() = g_poly_degree() + 1: subtables/mod.rs:60-62
+  PtrTable P; for (uint32_t i = 0; i < s->num_memories; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
+  const size_t half = n / 2; const unsigned nx = grid_for(half, 1024); const uint32_t K = degree + 1;
+  rc = ensure_scratch(c, (size_t)nx * K * sizeof(fr_t)); if (rc) return rc;
+  rc = ensure_small(c, K); if (rc) return rc;
+  {
+    ProfScope ps(c, LASSO_K_COMBINE, 32.0 * n * (s->num_memories + 1.0));
+    const fr_t scale = lt_pow32(Q, false); const uint32_t nt = s->num_terms, nf = s->term_start[s->num_terms];
+#define LAUNCH_COMBINE_CUSTOM(D_, T_, M_) hipLaunchKernelGGL((k_combine_round_custom<D_, T_, M_>), dim3(nx), dim3(LASSO_BLOCK), 0, c->stream, P, (const fr_t*)d_eq, (const CustomTermsDev*)c->d_terms, nt, nf, scale, half, degree, (fr_t*)c->d_scratch)
+    DISPATCH_CUSTOM(degree, nt > 1, LAUNCH_COMBINE_CUSTOM);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)c->d_scratch, nx, K, c->d_small);
+  }
+  HIPCHK(c, hipGetLastError());
+  return fetch_small(c, K, out);
+}
+static int32_t combine_claim_custom(lasso_ctx* c, const lasso_strategy_custom* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, lasso_fr* out) {
+  uint32_t Q = 1; int32_t rc = pack_custom_terms(c, s, Q); if (rc) return rc;
+  REQUIRE(c, d_polys && d_eq && out && n >= 1);
+  PtrTable P; for (uint32_t i = 0; i < s->num_memories; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
+  const unsigned nx = grid_for(n, 1024);
+  rc = ensure_scratch(c, (size_t)nx * sizeof(fr_t)); if (rc) return rc;
+  {
+    ProfScope ps(c, LASSO_K_COMBINE, 32.0 * n * (s->num_memories + 1.0));
+    hipLaunchKernelGGL(k_combine_claim_custom, dim3(nx), dim3(LASSO_BLOCK), 0, c->stream, P, (const fr_t*)d_eq, (const CustomTermsDev*)c->d_terms, s->num_terms, s->term_start[s->num_terms], n, (fr_t*)c->d_scratch);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)c->d_scratch, nx, 1u, c->d_small);
+  }
+  HIPCHK(c, hipGetLastError());
+  return fetch_small(c, 1, out);
+}
 #define DISPATCH_A(alpha, FN) do { if ((alpha) <= 2) { FN(2, 2); } else if ((alpha) <= 4) { FN(4, 3); } else if ((alpha) <= 8) { FN(8, 5); } else if ((alpha) <= 16) { FN(16, 9); } else { FN(32, 17); } } while (0)
 // the LT round kernel: (bound on NUM_MEMORIES, bound on the degree, lanes per index) — at most 6 evaluation points per lane
 #define DISPATCH_LT(alpha, FN) do { if ((alpha) <= 2) { FN(2, 2, 1); } else if ((alpha) <= 4) { FN(4, 3, 1); } else if ((alpha) <= 8) { FN(8, 5, 1); } else if ((alpha) <= 16) { FN(16, 9, 2); } else { FN(32, 17, 3); } } while (0)
@@ -1169,6 +1248,7 @@ static int32_t combine_round_impl(lasso_ctx* c, const lasso_strategy* s, const l
   return fetch_small(c, K, out);
 }
 int32_t lasso_sumcheck_combine_round(lasso_ctx* c, const lasso_strategy* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, uint32_t degree, lasso_fr* out) {
+  if (s && s->kind == LASSO_CUSTOM) return combine_round_custom(c, (const lasso_strategy_custom*)s, d_polys, d_eq, n, degree, out);
   return combine_round_impl(c, s, d_polys, d_eq, n, degree, out, false);
 }
 int32_t lasso_sumcheck_combine_round_lt_scaled(lasso_ctx* c, const lasso_strategy* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, uint32_t degree, lasso_fr* out) {
@@ -1208,6 +1288,7 @@ int32_t lasso_lt_prescale(lasso_ctx* c, const lasso_strategy* s, const lasso_fr*
   HIPCHK(c, hipGetLastError()); return 0;
 }
 int32_t lasso_combine_claim(lasso_ctx* c, const lasso_strategy* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, lasso_fr* out) {
+  if (s && s->kind == LASSO_CUSTOM) return combine_claim_custom(c, (const lasso_strategy_custom*)s, d_polys, d_eq, n, out);
   StrategyDev S; WeightTable W; int32_t rc = make_strategy(c, s, S, W); if (rc) return rc;
   REQUIRE(c, d_polys && d_eq && out && n >= 1);
   PtrTable P; for (uint32_t i = 0; i < S.alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }

@@ -1255,6 +1255,164 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_lt_u32(StrategyDe
     }
   }
 }
+// K3 for a CALLER-DEFINED strategy (include/lasso_hip.h lasso_strategy_custom): g(v) = sum_t coeff_t prod_j v[mem_{t,j}], any sparse polynomial in the memories, degree <= 16.
+// The PROD walk above, term by term: per point a lane keeps the running sum over indices (sum), the value of g at the current index (v) and the current term (t); each factor's
+// line (lo, hi - lo) is STREAMED from memory when its term needs it and stepped from point to point by addition — a memory named by several terms is read again and hits L1 / L2.
+// No register array is indexed by a memory number: the term list lives in LDS (coefficients unpacked once per workgroup), is read at wave-uniform addresses, and the memory index
+// goes through readfirstlane so that the pointer comes out of the kernarg segment with a scalar load.
+// Radix.  Everything is u-form as in the LT kernel (its magnitude argument holds: lines stepped to x <= 17 from lazily reduced inputs, |t| <= 1.2 p after every product).  A term of
+// L >= 1 factors makes L - 1 products among its lines and the eq weight makes one more: the term arrives as value / 32^L.  With Q = max(longest term, 1) the block sums are multiplied
+// by 32^Q at the end (`scale`, as LT's) and the HOST folds the rest into the coefficient, once: cf_t = coeff_t 32^(L + 1 - Q) multiplies the term's first line — its two end points,
+// two products per index, not one per point — and a constant term is cf_t = coeff_t 32^(1 - Q) itself.  A term of length Q with coefficient 1 needs no product at all (`unit`):
+// g = prod_m E_m costs exactly what k_combine_round_lt<.., PROD> costs.
+// Magnitude of v.  A finished term is below, in units of p and for lazily reduced inputs at their bound 2^254 + 2^130 (curve25519's p = 2^252 is the worse case):
+//   constant 1;  one factor 19 (never `unit`: the product with cf is what brings the raw line, up to 72, down to 18 (p + X));  two factors 12 (unit: the product of two raw lines,
+//   (18 * 2^254)^2 / 2^261) or 4;  three 3;  four and more 2.
+// The host adds these up along the term list and marks the terms after which v must be folded (one product with 2^261: back below 2 p) so that |v| <= 23 p where the eq weight
+// multiplies it — inside the 24 p the LT kernel's accumulation bound (LT_FOLD_EVERY) was derived for.  pack_custom_terms (lasso_hip.hip) is that walk.
+#define LASSO_CUSTOM_TERMS 256     // LASSO_CUSTOM_MAX_TERMS
+#define LASSO_CUSTOM_FACTORS 2048  // LASSO_CUSTOM_MAX_FACTORS
+struct CustomTermsDev {            // device memory, packed by the host (pack_custom_terms)
+  uint32_t num_terms, num_factors;
+  uint16_t term_start[LASSO_CUSTOM_TERMS + 2];
+  uint8_t flags[LASSO_CUSTOM_TERMS];         // bit 0: round kernel, no coefficient product (`unit`); bit 1: claim kernel, coefficient 1; bit 2: round kernel, fold v after this term
+  uint8_t term_mem[LASSO_CUSTOM_FACTORS];
+  fr_t coeff_round[LASSO_CUSTOM_TERMS];      // cf_t above
+  fr_t coeff_claim[LASSO_CUSTOM_TERMS];      // coeff_t
+};
+struct CustomTermsLds { fr29 coeff[LASSO_CUSTOM_TERMS]; uint16_t term_start[LASSO_CUSTOM_TERMS + 2]; uint8_t flags[LASSO_CUSTOM_TERMS]; uint8_t term_mem[LASSO_CUSTOM_FACTORS]; };
+template <bool CLAIM>
+__device__ __forceinline__ void load_custom_terms(const CustomTermsDev* __restrict__ G, uint32_t nt, uint32_t nf, CustomTermsLds& L) {
+  for (uint32_t t = threadIdx.x; t < nt; t += blockDim.x) {
+    if (CLAIM) L.coeff[t] = G->term_start[t + 1] == G->term_start[t] ? fr29_unpack_u(G->coeff_claim[t]) : fr29_unpack_s(G->coeff_claim[t]);   // a constant term IS its coefficient (u-form); otherwise a multiplier (s-form)
+    else L.coeff[t] = fr29_unpack_u(G->coeff_round[t]);
+    L.flags[t] = G->flags[t];
+  }
+  for (uint32_t t = threadIdx.x; t <= nt; t += blockDim.x) L.term_start[t] = G->term_start[t];
+  for (uint32_t j = threadIdx.x; j < nf; j += blockDim.x) L.term_mem[j] = G->term_mem[j];
+  __syncthreads();
+}
+#define CU_REP(M) M(0) M(1) M(2) M(3) M(4) M(5)
+#define CU_DECL(k) fr29 sum##k = fr29_zero(), t##k = fr29_zero(), v##k = fr29_zero();
+#define CU_ZERO(k) if constexpr (k < PPG) v##k = fr29_zero();
+#define CU_CONST(k) if constexpr (k < PPG) t##k = cf;
+#define CU_TOP(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = cur; cur = lt_line_step(cur, dif); } }
+#define CU_MUL(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = fr29_mul(cur, t##k); cur = lt_line_step(cur, dif); } }
+#define CU_ADD(k) if constexpr (k < PPG) { if constexpr (MULTI) v##k = fr29_weak(fr29_add(v##k, t##k)); else v##k = t##k; }
+#define CU_VFOLD(k) if constexpr (k < PPG) v##k = fr29_mul(v##k, fr29_one_s());
+#define CU_ACC(k) if constexpr (k < PPG) { if (x0 + k <= degree) { sum##k = lt_weighted_acc(sum##k, ecur, v##k); ecur = lt_line_step(ecur, edif); } }
+#define CU_FOLD(k) if constexpr (k < PPG) sum##k = fr29_mul(sum##k, fr29_one_s());
+#define CU_OUT(k) if constexpr (k < PPG) mine[k] = fr29_mul(sum##k, sc);
+// D = bound on the sumcheck degree, T = lanes that share one index (the LT kernel's layout: PPG = ceil((D + 1) / T) <= 6 points per lane in named registers).
+// Registers.  Three state elements per point (sum, v, t) are 162 VGPRs at PPG = 6: with the working set of a product the compiler moved 30 - 108 of them to AGPRs and the
+// kernel dropped to one wave per SIMD.  So a list of SEVERAL terms runs with PPG <= 4 (more lanes per index: DISPATCH_CUSTOM in lasso_hip.hip), and a list of ONE term
+// (MULTI = false: v is t, nothing to add up or fold) keeps the LT kernel's table — the shape in which g = prod_m E_m is the PROD kernel instruction for instruction.
+template <int D, int T, bool MULTI>
+__global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_custom(PtrTable polys, const fr_t* __restrict__ eq, const CustomTermsDev* __restrict__ G, uint32_t nt, uint32_t nf, fr_t scale,
+                                                                      size_t half, uint32_t degree, fr_t* __restrict__ partials) {
+  constexpr int PPG = (D + 1 + T - 1) / T;
+  constexpr uint32_t SLOTS = LASSO_BLOCK / T;
+  static_assert(PPG <= 6, "CU_REP lists 6 points per lane");
+  __shared__ RedScratch R;
+  __shared__ CustomTermsLds L;
+  load_custom_terms<false>(G, nt, nf, L);
+  const uint32_t slot = threadIdx.x / T, pg = threadIdx.x - slot * T, x0 = pg * PPG;
+  CU_REP(CU_DECL)
+  uint32_t cnt = 0;
+  if (slot < SLOTS && x0 <= degree)
+  for (size_t i = blockIdx.x * (size_t)SLOTS + slot; i < half; i += (size_t)gridDim.x * SLOTS) {
+    if constexpr (MULTI) { CU_REP(CU_ZERO) }
+    for (uint32_t t = 0; t < (MULTI ? nt : 1u); t++) {
+      const uint32_t b = __builtin_amdgcn_readfirstlane(L.term_start[t]), e = __builtin_amdgcn_readfirstlane(L.term_start[t + 1]), fl = __builtin_amdgcn_readfirstlane(L.flags[t]);
+      if (b == e) { const fr29 cf = L.coeff[t]; CU_REP(CU_CONST) }   // a constant term
+      else {
+        {   // first factor: the term's line, times the folded coefficient unless that is 1
+          const fr_t* __restrict__ pm = polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[b])];
+          fr29 lo = fr29_unpack_u(pm[i]), dif = fr29_sub(fr29_unpack_u(pm[i + half]), lo);
+          if (!(fl & 1u)) { const fr29 cf = L.coeff[t]; lo = fr29_mul(lo, cf); dif = fr29_mul(dif, cf); }
+          fr29 cur = lt_line_at(lo, dif, x0);
+          CU_REP(CU_TOP)
+        }
+        for (uint32_t j = b + 1; j < e; j++) {   // t <- (E_m * t) / 32
+          const fr_t* __restrict__ pm = polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[j])];
+          const fr29 lo = fr29_unpack_u(pm[i]), dif = fr29_sub(fr29_unpack_u(pm[i + half]), lo);
+          fr29 cur = lt_line_at(lo, dif, x0);
+          CU_REP(CU_MUL)
+        }
+      }
+      CU_REP(CU_ADD)
+      if constexpr (MULTI) { if (fl & 4u) { CU_REP(CU_VFOLD) } }
+    }
+    {   // weight by the eq polynomial's line and accumulate over the indices
+      const fr29 e0 = fr29_unpack_u(eq[i]), edif = fr29_sub(fr29_unpack_u(eq[i + half]), e0);
+      fr29 ecur = lt_line_at(e0, edif, x0);
+      CU_REP(CU_ACC)
+    }
+    if (++cnt >= LT_FOLD_EVERY()) { cnt = 0; CU_REP(CU_FOLD) }
+  }
+  const fr29 sc = fr29_unpack_s(scale);   // u-form sums of (value / 32^Q) times the s-form of 32^Q: u-form of the value
+  fr29 mine[6];
+#pragma unroll
+  for (int k = 0; k < 6; k++) mine[k] = fr29_zero();
+  CU_REP(CU_OUT)
+  // block sums, one point group at a time, as k_combine_round_lt
+#pragma unroll
+  for (int g = 0; g < T; g++) {
+#pragma unroll
+    for (int k0 = 0; k0 < PPG; k0 += 3) {
+      fr29 grp[3];
+#pragma unroll
+      for (int v = 0; v < 3; v++) {
+        grp[v] = fr29_zero();
+        if (k0 + v < PPG) {
+#pragma unroll
+          for (int l = 0; l < 9; l++) grp[v].v[l] = pg == (uint32_t)g ? mine[k0 + v].v[l] : 0;
+        }
+      }
+      block_columns<3>(grp, R);
+      const uint32_t pt = (uint32_t)(g * PPG + k0) + threadIdx.x;
+      if (threadIdx.x < 3 && k0 + (int)threadIdx.x < PPG && pt <= degree) partials[(size_t)blockIdx.x * (degree + 1) + pt] = columns_to_fr(R, threadIdx.x, 0);
+    }
+  }
+}
+#undef CU_REP
+#undef CU_DECL
+#undef CU_ZERO
+#undef CU_CONST
+#undef CU_TOP
+#undef CU_MUL
+#undef CU_ADD
+#undef CU_VFOLD
+#undef CU_ACC
+#undef CU_FOLD
+#undef CU_OUT
+// K10 for a caller-defined strategy: claim = sum_k eq[k] g(E(k)) with the same term list.  A term starts as its first value in u-form and every further factor, the coefficient
+// multiply it in s-form; the eq weight is u-form and the block sum is corrected by 2^5 like the linear strategies'.  A finished term is below 4 p (a lone lazily reduced value) and otherwise below 2 p; g is
+// folded after every 4 terms: |g| < 18 p where eq multiplies it.
+__global__ void __launch_bounds__(LASSO_BLOCK) k_combine_claim_custom(PtrTable polys, const fr_t* __restrict__ eq, const CustomTermsDev* __restrict__ G, uint32_t nt, uint32_t nf, size_t n,
+                                                                      fr_t* __restrict__ partials) {
+  __shared__ RedScratch R;
+  __shared__ CustomTermsLds L;
+  load_custom_terms<true>(G, nt, nf, L);
+  fr29 acc[1] = {fr29_zero()}; uint32_t cnt = 0;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    fr29 g = fr29_zero();
+    for (uint32_t t = 0; t < nt; t++) {
+      const uint32_t b = __builtin_amdgcn_readfirstlane(L.term_start[t]), e = __builtin_amdgcn_readfirstlane(L.term_start[t + 1]);
+      fr29 term;
+      if (b == e) term = L.coeff[t];
+      else {
+        term = fr29_unpack_u(polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[b])][i]);
+        if (!(__builtin_amdgcn_readfirstlane(L.flags[t]) & 2u)) term = fr29_mul(term, L.coeff[t]);
+        for (uint32_t j = b + 1; j < e; j++) term = fr29_mul(fr29_unpack_s(polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[j])][i]), term);
+      }
+      g = fr29_weak(fr29_add(g, term));
+      if ((t & 3u) == 3u) g = fr29_mul(g, fr29_one_s());
+    }
+    acc_add(acc[0], fr29_mul(g, fr29_unpack_u(eq[i])), cnt);
+  }
+  store_block_partials<1>(acc, 1, partials + blockIdx.x, 5, R);   // u * u: 2^5 short
+}
 // K10: claim = sum_k eq[k] * g(E(k))  (subtables/mod.rs:187-216)
 template <int A>
 __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_claim(StrategyDev S, PtrTable polys, const fr_t* __restrict__ eq, WeightTable W, size_t n, fr_t* __restrict__ partials) {

@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 from . import _abi
+from .custom import strategy_ptr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -204,16 +205,16 @@ class Device:
 
     def sumcheck_combine_round(self, strategy, ptrs, d_eq, n, degree):
         out = np.empty((degree + 1, 4), dtype=np.uint64)
-        self._chk(self.lib.lasso_sumcheck_combine_round(self.ctx, C.byref(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
+        self._chk(self.lib.lasso_sumcheck_combine_round(self.ctx, strategy_ptr(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
         return out
 
     def lt_prescale(self, strategy, ptrs, n, src=None):
         """LT_m <- 32^-(C-1-m) LT_m (the form lasso_sumcheck_combine_round_lt_scaled takes); src: read from there instead (all 2C polynomials land in ptrs)"""
-        self._chk(self.lib.lasso_lt_prescale(self.ctx, C.byref(strategy), None if src is None else self._ptrs(src), self._ptrs(ptrs), n))
+        self._chk(self.lib.lasso_lt_prescale(self.ctx, strategy_ptr(strategy), None if src is None else self._ptrs(src), self._ptrs(ptrs), n))
 
     def sumcheck_combine_round_lt_scaled(self, strategy, ptrs, d_eq, n, degree):
         out = np.empty((degree + 1, 4), dtype=np.uint64)
-        self._chk(self.lib.lasso_sumcheck_combine_round_lt_scaled(self.ctx, C.byref(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
+        self._chk(self.lib.lasso_sumcheck_combine_round_lt_scaled(self.ctx, strategy_ptr(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
         return out
 
     def sumcheck_linear_eqw_round_u32(self, u32_ptrs, d_e, n):
@@ -229,12 +230,12 @@ class Device:
 
     def sumcheck_combine_round_lt_u32(self, strategy, u32_ptrs, d_eq, n, degree):
         out = np.empty((degree + 1, 4), dtype=np.uint64)
-        self._chk(self.lib.lasso_sumcheck_combine_round_lt_u32(self.ctx, C.byref(strategy), self._ptrs(u32_ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
+        self._chk(self.lib.lasso_sumcheck_combine_round_lt_u32(self.ctx, strategy_ptr(strategy), self._ptrs(u32_ptrs), C.c_void_p(d_eq), n, degree, _vp(out)))
         return out
 
     def combine_claim(self, strategy, ptrs, d_eq, n):
         out = np.empty((1, 4), dtype=np.uint64)
-        self._chk(self.lib.lasso_combine_claim(self.ctx, C.byref(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, _vp(out)))
+        self._chk(self.lib.lasso_combine_claim(self.ctx, strategy_ptr(strategy), self._ptrs(ptrs), C.c_void_p(d_eq), n, _vp(out)))
         return out
 
     def multi_dot(self, ptrs, d_w, n):
@@ -307,7 +308,7 @@ class Device:
     def materialize_subtable_u32(self, strategy, sub):
         m = 1 << strategy.log_m
         p = self.alloc(4 * m)
-        self._chk(self.lib.lasso_materialize_subtable_u32(self.ctx, C.byref(strategy), sub, C.c_void_p(p)))
+        self._chk(self.lib.lasso_materialize_subtable_u32(self.ctx, strategy_ptr(strategy), sub, C.c_void_p(p)))
         out = self.download(p, (m,), dtype=np.uint32)
         self.free(p)
         return out

@@ -22,6 +22,7 @@
 #include "field52.hpp"
 #include "hashes.hpp"
 #include "../../include/lasso_prover.h"
+#include "../../include/lasso_custom_check.h"
 
 #include <chrono>
 #include <cstdio>
@@ -465,29 +466,61 @@ struct SparsePolyCommitmentGens {  // surge.rs:25-59
 };
 
 // ------------------------------------------------------------------ strategies (host side of subtables/*.rs)
+static_assert(sizeof(lasso_strategy) == 16 && sizeof(lasso_strategy_custom) == 88 && offsetof(lasso_strategy_custom, base) == 0, "the custom descriptor starts with a lasso_strategy (integration/rust/hip.rs and lasso_amd/_abi.py mirror this layout)");
 struct Strategy {
   lasso_strategy abi;
-  Strategy(int kind, uint32_t c, uint32_t log_m, uint32_t log_r) { abi.kind = kind; abi.c = c; abi.log_m = log_m; abi.log_r = log_r; }
+  // A caller-defined strategy (kind = LASSO_CUSTOM, include/lasso_hip.h lasso_strategy_custom): the descriptor itself, validated once by from_abi.  Its pointers are the
+  // caller's (tables, maps, term list: valid for the duration of the call that brought them), so the struct is copied shallowly; nothing here outlives that call.
+  lasso_strategy_custom cabi;
+  Strategy(int kind, uint32_t c, uint32_t log_m, uint32_t log_r) : cabi() { abi.kind = kind; abi.c = c; abi.log_m = log_m; abi.log_r = log_r; }
+  // every entry point of the C ABI builds its Strategy here: for LASSO_CUSTOM the larger struct is read and checked (a bad descriptor throws before anything is launched)
+  static Strategy from_abi(const lasso_strategy* st) {
+    if (!st) throw Error("null strategy");
+    if (st->kind != LASSO_CUSTOM) return Strategy(st->kind, st->c, st->log_m, st->log_r);
+    const lasso_strategy_custom* cs = (const lasso_strategy_custom*)st;
+    if (const char* why = custom_strategy_check(cs, 1)) throw Error(why);
+    Strategy S(st->kind, st->c, st->log_m, 0); S.cabi = *cs; S.cabi.base = S.abi;
+    return S;
+  }
+  // what the device entry points that take a strategy receive (lasso_sumcheck_combine_round, lasso_combine_claim, ...)
+  const lasso_strategy* abi_ptr() const { return custom() ? &cabi.base : &abi; }
   size_t C() const { return abi.c; }
   size_t M() const { return (size_t)1 << abi.log_m; }
+  bool custom() const { return abi.kind == LASSO_CUSTOM; }
   bool spark() const { return abi.kind == LASSO_SPARK_UNCONFIRMED; }   // NOT in the reference snapshot: see include/lasso_hip.h lasso_strategy_kind
-  size_t num_subtables() const { return abi.kind == LASSO_LT ? 2 : abi.kind == LASSO_RANGE ? 3 : spark() ? C() : 1; }
-  size_t num_memories() const { return abi.kind == LASSO_LT ? 2 * C() : C(); }
-  bool linear() const { return abi.kind != LASSO_LT && !spark(); }   // g = sum_k 2^(k*inc) E_k: and.rs:45-53, range_check.rs:78-86
-  bool integer_tables() const { return !spark(); }                  // every subtable of the snapshot holds small integers (u32 on the device); Spark's hold field elements
-  ScVec weights() const { ScVec w; size_t inc = abi.kind == LASSO_RANGE ? abi.log_m : abi.log_m / 2; for (size_t i = 0; i < num_memories(); i++) { LASSO_REQUIRE(i * inc < 64); w.push_back(Sc::from_u64((uint64_t)1 << (i * inc))); } return w; }
-  size_t sumcheck_poly_degree() const { return (abi.kind == LASSO_LT || spark() ? C() : 1) + 1; }
+  // a caller-defined g that is not linear: the route Spark takes (clone, no prescale, lasso_sumcheck_combine_round every round)
+  bool general() const { return custom() && !linear(); }
+  size_t num_subtables() const { return custom() ? cabi.num_subtables : abi.kind == LASSO_LT ? 2 : abi.kind == LASSO_RANGE ? 3 : spark() ? C() : 1; }
+  size_t num_memories() const { return custom() ? cabi.num_memories : abi.kind == LASSO_LT ? 2 * C() : C(); }
+  // g = sum_k w_k E_k: and.rs:45-53, range_check.rs:78-86; a caller-defined g whose every term has exactly one factor (a constant term makes it non-linear for this purpose)
+  bool linear() const {
+    if (custom()) { for (uint32_t t = 0; t < cabi.num_terms; t++) if (cabi.term_start[t + 1] - cabi.term_start[t] != 1) return false; return true; }
+    return abi.kind != LASSO_LT && !spark();
+  }
+  bool integer_tables() const { return custom() ? cabi.tables_u32 != nullptr : !spark(); }   // every subtable of the snapshot holds small integers (u32 on the device); Spark's hold field elements
+  ScVec weights() const {
+    ScVec w;
+    if (custom()) {   // linear(): the coefficients of a memory named by several terms add up; a memory named by none has weight 0
+      w.assign(num_memories(), Sc::zero());
+      for (uint32_t t = 0; t < cabi.num_terms; t++) w[cabi.term_mem[cabi.term_start[t]]] += Sc::from_abi(cabi.coeff[t]);
+      return w;
+    }
+    size_t inc = abi.kind == LASSO_RANGE ? abi.log_m : abi.log_m / 2; for (size_t i = 0; i < num_memories(); i++) { LASSO_REQUIRE(i * inc < 64); w.push_back(Sc::from_u64((uint64_t)1 << (i * inc))); } return w;
+  }
+  size_t sumcheck_poly_degree() const { return custom() ? custom_strategy_degree(&cabi) + 1 : (abi.kind == LASSO_LT || spark() ? C() : 1) + 1; }
   size_t memory_to_subtable_index(size_t i) const {
+    if (custom()) return cabi.memory_subtable ? cabi.memory_subtable[i] : i % cabi.num_subtables;
     if (abi.kind == LASSO_RANGE) { size_t lm = abi.log_m; if (i * lm > abi.log_r) return 2; return ((i + 1) * lm > abi.log_r) ? 1 : 0; }  // range_check.rs:62-69
     return i % num_subtables();                                                                                                        // subtables/mod.rs:64-68 (Spark: i)
   }
-  size_t memory_to_dimension_index(size_t i) const { return abi.kind == LASSO_RANGE || spark() ? i : i / num_subtables(); }             // mod.rs:70-74, range_check.rs:71-73
+  size_t memory_to_dimension_index(size_t i) const { if (custom()) return cabi.memory_dimension ? cabi.memory_dimension[i] : i / cabi.num_subtables; return abi.kind == LASSO_RANGE || spark() ? i : i / num_subtables(); }             // mod.rs:70-74, range_check.rs:71-73
   // Spark (unconfirmed): subtable i = EqPolynomial(tau_i).evals(); the snapshot's trait has no per-proof table parameter, so tau is fixed by the strategy:
   // C * log2(M) draws of F::rand from a fresh ark_std::test_rng(), tau_i = draws [i log M, (i + 1) log M)
   std::vector<ScVec> spark_point() const;
   // materialize_subtables: every table of the reference holds small integers, so the host builds u32 and the device lifts to Fr
   // largest entry of any subtable (bounds the scalars of E's commitment): l op r < 2^(log_m / 2); LT / EQ are bits; range tables hold indices
   uint32_t max_table_value() const {
+    if (custom()) { uint32_t mx = 0; if (cabi.tables_u32) for (uint32_t k = 0; k < cabi.num_subtables; k++) for (size_t i = 0; i < M(); i++) mx = std::max(mx, cabi.tables_u32[k][i]); return mx; }
     if (abi.kind == LASSO_LT) return 1;
     if (abi.kind == LASSO_RANGE) return (uint32_t)(M() - 1);
     return (uint32_t)(((size_t)1 << (abi.log_m / 2)) - 1);
@@ -841,7 +874,7 @@ class Prover {
     std::vector<const lasso_fr*> cp(polys.begin(), polys.begin() + alpha);
     for (size_t round = 0; round < rounds; round++) {
       std::vector<lasso_fr> ev(combined_degree + 1);
-      if (S.spark()) d.chk(lasso_sumcheck_combine_round(d.ctx, &S.abi, cp.data(), polys[alpha], len, (uint32_t)combined_degree, ev.data()), "lasso_sumcheck_combine_round");   // g = prod E_m: nothing is pre-scaled
+      if (S.spark() || S.general()) d.chk(lasso_sumcheck_combine_round(d.ctx, S.abi_ptr(), cp.data(), polys[alpha], len, (uint32_t)combined_degree, ev.data()), "lasso_sumcheck_combine_round");   // g = prod E_m, or the caller's term list: nothing is pre-scaled
       else if (round == 0 && first_u32) d.chk(lasso_sumcheck_combine_round_lt_u32(d.ctx, &S.abi, first_u32->data(), polys[alpha], len, (uint32_t)combined_degree, ev.data()), "lasso_sumcheck_combine_round_lt_u32");
       else d.chk(lasso_sumcheck_combine_round_lt_scaled(d.ctx, &S.abi, cp.data(), polys[alpha], len, (uint32_t)combined_degree, ev.data()), "lasso_sumcheck_combine_round_lt_scaled");
       if (reduce) d.comm.sum(ev);
@@ -994,7 +1027,7 @@ class Prover {
       return proof;
     }
     // the caller's work arrays, once (slab mode: the local arrays; the replicated tails are gathered from them).  With src the call also IS the clone of the lookup polynomials
-    if (S.spark()) { if (src) for (size_t i = 0; i < alpha; i++) d.chk(lasso_copy(d.ctx, polys[i], (*src)[i], len_loc * sizeof(lasso_fr)), "lasso_copy"); }   // the clone of surge.rs:151
+    if (S.spark() || S.general()) { if (src) for (size_t i = 0; i < alpha; i++) d.chk(lasso_copy(d.ctx, polys[i], (*src)[i], len_loc * sizeof(lasso_fr)), "lasso_copy"); }   // the clone of surge.rs:151
     else d.chk(lasso_lt_prescale(d.ctx, &S.abi, src ? src->data() : nullptr, polys.data(), len_loc), "lasso_lt_prescale");
     if (P == 1) { arbitrary_rounds(num_rounds, len_loc, polys, combined_degree, false, proof, r_out, src_u32); read_heads(polys); return proof; }
     LASSO_REQUIRE(num_rounds >= lgP && ((size_t)1 << (num_rounds - lgP)) == len_loc);
@@ -1750,6 +1783,11 @@ class Prover {
     // the subtables as integers, written by the device (64 K entries each: nothing to compute on the host and upload); they stay until E is
     // committed (the commitment's scalars are T[dim] as integers)
     std::vector<DBufU32> tables_u32; const bool ints = S.integer_tables(); const uint32_t table_max = ints ? S.max_table_value() : 0;
+    if (S.custom()) for (size_t i = 0; i < S.num_subtables(); i++) {   // the caller's tables are uploaded instead of materialised
+      tables.emplace_back(d, m);
+      if (ints) { tables_u32.emplace_back(d, m); d.chk(lasso_upload(d.ctx, tables_u32.back().p, S.cabi.tables_u32[i], m * sizeof(uint32_t)), "lasso_upload"); }
+      else d.chk(lasso_upload(d.ctx, tables.back().p, S.cabi.tables_fr[i], m * sizeof(lasso_fr)), "lasso_upload");
+    } else
     if (ints) for (size_t i = 0; i < S.num_subtables(); i++) {
       tables_u32.emplace_back(d, m); tables.emplace_back(d, m);
       d.chk(lasso_materialize_subtable_u32(d.ctx, &S.abi, (uint32_t)i, tables_u32.back().p), "lasso_materialize_subtable_u32");
@@ -1805,7 +1843,7 @@ class Prover {
     std::vector<const lasso_fr*> Eptr; for (size_t i = 0; i < alpha; i++) Eptr.push_back(E(i));
     std::vector<lasso_fr> claim_abi(1);
     d.chk(lasso_defer_next(d.ctx), "lasso_defer_next");
-    d.chk(lasso_combine_claim(d.ctx, &S.abi, Eptr.data(), eq.p, s_loc, claim_abi.data()), "lasso_combine_claim");
+    d.chk(lasso_combine_claim(d.ctx, S.abi_ptr(), Eptr.data(), eq.p, s_loc, claim_abi.data()), "lasso_combine_claim");
     t.append_message("subtable_evals_commitment", "begin_subtable_evals_commitment");
     append_poly_commitment(t, "comm_poly_row_col_ops_val", comm_derefs);
     t.append_message("subtable_evals_commitment", "end_subtable_evals_commitment");

@@ -145,9 +145,18 @@ int32_t lasso_host_commit(lasso_host_dense* d, lasso_host_gens* g, uint8_t* out,
 }
 // one proof (capacity mode's bound on what stays parked between proofs is in Dev::alloc_bytes: returning everything to the driver here was measured at 1.4 s per proof
 // of hipFree / hipMalloc at configs[3])
+// A caller-defined strategy states its own NUM_MEMORIES: the derefs generators must have been made for it (surge.rs:39-47) — found here, before anything is launched,
+// instead of at batch_commit's assert in the middle of the proof
+static void check_custom_gens(const Strategy& S, const SparsePolyCommitmentGens& G, size_t s) {
+  if (!S.custom()) return;
+  const size_t nv = ceil_log2(next_pow2(S.num_memories() * next_pow2(s)));
+  if (G.gens_derefs.n != ((size_t)1 << (nv - nv / 2))) throw Error("custom strategy: num_memories does not match the generators (gens_derefs was made for another number of memories or lookups)");
+}
 static std::vector<uint8_t> run_prover(lasso_host* h, const Strategy& S, DensifiedRepresentation& D, const SparsePolyCommitmentGens& G, ProofTranscript& t, RandomTape& tape, const ScVec& rv) {
   std::vector<uint8_t> bytes;
   {
+    if (S.custom() && (S.C() != D.C || S.M() != D.m)) throw Error("custom strategy: c / log_m do not match the densified representation");
+    check_custom_gens(S, G, D.s);
     Prover P(h->dev, S, D, G, t, tape);
     try { P.prove(rv); } catch (...) { h->dev.abort_all(); throw; }
     bytes.swap(P.proof_bytes);
@@ -157,7 +166,7 @@ static std::vector<uint8_t> run_prover(lasso_host* h, const Strategy& S, Densifi
 int32_t lasso_host_prove(lasso_host* h, lasso_host_dense* d, lasso_host_gens* g, const lasso_strategy* st, const lasso_fr* r, size_t r_len, const char* tl, const char* pl,
                          uint8_t* out, size_t cap, size_t* len) {
   GUARD(
-    Strategy S(st->kind, st->c, st->log_m, st->log_r);
+    Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tl); RandomTape tape(pl);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     std::vector<uint8_t> bytes = run_prover(h, S, *d->d, *g->g, t, tape, rv);
@@ -184,7 +193,7 @@ int32_t lasso_host_prove_cb(lasso_host* h, lasso_host_dense* d, lasso_host_gens*
                             const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, uint8_t* out, size_t cap, size_t* len) {
   GUARD(
     if (!h || !d || !g || !st || !r || !tv || !pv) throw Error("lasso_host_prove_cb: null argument");
-    Strategy S(st->kind, st->c, st->log_m, st->log_r);
+    Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     std::vector<uint8_t> bytes = run_prover(h, S, *d->d, *g->g, t, tape, rv);
@@ -194,9 +203,10 @@ int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_stra
                              const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
   GUARD(
     if (!h || !g || !st || !r || !proof || !commitment || !ok || !tv) throw Error("lasso_host_verify_cb: null argument");
-    Strategy S(st->kind, st->c, st->log_m, st->log_r);
+    Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tv, tu);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    check_custom_gens(S, *g->g, s);
     Verifier V(h->dev, S, *g->g, t);
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     return 0;)
@@ -205,9 +215,10 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
                           const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
   GUARD(
     if (!h || !g || !st || !r || !proof || !commitment || !ok) throw Error("lasso_host_verify: null argument");
-    Strategy S(st->kind, st->c, st->log_m, st->log_r);
+    Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tl);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    check_custom_gens(S, *g->g, s);
     Verifier V(h->dev, S, *g->g, t);
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     return 0;)
@@ -219,7 +230,7 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
 int32_t lasso_host_debug_cubic_batched(lasso_host* h, lasso_host_dense* dn, lasso_host_gens* g, const lasso_strategy* st, size_t k, size_t ell, const lasso_fr* A, const lasso_fr* B,
                                        const lasso_fr* rand, const lasso_fr* coeffs, const lasso_fr* claim, const char* tl, uint8_t* out, size_t cap, size_t* len) {
   try {
-    Strategy S(st->kind, st->c, st->log_m, st->log_r);
+    Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tl); RandomTape tape("unused");
     Prover P(h->dev, S, *dn->d, *g->g, t, tape);
     const size_t n = (size_t)1 << ell;
@@ -250,6 +261,9 @@ int32_t lasso_host_debug_cubic_batched(lasso_host* h, lasso_host_dense* dn, lass
     w.sc_arr(r_out); w.sc_arr(ca); w.sc_arr(cb);
     return emit(w.b, out, cap, len);
   } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
+}
+int32_t lasso_host_strategy_check(const lasso_strategy* st) {
+  GUARD(const Strategy S = Strategy::from_abi(st); (void)S; return 0;)
 }
 void lasso_host_gen_indices(size_t sparsity, size_t memory_size, uint64_t* out) { ChaChaRng rng = ChaChaRng::test_rng(); for (size_t i = 0; i < sparsity; i++) out[i] = rng.next_u64() % memory_size; }
 void lasso_host_gen_random_point(size_t bits, lasso_fr* out) { ChaChaRng rng = ChaChaRng::test_rng(); for (size_t i = 0; i < bits; i++) out[i] = fr_rand(rng).abi(); }

@@ -129,8 +129,17 @@ inline WireProof read_proof(const Strategy& S, const uint8_t* bytes, size_t n) {
 }
 
 // ------------------------------------------------------------------ host side of SubtableStrategy the verifier needs (subtables/*.rs)
+// A caller-defined table has no closed form: its MLE at a point is the dot product of the table with EqPolynomial(point).evals() (2^log_m products, on the host).  The
+// tables are part of the STATEMENT — fixed by the strategy prover and verifier agreed on, never taken from the prover (include/lasso_hip.h lasso_strategy_custom).
 inline Sc evaluate_subtable_mle(const Strategy& S, size_t k, const ScVec& point) {
   const int kind = S.abi.kind; const size_t n = point.size();
+  if (kind == LASSO_CUSTOM) {
+    LASSO_REQUIRE(k < S.cabi.num_subtables && n == S.abi.log_m);
+    const ScVec chi = eq_evals_host(point.data(), n); Sc res = Sc::zero();
+    if (S.cabi.tables_u32) { const uint32_t* T = S.cabi.tables_u32[k]; for (size_t i = 0; i < chi.size(); i++) if (T[i]) res += chi[i] * Sc::from_u64(T[i]); }
+    else { const lasso_fr* T = S.cabi.tables_fr[k]; for (size_t i = 0; i < chi.size(); i++) res += chi[i] * Sc::from_abi(T[i]); }
+    return res;
+  }
   if (kind == LASSO_SPARK_UNCONFIRMED) {   // the MLE of eq(tau_k, .) at a point is eq(tau_k, point) (eq_poly.rs:14-20)
     const std::vector<ScVec> tau = S.spark_point(); LASSO_REQUIRE(k < tau.size() && n == tau[k].size());
     Sc res = Sc::one();
@@ -162,6 +171,11 @@ inline Sc evaluate_subtable_mle(const Strategy& S, size_t k, const ScVec& point)
   return res;
 }
 inline Sc combine_lookups(const Strategy& S, const ScVec& vals) {
+  if (S.custom()) {   // the caller's term list: g(v) = sum_t coeff_t prod_j v[mem_{t,j}]
+    Sc sum = Sc::zero();
+    for (uint32_t t = 0; t < S.cabi.num_terms; t++) { Sc term = Sc::from_abi(S.cabi.coeff[t]); for (uint32_t j = S.cabi.term_start[t]; j < S.cabi.term_start[t + 1]; j++) term *= vals[S.cabi.term_mem[j]]; sum += term; }
+    return sum;
+  }
   if (S.spark()) { Sc prod = Sc::one(); for (size_t i = 0; i < S.C(); i++) prod *= vals[i]; return prod; }
   if (S.abi.kind == LASSO_LT) {   // lt.rs:62-71
     Sc sum = Sc::zero(), eq = Sc::one();
@@ -352,9 +366,11 @@ class Verifier {
     for (size_t i = 0; i < rand_mem.size(); i++) init_addr += Sc::from_u64((uint64_t)1 << (rand_mem.size() - i - 1)) * rand_mem[i];
     const Sc g2 = gamma.square();
     auto h = [&](const Sc& a, const Sc& v, const Sc& ts) { return ts * g2 + v * gamma + a - tau; };
+    std::map<size_t, Sc> mle_of;   // one evaluation per subtable, not per memory (a caller-defined table costs 2^log_m products)
     for (size_t i = 0; i < alpha; i++) {
       const size_t j = S.memory_to_dimension_index(i), k = S.memory_to_subtable_index(i);
-      const Sc init_memory = evaluate_subtable_mle(S, k, rand_mem);
+      if (!mle_of.count(k)) mle_of[k] = evaluate_subtable_mle(S, k, rand_mem);
+      const Sc init_memory = mle_of[k];
       if (!(h(init_addr, init_memory, Sc::zero()) == claims_mem[2 * i])) return false;                                              // init
       if (!(h(P.eval_dim[j], P.eval_derefs_hash[i], P.eval_read[j]) == claims_ops[2 * i])) return false;                           // read
       if (!(h(P.eval_dim[j], P.eval_derefs_hash[i], P.eval_read[j] + Sc::one()) == claims_ops[2 * i + 1])) return false;           // write

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from . import _abi
+from .custom import strategy_ptr
 from .device import LassoError
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +64,7 @@ def declare_prover(lib):
     lib.lasso_host_random_tape_new.argtypes = [C.c_char_p]; lib.lasso_host_random_tape_new.restype = vp
     lib.lasso_host_merlin_free.argtypes = [vp]
     lib.lasso_host_merlin_vtbl.argtypes = []; lib.lasso_host_merlin_vtbl.restype = vt
+    lib.lasso_host_strategy_check.argtypes = [C.POINTER(_abi.Strategy)]
     lib.lasso_host_gen_indices.argtypes = [sz, sz, vp]
     lib.lasso_host_gen_random_point.argtypes = [sz, vp]
     return lib
@@ -160,18 +162,18 @@ class HostProver:
 
     def prove(self, dense, gens, strategy, r, transcript=b"example", tape=b"proof"):
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
-        return self._bytes_call(self.lib.lasso_host_prove, self.h, dense, gens, C.byref(strategy), r.ctypes.data_as(C.c_void_p), r.shape[0], transcript, tape)
+        return self._bytes_call(self.lib.lasso_host_prove, self.h, dense, gens, strategy_ptr(strategy), r.ctypes.data_as(C.c_void_p), r.shape[0], transcript, tape)
 
     def prove_with(self, dense, gens, strategy, r, transcript, tape):
         """SparsePolynomialEvaluationProof::prove against LIVE transcripts (surge.rs:119-125 `&mut Transcript`, `&mut RandomTape`): `transcript` / `tape` are
         (vtbl pointer, user pointer) pairs — lasso_host_prove_cb; see Transcript below for the library's own Merlin behind that interface"""
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
-        return self._bytes_call(lambda *a: self.lib.lasso_host_prove_cb(self.h, dense, gens, C.byref(strategy), r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1], *a))
+        return self._bytes_call(lambda *a: self.lib.lasso_host_prove_cb(self.h, dense, gens, strategy_ptr(strategy), r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1], *a))
 
     def verify_with(self, gens, strategy, s, r, proof, commitment, transcript):
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         ok = C.c_int32(-1)
-        self._chk(self.lib.lasso_host_verify_cb(self.h, gens, C.byref(strategy), s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], proof, len(proof), commitment, len(commitment), C.byref(ok)))
+        self._chk(self.lib.lasso_host_verify_cb(self.h, gens, strategy_ptr(strategy), s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], proof, len(proof), commitment, len(commitment), C.byref(ok)))
         return ok.value == 1
 
     def verify(self, gens, strategy, s, r, proof, commitment, transcript=b"example"):
@@ -179,8 +181,12 @@ class HostProver:
         that do not deserialize or on shapes the reference would assert on."""
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         ok = C.c_int32(-1)
-        self._chk(self.lib.lasso_host_verify(self.h, gens, C.byref(strategy), s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript, proof, len(proof), commitment, len(commitment), C.byref(ok)))
+        self._chk(self.lib.lasso_host_verify(self.h, gens, strategy_ptr(strategy), s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript, proof, len(proof), commitment, len(commitment), C.byref(ok)))
         return ok.value == 1
+
+    def strategy_check(self, strategy):
+        """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
+        self._chk(self.lib.lasso_host_strategy_check(strategy_ptr(strategy)))
 
     def debug_cubic_batched(self, dense, gens, strategy, A, B, rand, coeffs, claim, transcript=b"test"):
         """test support: prove_cubic_batched on caller arrays with a scripted eq point (lasso_host_debug_cubic_batched)"""
@@ -190,7 +196,7 @@ class HostProver:
         claim = np.ascontiguousarray(claim, dtype=np.uint64).reshape(4)
         assert rand.shape[0] == ell and coeffs.shape[0] == k and B.shape == A.shape
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        return self._bytes_call(self.lib.lasso_host_debug_cubic_batched, self.h, dense, gens, C.byref(strategy), k, ell, vp(A), vp(B), vp(rand), vp(coeffs), vp(claim), transcript)
+        return self._bytes_call(self.lib.lasso_host_debug_cubic_batched, self.h, dense, gens, strategy_ptr(strategy), k, ell, vp(A), vp(B), vp(rand), vp(coeffs), vp(claim), transcript)
 
     def free(self, dense=None, gens=None):
         if dense:
