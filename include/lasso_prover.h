@@ -145,6 +145,18 @@ void lasso_host_gen_random_point(size_t bits, lasso_fr* out);
  * that trips one of the reference's assert!s on shapes, returns -1 with the reason in lasso_host_last_error(). */
 int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strategy* strategy, size_t s, const lasso_fr* r, size_t r_len, const char* transcript_label,
                           const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok);
+/* ark-serialize compressed points (the encoding of every commitment row and of every L / R / delta / beta of a proof; a Rust caller's serialize_compressed) decoded and
+ * validated as deserialize_compressed with Validate::Yes does: wire32 = n x 32 bytes in; per point a lasso_wire_status (include/lasso_hip_wire.h: ok, ok-identity,
+ * non-canonical, bad flags, not on the curve, not in the subgroup), the affine point in the form lasso_bases_create / lasso_host_gens_from_points take, and the 32 canonical
+ * bytes of the decoded point (what a transcript absorbs); out and canon32 may be NULL; rejected encodings leave zeros.  where = 0: on the host, one point after the other
+ * (the verifier's own decoder); where = 1: on the device, all points in one launch (lasso_points_decompress) — -1 with a message when the device library this host was linked
+ * against does not have it.  Returns 0 even when some encodings are invalid: the per-point outcome is in status.
+ * lasso_host_verify* decodes a proof's and a commitment's points through the device call when it exists and the batch has at least LASSO_WIRE_DEVICE_MIN points;
+ * LASSO_VERIFY_DEVICE_POINTS=0 keeps the host decoder.  Verdicts, return codes and error texts do not depend on the path. */
+int32_t lasso_host_points_decompress(lasso_host* h, const uint8_t* wire32, size_t n, int32_t where, lasso_affine* out, uint8_t* canon32, uint8_t* status);
+/* *device_points = compressed points this host has decoded on the device so far (verifier and lasso_host_points_decompress(where = 1) together);
+ * *device_available = 1 when the device decoder exists; either may be NULL; reset != 0 zeroes the counter. */
+int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* device_available, int32_t reset);
 /* Validate a strategy descriptor without proving anything: 0, or LASSO_ERR_INVALID (-1) with the reason in lasso_host_last_error().  For kind = LASSO_CUSTOM
  * (include/lasso_hip.h lasso_strategy_custom, passed as (const lasso_strategy*)&custom) this is the check lasso_host_prove* / lasso_host_verify* make on entry: table pointers,
  * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (2^log_m products per memory): THE TABLES ARE PART OF THE STATEMENT,

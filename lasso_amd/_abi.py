@@ -147,4 +147,16 @@ def declare(lib):
     return sorted(sig)
 
 
+WIRE_STATUS = ["ok", "ok-identity", "non-canonical", "bad-flags", "not-on-curve", "not-in-subgroup"]   # include/lasso_hip_wire.h lasso_wire_status
+
+
+def declare_wire(lib):
+    """include/lasso_hip_wire.h — the device decoder of compressed points.  Declared apart from declare(): an implementation of lasso_hip.h alone (the tests' mock) does
+    not have it.  AttributeError = the library does not export it."""
+    fn = lib.lasso_points_decompress
+    fn.restype = i32
+    fn.argtypes = [vp, vp, sz, vp, vp, vp]
+    return ["lasso_points_decompress"]
+
+
 HEADER_SYMBOLS = None

@@ -9,6 +9,7 @@
 //                         "loose"    <= 2^30 + 2^16   (one add/sub of reduced values)
 // fe_mul(a, b) requires a loose, b reduced: 9 products of <= 2^59.01 stay below 2^63.
 #pragma once
+#include "../../include/lasso_hip_wire.h"   // lasso_wire_status: what pt_decompress returns
 #ifdef LASSO_BN254
 #include "bn254_fe29.cuh"   // the same interface over ark-bn254's Fq and G1
 #else
@@ -271,6 +272,79 @@ LHD void pt_compress(const pt29& p, uint32_t* out) {
   if (neg) out[7] |= 0x80000000u;
 }
 LHD ed_point pt_to_ed(const pt29& p) { ed_point e; e.X = fe_to_fq(p.X); e.Y = fe_to_fq(p.Y); e.T = fe_to_fq(p.T); e.Z = fe_to_fq(p.Z); return e; }
+
+// ------------------------------------------------------------------ the reading half of the wire format (include/lasso_hip_wire.h)
+// a^(2^252 - 3) = a^((p - 5) / 8): fe_inv_chain's chain up to 2^250 - 1, two squarings and one product (252 squarings + 11 multiplications); a reduced
+LHD fe29 fe_pow22523(const fe29& z) {
+  fe29 z2 = fe_sqr(z);
+  fe29 z8 = fe_sqr(fe_sqr(z2));
+  fe29 z9 = fe_mul(z8, z);
+  fe29 z11 = fe_mul(z9, z2);
+  fe29 z22 = fe_sqr(z11);
+  fe29 z_5_0 = fe_mul(z22, z9);
+  fe29 t = z_5_0; for (int i = 0; i < 5; i++) t = fe_sqr(t);
+  fe29 z_10_0 = fe_mul(t, z_5_0);
+  t = z_10_0; for (int i = 0; i < 10; i++) t = fe_sqr(t);
+  fe29 z_20_0 = fe_mul(t, z_10_0);
+  t = z_20_0; for (int i = 0; i < 20; i++) t = fe_sqr(t);
+  t = fe_mul(t, z_20_0);
+  for (int i = 0; i < 10; i++) t = fe_sqr(t);
+  fe29 z_50_0 = fe_mul(t, z_10_0);
+  t = z_50_0; for (int i = 0; i < 50; i++) t = fe_sqr(t);
+  fe29 z_100_0 = fe_mul(t, z_50_0);
+  t = z_100_0; for (int i = 0; i < 100; i++) t = fe_sqr(t);
+  t = fe_mul(t, z_100_0);
+  for (int i = 0; i < 50; i++) t = fe_sqr(t);
+  t = fe_mul(t, z_50_0);                              // 2^250 - 1
+  t = fe_sqr(fe_sqr(t));                              // 2^252 - 4
+  return fe_mul(t, z);
+}
+LHD bool fe_is_zero(const fe29& a) { return fq_is_zero(fe_to_fq(a)); }   // a loose
+// ark-ec's deserialize_compressed with Validate::Yes for a twisted-Edwards point, the mirror of decompress_point in lasso_amd/host/verifier.hpp: in = 8 little-endian
+// words (canonical y, bit 255 = "x is the larger root").  Returns a lasso_wire_status; on LASSO_WIRE_OK aff = the affine point as lasso_affine holds it (x then y, 8 words
+// each, ark-ff's Montgomery limbs) and canon = serialize_compressed of the decoded point (differs from `in` only for x = 0 with the flag set); all zero otherwise.
+//   x^2 = (1 - y^2) / (-1 - d y^2) = u / v with u = y^2 - 1, v = d y^2 + 1.  ONE power chain serves the inversion and the root (p = 5 mod 8):
+//   x = u v^3 (u v^7)^((p-5)/8) has v x^2 = +-u when u / v is a square; the minus case is mended by sqrt(-1).  Which of the two roots the chain lands on does not
+//   matter: the flag picks one by comparing the canonical integers x and p - x, exactly as `(neg == x_larger) ? x : nx` does.
+//   Subgroup: [l]P == O by double-and-add over the fixed bits of l = 2^252 + 27742317777372353535851937790883648493 (252 doublings, 65 additions).
+LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
+  for (int i = 0; i < 16; i++) aff[i] = 0;
+  for (int i = 0; i < 8; i++) canon[i] = 0;
+  const bool neg = (in[7] >> 31) != 0;
+  fq_t yw; for (int i = 0; i < 8; i++) yw.v[i] = in[i];
+  yw.v[7] &= 0x7fffffffu;
+  { uint64_t c = 19; uint32_t top = 0;   // y >= p  <=>  y + 19 >= 2^255
+    for (int i = 0; i < 8; i++) { c += yw.v[i]; top = (uint32_t)c; c >>= 32; }
+    if (top >> 31) return LASSO_WIRE_NONCANONICAL; }
+  const fe29 y = fe_from_fq(yw), y2 = fe_sqr(y);
+  const fe29 u = fe_weak(fe_sub(y2, fe_one())), v = fe_weak(fe_add(fe_mul(y2, fe_from_fq(fq_d())), fe_one()));
+  const fe29 v3 = fe_mul(fe_sqr(v), v), v7 = fe_mul(fe_sqr(v3), v);
+  fe29 x = fe_mul(fe_mul(u, v3), fe_pow22523(fe_mul(u, v7)));
+  const fe29 vxx = fe_mul(fe_sqr(x), v);
+  if (!fe_is_zero(fe_sub(vxx, u))) {
+    if (!fe_is_zero(fe_add(vxx, u))) return LASSO_WIRE_NOT_ON_CURVE;
+    x = fe_mul(x, fe_from_fq(fq_from_limbs(0x4a0ea0b0u, 0xc4ee1b27u, 0xad2fe478u, 0x2f431806u, 0x3dfbd7a7u, 0x2b4d0099u, 0x4fc1df0bu, 0x2b832480u)));   // sqrt(-1)
+  }
+  const fq_t xc = fq_canonical(fe_to_fq(x)), nxc = fq_canonical(fq_neg(xc));
+  bool x_larger = false;   // nx < x as canonical integers
+  for (int i = 7; i >= 0; i--) if (xc.v[i] != nxc.v[i]) { x_larger = nxc.v[i] < xc.v[i]; break; }
+  const bool take_x = neg == x_larger;
+  fq_t X, other; for (int i = 0; i < 8; i++) { X.v[i] = take_x ? xc.v[i] : nxc.v[i]; other.v[i] = take_x ? nxc.v[i] : xc.v[i]; }
+  // [l]P: the top bit (252) is P itself and bit 251 is clear, so the sum starts at 2P — every coordinate a product output, no constant limbs carried into the loop
+  pt29 P; P.X = fe_from_fq(X); P.Y = y; P.T = fe_mul(P.X, y); P.Z = fe_one();
+  const fe29 d2 = fe_d2();
+  const uint32_t L[8] = {0x5cf5d3edu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu, 0u, 0u, 0u, 0x10000000u};
+  pt29 r = pt_dbl(P);
+#pragma unroll 1
+  for (int i = 250; i >= 0; i--) { r = pt_dbl(r); if ((L[i >> 5] >> (i & 31)) & 1u) r = pt_add(r, P, d2); }
+  if (!(fe_is_zero(r.X) && fe_is_zero(fe_sub(r.Y, r.Z)))) return LASSO_WIRE_NOT_IN_SUBGROUP;
+  const fq_t xm = fq_to_mont(X), ym = fq_to_mont(yw);
+  bool sign = false;   // X > -X
+  for (int i = 7; i >= 0; i--) if (X.v[i] != other.v[i]) { sign = other.v[i] < X.v[i]; break; }
+  for (int i = 0; i < 8; i++) { aff[i] = xm.v[i]; aff[8 + i] = ym.v[i]; canon[i] = yw.v[i]; }
+  if (sign) canon[7] |= 0x80000000u;
+  return LASSO_WIRE_OK;
+}
 
 // helpers the kernels share with the BN254 build (bn254_fe29.cuh)
 LHD niels29 niels_from_xy29(const fe29& x, const fe29& y, const fe29& d2) { niels29 e; e.ypx = fe_weak(fe_add(y, x)); e.ymx = fe_weak(fe_sub(y, x)); e.t2d = fe_mul(fe_mul(x, y), d2); e.pad = 0; return e; }

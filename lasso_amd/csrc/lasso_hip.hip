@@ -16,6 +16,8 @@
 #include "poly_kernels.cuh"
 #include "msm_kernels.cuh"
 #include "densify_kernels.cuh"
+#include "../../include/lasso_hip_wire.h"
+#include "wire_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1545,6 +1547,28 @@ int32_t lasso_densify_dim_slab(lasso_ctx* c, const uint64_t* d_indices, size_t n
 }
 
 // ------------------------------------------------------------------ curve entry points
+// include/lasso_hip_wire.h: n compressed points in, per point a status, the affine point and its canonical encoding out.  Device layout in the context's scratch:
+// [wire 32 n][affine 64 n][canonical 32 n][status n] — every region starts on a 16-byte boundary.
+int32_t lasso_points_decompress(lasso_ctx* c, const uint8_t* wire32, size_t n, lasso_affine* out, uint8_t* canon32, uint8_t* status) {
+  REQUIRE(c, status && (wire32 || n == 0) && n < ((size_t)1 << 31));
+  if (!n) return 0;
+  int32_t rc = ensure_scratch(c, 129 * n);
+  if (rc) return rc == LASSO_ERR_UNSUPPORTED ? fail(c, rc, "lasso_points_decompress: the scratch buffer cannot grow while a resident kernel is active") : rc;
+  uint8_t* base = (uint8_t*)c->d_scratch;
+  HIPCHK(c, hipMemcpyAsync(base, wire32, 32 * n, hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, LASSO_K_MISC, 129.0 * n);
+    hipLaunchKernelGGL(k_points_decompress, dim3((unsigned)((n + WIRE_THREADS - 1) / WIRE_THREADS)), dim3(WIRE_THREADS), 0, c->stream, (const uint4*)base, n, (uint4*)(base + 32 * n), (uint4*)(base + 96 * n), base + 128 * n);
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint8_t> host(97 * n);
+  HIPCHK(c, hipMemcpyAsync(host.data(), base + 32 * n, 97 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (out) memcpy(out, host.data(), 64 * n);
+  if (canon32) memcpy(canon32, host.data() + 64 * n, 32 * n);
+  memcpy(status, host.data() + 96 * n, n);
+  return 0;
+}
 int32_t lasso_bases_create(lasso_ctx* c, const lasso_affine* points, size_t n, lasso_bases** out) { return lasso_bases_create_opt(c, points, n, 1, out); }
 int32_t lasso_bases_create_opt(lasso_ctx* c, const lasso_affine* points, size_t n, int32_t byte_multiples, lasso_bases** out) {
   REQUIRE(c, points && out && n >= 1 && n * MSM_WINDOWS < ((size_t)1 << 32));

@@ -287,6 +287,24 @@ class Device:
         self._chk(self.lib.lasso_bases_create(self.ctx, _vp(affine), affine.shape[0], C.byref(b)))
         return b.value
 
+    def points_decompress(self, wire):
+        """ark-serialize compressed points decoded and validated on the device (include/lasso_hip_wire.h lasso_points_decompress): `wire` = n x 32 bytes (bytes, or a uint8
+        array).  Returns (affine (n, 8) uint64 as bases_create takes it, canonical (n, 32) uint8, status (n,) uint8 — _abi.WIRE_STATUS names the values); rejected
+        encodings leave zero rows.  A library without the decoder is an error, not a fall-back."""
+        if not hasattr(self, "_wire"):
+            try:
+                _abi.declare_wire(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_points_decompress (include/lasso_hip_wire.h)")
+            self._wire = True
+        w = np.ascontiguousarray(np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray, memoryview)) else np.asarray(wire, dtype=np.uint8)).reshape(-1)
+        if w.size % 32:
+            raise LassoError("points_decompress: the input is not a whole number of 32-byte encodings")
+        n = w.size // 32
+        aff = np.zeros((n, 8), dtype=np.uint64); canon = np.zeros((n, 32), dtype=np.uint8); status = np.zeros(n, dtype=np.uint8)
+        self._chk(self.lib.lasso_points_decompress(self.ctx, _vp(w), n, _vp(aff), _vp(canon), _vp(status)))
+        return aff, canon, status
+
     def bases_destroy(self, b):
         self.lib.lasso_bases_destroy(self.ctx, C.c_void_p(b))
 

@@ -4,8 +4,19 @@
 #include "shm_comm.hpp"
 #include <atomic>
 #include "../../include/lasso_prover.h"
+#include "../../include/lasso_hip_wire.h"
 
 using namespace lasso;
+
+// The device decoder of compressed points is an OPTIONAL part of the device library (include/lasso_hip_wire.h, not lasso_hip.h): a weak reference, null when these
+// sources are linked against an implementation of lasso_hip.h alone — the verifier then decodes on the host, and lasso_host_points_decompress(where = 1) says so.
+extern "C" int32_t lasso_points_decompress(lasso_ctx*, const uint8_t*, size_t, lasso_affine*, uint8_t*, uint8_t*) __attribute__((weak));
+// Read once per process.  LASSO_VERIFY_DEVICE_POINTS=0: the verifier decodes every point on the host, as it did before the device decoder existed.
+// LASSO_WIRE_DEVICE_MIN: the smallest batch the verifier hands to the device.  The default is the smallest batch MEASURED with the device ahead (376 points: AND, C = 1,
+// 2^10 lookups on curve25519, 91 ms -> 59 ms; profiles/verify_device_points.json) — smaller batches have not been measured and stay on the host.
+#define LASSO_WIRE_DEVICE_MIN_DEFAULT 376
+static bool wire_device_on() { static const bool on = [] { const char* e = getenv("LASSO_VERIFY_DEVICE_POINTS"); return !(e && e[0] == '0'); }(); return on; }
+static size_t wire_device_min() { static const size_t v = [] { const char* e = getenv("LASSO_WIRE_DEVICE_MIN"); const long long x = e ? atoll(e) : LASSO_WIRE_DEVICE_MIN_DEFAULT; return (size_t)(x < 1 ? 1 : x); }(); return v; }
 
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
@@ -13,6 +24,8 @@ using namespace lasso;
 struct lasso_host {
   Dev dev; std::atomic<int> refs{1};
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
+  uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
+  WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && wire_device_on()) { w.fn = &lasso_points_decompress; w.min_points = wire_device_min(); w.counter = &wire_device_points; } return w; }
   explicit lasso_host(int device) : dev(device) {}
   void retain() { refs.fetch_add(1, std::memory_order_relaxed); }
   void release() { if (refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete this; }
@@ -207,7 +220,7 @@ int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_stra
     ProofTranscript t(tv, tu);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t);
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     return 0;)
 }
@@ -219,7 +232,7 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
     ProofTranscript t(tl);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t);
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     return 0;)
 }
@@ -261,6 +274,26 @@ int32_t lasso_host_debug_cubic_batched(lasso_host* h, lasso_host_dense* dn, lass
     w.sc_arr(r_out); w.sc_arr(ca); w.sc_arr(cb);
     return emit(w.b, out, cap, len);
   } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
+}
+int32_t lasso_host_points_decompress(lasso_host* h, const uint8_t* wire32, size_t n, int32_t where, lasso_affine* out, uint8_t* canon32, uint8_t* status) {
+  GUARD(
+    if (!h || !status || (!wire32 && n) || (where != 0 && where != 1)) throw Error("lasso_host_points_decompress: null argument, or `where` is neither 0 (host) nor 1 (device)");
+    if (where == 1) {
+      if (!lasso_points_decompress) throw Error("lasso_host_points_decompress: the device decoder (lasso_points_decompress, include/lasso_hip_wire.h) is not available in the device library this host was linked against");
+      h->dev.chk(lasso_points_decompress(h->dev.ctx, wire32, n, out, canon32, status), "lasso_points_decompress");
+      h->wire_device_points += n;
+      return 0;
+    }
+    for (size_t i = 0; i < n; i++) status[i] = decompress_point_abi(wire32 + 32 * i, out ? out + i : nullptr, canon32 ? canon32 + 32 * i : nullptr);
+    return 0;)
+}
+int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* device_available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_wire_stats: null host");
+    if (device_points) *device_points = h->wire_device_points;
+    if (device_available) *device_available = lasso_points_decompress ? 1 : 0;
+    if (reset) h->wire_device_points = 0;
+    return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {
   GUARD(const Strategy S = Strategy::from_abi(st); (void)S; return 0;)

@@ -20,35 +20,37 @@
 // A rejected proof returns false; a proof the reference would `assert!` on / fail to deserialize throws Error (-> non-zero status at the C ABI).
 #pragma once
 #include "prover.hpp"
+#include "../../include/lasso_hip_wire.h"
 
 namespace lasso {
 
 // ------------------------------------------------------------------ points from the wire (ark-ec deserialize_compressed with Validate::Yes)
 #ifdef LASSO_BN254
 // short Weierstrass (ark-ec SWFlags): canonical x, bit 7 of the last byte = "y is the larger root", bit 6 = infinity.  G1 has cofactor 1.
-inline bool decompress_point(const uint8_t in[32], Pt& out, bool& infinity) {
+// decompress_point_status: the same checks in the same order, with the failing one named (lasso_wire_status, include/lasso_hip_wire.h)
+inline uint8_t decompress_point_status(const uint8_t in[32], Pt& out, bool& infinity) {
   uint8_t b[32]; memcpy(b, in, 32);
   const bool neg = (b[31] & 0x80) != 0; infinity = (b[31] & 0x40) != 0; b[31] &= 0x3f;
   fq_t c; memcpy(c.v, b, 32);
   // ark-ec 0.4 (SWCurveConfig::deserialize_with_mode): both flags set is no SWFlags value; x must be a canonical field element whatever the flags say;
   // with the infinity flag the point is the identity WHATEVER x is (the transcript then absorbs the re-serialised identity: x = 0 with the flag)
-  if (neg && infinity) return false;
-  if (fq_geq_p(c.v)) return false;
-  if (infinity) { out = Pt::identity(); return true; }
+  if (neg && infinity) return LASSO_WIRE_BAD_FLAGS;
+  if (fq_geq_p(c.v)) return LASSO_WIRE_NONCANONICAL;
+  if (infinity) { out = Pt::identity(); return LASSO_WIRE_OK_IDENTITY; }
   const fq_t x = fq_from_canonical(c);
   fq_t y;
-  if (!fq_sqrt(fq_add(fq_mul(fq_sqr(x), x), fq_from_u64(3)), y)) return false;
+  if (!fq_sqrt(fq_add(fq_mul(fq_sqr(x), x), fq_from_u64(3)), y)) return LASSO_WIRE_NOT_ON_CURVE;
   const fq_t ny = fq_neg(y);
   const bool y_larger = canonical_less(ny, y);
   out = Pt::from_affine_plain(x, (neg == y_larger) ? y : ny);
-  return true;
+  return LASSO_WIRE_OK;
 }
 inline void affine_to_abi(const Pt& p, lasso_affine& a) { memcpy(a.x, p.p.X.v, 32); memcpy(a.y, p.p.Y.v, 32); }   // Z = 1, Montgomery limbs as stored
 inline void compress_affine_pt(const Pt& p, bool infinity, uint8_t out[32]) { if (infinity) compress_infinity(out); else compress_affine(p.p.X, p.p.Y, out); }
 #else
 // twisted Edwards (ark-ec TEFlags): canonical y, bit 7 of the last byte = "x is the larger root"; the point must lie in the prime-order subgroup
 // (Affine::check: is_on_curve && is_in_correct_subgroup_assuming_on_curve, cofactor 8)
-inline bool decompress_point(const uint8_t in[32], Pt& out, bool& infinity) {
+inline uint8_t decompress_point_status(const uint8_t in[32], Pt& out, bool& infinity) {
   infinity = false;
   uint8_t b[32]; memcpy(b, in, 32);
   const bool neg = (b[31] & 0x80) != 0; b[31] &= 0x7f;
@@ -56,28 +58,57 @@ inline bool decompress_point(const uint8_t in[32], Pt& out, bool& infinity) {
   {
     const uint32_t P[8] = {0xffffffedu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x7fffffffu};
     bool lt = false; for (int i = 7; i >= 0; i--) if (y.v[i] != P[i]) { lt = y.v[i] < P[i]; break; }
-    if (!lt) return false;
+    if (!lt) return LASSO_WIRE_NONCANONICAL;
   }
   const fq_t y2 = fq_sqr(y), den = fq_sub(fq_neg(fq_one()), fq_mul(fq_d(), y2));   // x^2 = (1 - y^2) / (a - d y^2), a = -1
-  if (fq_is_zero(den)) return false;
+  if (fq_is_zero(den)) return LASSO_WIRE_NOT_ON_CURVE;
   fq_t x;
-  if (!fq_sqrt(fq_mul(fq_sub(fq_one(), y2), fq_inv_host(den)), x)) return false;
+  if (!fq_sqrt(fq_mul(fq_sub(fq_one(), y2), fq_inv_host(den)), x)) return LASSO_WIRE_NOT_ON_CURVE;
   const fq_t nx = fq_neg(x);
   const bool x_larger = canonical_less(nx, x);
   out = Pt::from_affine_plain((neg == x_larger) ? x : nx, y);
   uint32_t order[8]; for (int i = 0; i < 8; i++) order[i] = fr_p_limb(i);
   const ed_point chk = ed_mul_limbs(out.p, order, 253);
-  return ed_eq(chk, ed_identity());
+  return ed_eq(chk, ed_identity()) ? LASSO_WIRE_OK : LASSO_WIRE_NOT_IN_SUBGROUP;
 }
 inline void affine_to_abi(const Pt& p, lasso_affine& a) { const fq_t x = fq_to_mont(p.p.X), y = fq_to_mont(p.p.Y); memcpy(a.x, x.v, 32); memcpy(a.y, y.v, 32); }
 inline void compress_affine_pt(const Pt& p, bool, uint8_t out[32]) { compress_affine(p.p.X, p.p.Y, out); }
 #endif
+inline bool decompress_point(const uint8_t in[32], Pt& out, bool& infinity) { return decompress_point_status(in, out, infinity) <= LASSO_WIRE_OK_IDENTITY; }
 
 struct WirePoint { Pt p; bool infinity = false; uint8_t bytes[32]; };   // bytes = serialize_compressed of the decoded point (what the transcript absorbs)
+// one decoded point as lasso_points_decompress reports it (status LASSO_WIRE_OK or LASSO_WIRE_OK_IDENTITY) -> what ProofReader::pt() builds on the host
+inline WirePoint wire_point_from_abi(const lasso_affine& a, const uint8_t canon[32], uint8_t status) {
+  WirePoint w; w.infinity = status == LASSO_WIRE_OK_IDENTITY;
+  if (w.infinity) w.p = Pt::identity();
+  else { fq_t x, y; memcpy(x.v, a.x, 32); memcpy(y.v, a.y, 32); w.p = Pt::from_affine_plain(fq_from_mont(x), fq_from_mont(y)); }
+  memcpy(w.bytes, canon, 32); return w;
+}
+// lasso_host_points_decompress(where = 0): the host decoder in the output form of lasso_points_decompress (rejected encodings leave zeros)
+inline uint8_t decompress_point_abi(const uint8_t in[32], lasso_affine* out, uint8_t* canon) {
+  Pt p; bool inf = false;
+  const uint8_t st = decompress_point_status(in, p, inf);
+  if (out) memset(out, 0, sizeof(*out));
+  if (canon) memset(canon, 0, 32);
+  if (st > LASSO_WIRE_OK_IDENTITY) return st;
+  if (out && !inf) affine_to_abi(p, *out);
+  if (canon) compress_affine_pt(p, inf, canon);
+  return st;
+}
+// The device decoder as the verifier sees it (prover_capi.cpp fills it in: the entry point is a weak reference, absent from libraries that implement lasso_hip.h alone)
+struct WireDecoder {
+  int32_t (*fn)(lasso_ctx*, const uint8_t*, size_t, lasso_affine*, uint8_t*, uint8_t*) = nullptr;
+  size_t min_points = 0;          // batches below this stay on the host (LASSO_WIRE_DEVICE_MIN)
+  uint64_t* counter = nullptr;    // points decoded on the device, per host (lasso_host_wire_stats)
+};
 
 // ------------------------------------------------------------------ reader of the ark-serialize byte stream
 struct ProofReader {
   const uint8_t* p; size_t n, pos = 0;
+  // Batched decoding (Verifier::verify): a first, structural pass COLLECTS the position of every point encoding instead of decoding it (pt() returns a placeholder),
+  // one lasso_points_decompress call decodes them all, and a second pass over the same bytes takes the decoded points in the same order (FILL).
+  std::vector<const uint8_t*>* collect = nullptr;
+  const std::vector<WirePoint>* fill = nullptr; size_t* fill_pos = nullptr;
   ProofReader(const uint8_t* p_, size_t n_) : p(p_), n(n_) {}
   void need(size_t k) const { if (pos + k > n) throw Error("proof bytes: truncated"); }
   uint64_t u64le() { need(8); uint64_t x = 0; for (int i = 0; i < 8; i++) x |= (uint64_t)p[pos + i] << (8 * i); pos += 8; return x; }
@@ -88,6 +119,8 @@ struct ProofReader {
   }
   WirePoint pt() {
     need(32); WirePoint w;
+    if (collect) { collect->push_back(p + pos); pos += 32; return WirePoint(); }
+    if (fill) { pos += 32; return (*fill)[(*fill_pos)++]; }
     if (!decompress_point(p + pos, w.p, w.infinity)) throw Error("proof bytes: invalid point encoding");
     compress_affine_pt(w.p, w.infinity, w.bytes); pos += 32; return w;
   }
@@ -115,8 +148,8 @@ inline WireBgpa read_bgpa(ProofReader& r) {
   for (size_t i = 0; i < k; i++) { LayerProofBatched l; l.proof = r.sumcheck(); l.claims_prod_left = r.sc_vec(); l.claims_prod_right = r.sc_vec(); g.proof.push_back(std::move(l)); }
   return g;
 }
-inline WireProof read_proof(const Strategy& S, const uint8_t* bytes, size_t n) {
-  ProofReader r(bytes, n); WireProof P;
+inline WireProof read_proof(const Strategy& S, ProofReader& r) {
+  WireProof P;
   const size_t alpha = S.num_memories(), C = S.C();
   P.comm_derefs = r.pts_vec();
   P.primary = r.sumcheck(); P.claimed_evaluation = r.sc(); P.eval_derefs = r.sc_arr(alpha); P.proof_derefs = read_dpl(r);
@@ -127,6 +160,7 @@ inline WireProof read_proof(const Strategy& S, const uint8_t* bytes, size_t n) {
   if (!r.done()) throw Error("proof bytes: trailing data");
   return P;
 }
+inline WireProof read_proof(const Strategy& S, const uint8_t* bytes, size_t n) { ProofReader r(bytes, n); return read_proof(S, r); }
 
 // ------------------------------------------------------------------ host side of SubtableStrategy the verifier needs (subtables/*.rs)
 // A caller-defined table has no closed form: its MLE at a point is the dot product of the table with EqPolynomial(point).evals() (2^log_m products, on the host).  The
@@ -189,7 +223,7 @@ inline Sc combine_lookups(const Strategy& S, const ScVec& vals) {
 
 // ------------------------------------------------------------------ the verifier
 class Verifier {
-  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t;
+  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t; WireDecoder decoder;
 
   // sumcheck.rs:286-328
   bool sumcheck_verify(const SumcheckProof& proof, const Sc& claim, size_t num_rounds, size_t degree_bound, Sc& e_out, ScVec& r_out) {
@@ -303,14 +337,42 @@ class Verifier {
   }
 
  public:
-  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_) : d(d_), S(S_), gens(g_), t(t_) {}
+  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_) {}
+
+  // Proof and commitment with every point decoded in ONE device call.  false = not taken (no device decoder, a batch below the threshold) or not clean (the bytes do
+  // not walk, a scalar is not canonical, some encoding is rejected): the caller then runs the sequential reader, which finds the FIRST error in stream order and
+  // words it as it always did — an honest proof never pays for that.
+  bool read_batched(const uint8_t* proof_bytes, size_t proof_len, const uint8_t* comm_bytes, size_t comm_len, WireProof& P, std::vector<WirePoint>& comm_l, std::vector<WirePoint>& comm_m) {
+    if (!decoder.fn) return false;
+    std::vector<const uint8_t*> at;
+    try {
+      ProofReader r(proof_bytes, proof_len); r.collect = &at; (void)read_proof(S, r);
+      ProofReader cr(comm_bytes, comm_len); cr.collect = &at; (void)cr.pts_vec(); (void)cr.pts_vec();
+      if (!cr.done()) return false;
+    } catch (const std::exception&) { return false; }
+    const size_t k = at.size();
+    if (k == 0 || k < decoder.min_points) return false;
+    std::vector<uint8_t> enc(32 * k), canon(32 * k), status(k); std::vector<lasso_affine> aff(k);
+    for (size_t i = 0; i < k; i++) memcpy(&enc[32 * i], at[i], 32);
+    d.chk(decoder.fn(d.ctx, enc.data(), k, aff.data(), canon.data(), status.data()), "lasso_points_decompress");
+    if (decoder.counter) *decoder.counter += k;
+    std::vector<WirePoint> pts(k);
+    for (size_t i = 0; i < k; i++) { if (status[i] > LASSO_WIRE_OK_IDENTITY) return false; pts[i] = wire_point_from_abi(aff[i], &canon[32 * i], status[i]); }
+    size_t next = 0;
+    ProofReader r(proof_bytes, proof_len); r.fill = &pts; r.fill_pos = &next; P = read_proof(S, r);
+    ProofReader cr(comm_bytes, comm_len); cr.fill = &pts; cr.fill_pos = &next; comm_l = cr.pts_vec(); comm_m = cr.pts_vec();
+    return true;
+  }
 
   // commitment: SparsePolynomialCommitment's two PolyCommitments in wire form ([u64 n][n x 32 B] twice: lasso_host_commit's layout) for s lookups, M = 2^log_m
   bool verify(const uint8_t* proof_bytes, size_t proof_len, const uint8_t* comm_bytes, size_t comm_len, size_t s, size_t log_m, const ScVec& eq_randomness) {
-    const WireProof P = read_proof(S, proof_bytes, proof_len);
-    ProofReader cr(comm_bytes, comm_len);
-    const std::vector<WirePoint> comm_l = cr.pts_vec(), comm_m = cr.pts_vec();
-    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    WireProof P; std::vector<WirePoint> comm_l, comm_m;
+    if (!read_batched(proof_bytes, proof_len, comm_bytes, comm_len, P, comm_l, comm_m)) {
+      P = read_proof(S, proof_bytes, proof_len);
+      ProofReader cr(comm_bytes, comm_len);
+      comm_l = cr.pts_vec(); comm_m = cr.pts_vec();
+      if (!cr.done()) throw Error("commitment bytes: trailing data");
+    }
     const size_t alpha = S.num_memories(), m = (size_t)1 << log_m;
     LASSO_REQUIRE(log_m == S.abi.log_m && eq_randomness.size() == ceil_log2(s));
     // surge.rs:214-271

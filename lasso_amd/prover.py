@@ -65,6 +65,8 @@ def declare_prover(lib):
     lib.lasso_host_merlin_free.argtypes = [vp]
     lib.lasso_host_merlin_vtbl.argtypes = []; lib.lasso_host_merlin_vtbl.restype = vt
     lib.lasso_host_strategy_check.argtypes = [C.POINTER(_abi.Strategy)]
+    lib.lasso_host_points_decompress.argtypes = [vp, vp, sz, i32, vp, vp, vp]
+    lib.lasso_host_wire_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
     lib.lasso_host_gen_indices.argtypes = [sz, sz, vp]
     lib.lasso_host_gen_random_point.argtypes = [sz, vp]
     return lib
@@ -183,6 +185,24 @@ class HostProver:
         ok = C.c_int32(-1)
         self._chk(self.lib.lasso_host_verify(self.h, gens, strategy_ptr(strategy), s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript, proof, len(proof), commitment, len(commitment), C.byref(ok)))
         return ok.value == 1
+
+    def points_decompress(self, wire, where=0):
+        """compressed points -> (affine (n, 8) uint64, canonical (n, 32) uint8, status (n,) uint8), decoded on the host (where=0: the verifier's own decoder) or on the
+        device (where=1: one launch; LassoError when the device library has no decoder) — lasso_host_points_decompress"""
+        w = np.ascontiguousarray(np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray, memoryview)) else np.asarray(wire, dtype=np.uint8)).reshape(-1)
+        if w.size % 32:
+            raise LassoError("points_decompress: the input is not a whole number of 32-byte encodings")
+        n = w.size // 32
+        aff = np.zeros((n, 8), dtype=np.uint64); canon = np.zeros((n, 32), dtype=np.uint8); status = np.zeros(n, dtype=np.uint8)
+        vpt = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.lasso_host_points_decompress(self.h, vpt(w), n, where, vpt(aff), vpt(canon), vpt(status)))
+        return aff, canon, status
+
+    def wire_stats(self, reset=False):
+        """{"device_points": compressed points this host decoded on the device so far, "device_available": whether the device decoder exists} (lasso_host_wire_stats)"""
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(self.lib.lasso_host_wire_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"device_points": k.value, "device_available": bool(a.value)}
 
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""

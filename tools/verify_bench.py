@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Time HostProver.verify with the proof's and the commitment's compressed points decoded on the host (LASSO_VERIFY_DEVICE_POINTS=0: one point after the other on one CPU
+thread, the only path before the device decoder existed) and on the device (the default: ONE lasso_points_decompress call per proof, include/lasso_hip_wire.h).
+
+AND, C = 1, M = 2^16 at 2^10, 2^16, 2^20 and 2^24 lookups on curve25519 (2^24 is the headline instance) and at 2^20 on BN254.  The switches are read once per process,
+so every (instance, setting) is measured in a fresh child process: it proves once, verifies `--runs` times (host clock around verify), and — with the device decoder —
+reports the kernel's own time from the library's event brackets (lasso_prof_*, family LASSO_K_MISC, in an extra verify that is not among the timed ones).
+
+Writes one JSON file (default profiles/verify_device_points.json) with, per instance, median / min / max of both settings, the ratio, and whether the acceptance condition
+holds: the default is not slower than the host path by more than the host path's own spread.  Needs the built libraries and a GPU; nothing here falls back to a CPU."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+INSTANCES = [("curve25519", 10), ("curve25519", 16), ("curve25519", 20), ("curve25519", 24), ("bn254", 20)]
+
+
+def child(curve, log_s, runs):
+    import numpy as np  # noqa: F401
+    from lasso_amd import HostProver, _abi
+    from lasso_amd.device import load_device_library
+    hp = HostProver(curve=curve)
+    c, log_m, s = 1, 16, 1 << log_s
+    idx = hp.gen_indices(s, 1 << log_m, c); r = hp.gen_random_point(log_s)
+    S = _abi.Strategy(_abi.KINDS["and"], c, log_m, 0)
+    gens = hp.gens(c, s, c, log_m); hp.gens_prepare(gens)
+    dense = hp.densify(idx, log_m)
+    comm = hp.commit(dense, gens); proof = hp.prove(dense, gens, S, r)
+    hp.free(dense)
+    assert hp.verify(gens, S, s, r, proof, comm) is True      # warm-up: buffers, tables
+    hp.wire_stats(reset=True)
+    ms = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        ok = hp.verify(gens, S, s, r, proof, comm)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        assert ok is True
+    points = hp.wire_stats()["device_points"] // runs
+    kernel_ms = None
+    if points:
+        lib = load_device_library(curve=curve)      # the same shared object the host library is linked against
+        ctx = C.c_void_p(hp.ctx())
+        lib.lasso_prof_reset(ctx); lib.lasso_prof_enable(ctx, 1 << _abi.K_MISC)
+        assert hp.verify(gens, S, s, r, proof, comm) is True
+        n, t, b = C.c_uint64(), C.c_double(), C.c_double()
+        lib.lasso_prof_get(ctx, _abi.K_MISC, C.byref(n), C.byref(t), C.byref(b))
+        lib.lasso_prof_enable(ctx, 0)
+        kernel_ms = t.value
+    hp.free(None, gens); hp.close()
+    print("VERIFY_BENCH " + json.dumps({"curve": curve, "log_s": log_s, "verify_ms": ms, "device_points_per_verify": points, "kernel_ms": kernel_ms, "proof_bytes": len(proof),
+                                        "commitment_bytes": len(comm)}))
+
+
+def run_child(curve, log_s, runs, env_extra):
+    env = dict(os.environ)
+    env.pop("LASSO_VERIFY_DEVICE_POINTS", None)
+    env.update(env_extra)
+    res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", curve, str(log_s), "--runs", str(runs)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
+    if res.returncode != 0:
+        raise SystemExit(f"child failed ({curve}, 2^{log_s}, {env_extra}):\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
+    line = [ln for ln in res.stdout.split("\n") if ln.startswith("VERIFY_BENCH ")][-1]
+    return json.loads(line[len("VERIFY_BENCH "):])
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "spread_ms": max(ms) - min(ms), "all_ms": ms}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--child", nargs=2, metavar=("CURVE", "LOG_S"))
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_device_points.json"))
+    ap.add_argument("--only", default="", help="comma-separated subset, e.g. curve25519-2p10,bn254-2p20")
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child[0], int(a.child[1]), a.runs)
+    runs = max(a.runs, 5)
+    rows = []
+    for curve, log_s in INSTANCES:
+        name = f"{curve}-2p{log_s}"
+        if a.only and name not in a.only.split(","):
+            continue
+        off = run_child(curve, log_s, runs, {"LASSO_VERIFY_DEVICE_POINTS": "0"})
+        on = run_child(curve, log_s, runs, {"LASSO_WIRE_DEVICE_MIN": os.environ.get("LASSO_WIRE_DEVICE_MIN", "1")})      # threshold out of the way: the decoder itself is measured at every size
+        so, sn = summary(off["verify_ms"]), summary(on["verify_ms"])
+        row = {"instance": name, "strategy": "and", "C": 1, "log_m": 16, "wire_points": on["device_points_per_verify"], "host_points": so, "device_points": sn,
+               "kernel_ms": on["kernel_ms"], "speedup": so["median_ms"] / sn["median_ms"],
+               "no_slower_than_host_path_within_its_spread": sn["median_ms"] <= so["median_ms"] + so["spread_ms"]}
+        assert off["device_points_per_verify"] == 0 and on["device_points_per_verify"] > 0
+        rows.append(row)
+        print(f"{name}: {row['wire_points']} points  host {so['median_ms']:.2f} ms [{so['min_ms']:.2f}, {so['max_ms']:.2f}]  device {sn['median_ms']:.2f} ms "
+              f"[{sn['min_ms']:.2f}, {sn['max_ms']:.2f}]  kernel {row['kernel_ms']:.3f} ms  x{row['speedup']:.2f}", flush=True)
+    wins = [r["wire_points"] for r in rows if r["device_points"]["median_ms"] < r["host_points"]["median_ms"]]
+    out = {"what": "HostProver.verify, compressed points decoded on the host (LASSO_VERIFY_DEVICE_POINTS=0) against on the device (LASSO_WIRE_DEVICE_MIN=1)", "runs_per_setting": runs,
+           "rows": rows, "smallest_measured_batch_where_the_device_wins": min(wins) if wins else None}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
