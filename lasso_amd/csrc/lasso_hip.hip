@@ -1,9 +1,6 @@
 // liblasso_hip.so — implementation of include/lasso_hip.h for MI355X (gfx950).
 // One context = one device + one HIP stream + scratch.  See the header for the contract of each entry point.
 #include <hip/hip_runtime.h>
-#if defined(__SSE2__)
-#include <emmintrin.h>   // 16-byte single-copy stores / loads of the hand-off chunks; other hosts take the per-word fallbacks (the check word covers tearing)
-#endif
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -48,11 +45,11 @@ struct lasso_ctx {
   fr_t* h_small = nullptr;                                // pinned, mapped, coherent
   size_t small_cap = 0;
   uint32_t* h_flag = nullptr; uint32_t* d_flag = nullptr; // sequence flag (mapped), device alias
-  // Since round 3 the round kernels of the sumchecks hand their results over as SELF-VALIDATING chunks instead (poly_kernels.cuh "results for the host": three tagged 16-byte
+  // Since round 3 the round kernels of the sumchecks hand their results over as SELF-VALIDATING chunks instead (handoff_device.cuh: three tagged 16-byte
   // chunks per element in h_tag, one release fence on the device, no ticket and no flag: 2.1 us per resident turn instead of 4.1, tools/handoff_bench.hip).  LASSO_TAGGED_RESULTS=0: the flag protocol.
   uint32_t* h_tag = nullptr; uint32_t* d_tag = nullptr;    // small_cap elements of 48 bytes (mapped, zero-initialised: sequence numbers start at 1)
-  bool tagged = true, pending_tagged = false;
-  uint32_t pending_groups = 1, pending_K = 0;   // a launch whose workgroups each published their own block sums (LASSO_TAGGED_DIRECT): groups per row, values per row
+  bool tagged = true;
+  HandoffState proto;                                      // what is in flight between the device and the host (handoff.cuh): pending result, launches ahead, the resident tail
   std::vector<lasso_fr> group_tmp;
   // The resident tails' mailbox: three tagged 16-byte chunks of host-mapped memory (h_flag + 32) the kernel polls (k_cubic_tail).  Putting it in device memory the host writes through the BAR
   // (hsa_amd_agents_allow_access) was tried in round 3: 2.5 -> 2.1 us per empty turn in tools/pingpong_bench.hip, nothing measurable in a proof, and hand-offs lost with four contexts proving at once — dropped.
@@ -62,21 +59,12 @@ struct lasso_ctx {
   fr_t* d_big = nullptr; fr_t* h_big = nullptr; size_t big_cap = 0;   // large results (matvec rows): device buffer + pinned mirror, hipMemcpyAsync
   uint32_t* d_flags = nullptr;
   uint32_t* d_counters = nullptr;                         // arrival tickets of the in-launch reductions (zero between launches)
-  bool pending = false, defer_next = false; uint32_t pending_seq = 0; size_t pending_count = 0;   // a deferred result not yet collected by lasso_result_wait
-  // a bullet round launched ahead of its challenge (k_bullet_msm with a mailbox): enqueued by lasso_bullet_round_ahead, released by lasso_bullet_post (u, u^-1 in the two
-  // mailboxes mail_h, mail_h + 12), after which it is an ordinary pending result.  d_gmail: 18 words of device memory, workgroup (0, 0)'s republication of the two scalars
-  bool ahead_active = false; uint32_t ahead_seq = 0; uint32_t* d_gmail = nullptr;
-  bool tail_active = false; uint32_t tail_seq0 = 0, tail_turn = 0, tail_turns = 0; size_t tail_count = 0, tail_final = 0;   // resident sumcheck-tail kernel (k_cubic_tail); its mailbox = h_flag + 32 (bytes 128..163)
-  bool tail_unstarted = false;    // the resident tail was launched AHEAD of its first challenge (lasso_sumcheck_cubic_tail_begin_ahead): the first lasso_sumcheck_cubic_tail_next starts it
-  uint32_t handover_next = 0;     // lasso_tail_handover_next: the next cubic tail stops at this many elements per array and hands the arrays over
-  // a sumcheck round launched ahead (lasso_sumcheck_cubic_eqw2_begin_ahead): what lasso_challenge_post turns into the pending result
-  size_t ahead_count = 0; bool ahead_tagged = false; uint32_t ahead_groups = 1, ahead_K = 0; bool ahead_bullet = false;
-  // a LAYER's first launch enqueued ahead of the layer's eq point (lasso_sumcheck_cubic_eqw2_begin_eq_ahead / lasso_sumcheck_cubic_tail_begin_eq_ahead): legal while the previous
-  // layer's tail is still active; lasso_point_post delivers the point through pmail (host-mapped, one mailbox entry per field element) and turns the launch into the pending
-  // result / the active tail; lasso_point_cancel ends it without a result.  d_gpoint: where the gate (k_gate_point) leaves the point for the kernels behind it.
+  // a round launched ahead of its challenge waits for lasso_challenge_post's scalar in mail_h; a bullet round (k_bullet_msm with a mailbox) for lasso_bullet_post's u, u^-1 in the
+  // two mailboxes mail_h, mail_h + 12.  d_gmail: 18 words of device memory, workgroup (0, 0)'s republication of the two scalars.  The resident tails (k_cubic_tail) poll mail_h too.
+  uint32_t* d_gmail = nullptr;
+  // a LAYER enqueued ahead of its eq point (lasso_sumcheck_cubic_eqw2_begin_eq_ahead / lasso_sumcheck_cubic_tail_begin_eq_ahead): lasso_point_post delivers the point through pmail
+  // (host-mapped, one mailbox entry per field element).  d_gpoint: where the gate (k_gate_point) leaves the point for the kernels behind it.
   uint32_t* pmail_h = nullptr; uint32_t* pmail_d = nullptr; uint32_t* d_gpoint = nullptr;
-  uint32_t gate_sent = 0;         // sequence number of the last point gate launched: the mailbox area is its until pmail_h[LASSO_PMAIL_ACK_WORD] shows it (gate_free)
-  bool lay_active = false, lay_tail = false, lay_tagged = false, no_grow = false; uint32_t lay_seq = 0, lay_ell = 0, lay_groups = 1, lay_K = 0, lay_turns = 0; size_t lay_count = 0, lay_final = 0;
   uint32_t prof_mask = 0;   // bit k set = kernel family k is bracketed with events
   std::vector<EventPair> events; size_t events_used = 0;
   uint64_t prof_launches[LASSO_K_COUNT] = {0}; double prof_ms[LASSO_K_COUNT] = {0}; double prof_bytes[LASSO_K_COUNT] = {0};
@@ -127,25 +115,29 @@ static hipError_t dfree(lasso_ctx* c, void* p) {
   return hipFree(p);
 }
 
+// a context buffer is too small: may it be reallocated now?
+static int32_t grow_guard(lasso_ctx* c) {
+  if (c->proto.no_grow) return LASSO_ERR_UNSUPPORTED;   // a launch enqueued behind a resident kernel: the caller takes the ordinary path instead
+  if (c->proto.waiting_on_device()) return fail(c, LASSO_ERR_INVALID, "a launch is waiting on the device for its challenge: only lasso_result_wait and the post of that challenge are legal until then");   // growing would synchronise the stream for the kernel's whole 5 s bail-out and lose the round
+  return 0;
+}
 static int32_t ensure_scratch(lasso_ctx* c, size_t bytes) {
   if (bytes <= c->scratch_cap) return 0;
-  if (c->no_grow) return LASSO_ERR_UNSUPPORTED;   // a launch enqueued behind a resident kernel: the caller takes the ordinary path instead
-  if (c->ahead_active || c->lay_active) return fail(c, LASSO_ERR_INVALID, "a launch is waiting on the device for its challenge: only lasso_result_wait and the post of that challenge are legal until then");   // growing would synchronise the stream for the kernel's whole 5 s bail-out and lose the round
+  if (int32_t g = grow_guard(c)) return g;
   if (c->d_scratch) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0; }
   size_t cap = bytes < ((size_t)1 << 22) ? ((size_t)1 << 22) : bytes;
   HIPCHK(c, dmalloc(c, &c->d_scratch, cap)); c->scratch_cap = cap; return 0;
 }
 static int32_t ensure_pip(lasso_ctx* c, size_t bytes) {
   if (bytes <= c->pip_cap) return 0;
-  if (c->no_grow || c->ahead_active || c->lay_active) return LASSO_ERR_UNSUPPORTED;   // the caller takes the bucket kernel instead
+  if (!c->proto.may_grow()) return LASSO_ERR_UNSUPPORTED;   // the caller takes the bucket kernel instead
   if (c->d_pip) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
   if (dmalloc(c, &c->d_pip, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_pip = nullptr; return LASSO_ERR_UNSUPPORTED; }   // no room: not an error, the bucket kernel serves the commitment
   c->pip_cap = bytes; return 0;
 }
 static int32_t ensure_small(lasso_ctx* c, size_t count) {
   if (count <= c->small_cap) return 0;
-  if (c->no_grow) return LASSO_ERR_UNSUPPORTED;   // a launch enqueued behind a resident kernel: the caller takes the ordinary path instead
-  if (c->ahead_active || c->lay_active) return fail(c, LASSO_ERR_INVALID, "a launch is waiting on the device for its challenge: only lasso_result_wait and the post of that challenge are legal until then");   // growing would synchronise the stream for the kernel's whole 5 s bail-out and lose the round
+  if (int32_t g = grow_guard(c)) return g;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->h_small) (void)hipHostFree(c->h_small);
   c->h_small = nullptr; c->d_small = nullptr; c->small_cap = 0;
@@ -161,8 +153,7 @@ static int32_t ensure_small(lasso_ctx* c, size_t count) {
 }
 static int32_t ensure_big(lasso_ctx* c, size_t count) {
   if (count <= c->big_cap) return 0;
-  if (c->no_grow) return LASSO_ERR_UNSUPPORTED;   // a launch enqueued behind a resident kernel: the caller takes the ordinary path instead
-  if (c->ahead_active || c->lay_active) return fail(c, LASSO_ERR_INVALID, "a launch is waiting on the device for its challenge: only lasso_result_wait and the post of that challenge are legal until then");   // growing would synchronise the stream for the kernel's whole 5 s bail-out and lose the round
+  if (int32_t g = grow_guard(c)) return g;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->d_big) (void)dfree(c, c->d_big);
   if (c->h_big) (void)hipHostFree(c->h_big);
@@ -218,21 +209,8 @@ static inline fr_t to_fr(const lasso_fr* p) { fr_t r; memcpy(r.v, p, 32); return
 // Wait until the device has stored sequence number `seq` to the mapped flag, then copy `count` results out of the mapped buffer.
 // The producer's stores to h_small are ordered before the flag by a system-scope release on the device (k_publish / publish_flag).
 static inline double now_us() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-// One element of the tagged result area (three 16-byte chunks, poly_kernels.cuh result_store): true once all three carry `seq` and the check word agrees.  Each chunk is read with
-// one aligned 16-byte load (the device wrote it with one aligned 16-byte store); the check word also covers a platform that would tear either.
-static inline bool tagged_element(const uint32_t* e, uint32_t seq, uint32_t* w8) {
-  uint32_t c[12];
-#if defined(__SSE2__)
-  for (int k = 0; k < 3; k++) _mm_storeu_si128((__m128i*)(c + 4 * k), _mm_load_si128((const __m128i*)(e + 4 * k)));
-#else
-  for (int k = 0; k < 12; k++) c[k] = __atomic_load_n(e + k, __ATOMIC_ACQUIRE);
-#endif
-  if (c[0] != seq || c[4] != seq || c[8] != seq) return false;
-  w8[0] = c[1]; w8[1] = c[2]; w8[2] = c[3]; w8[3] = c[5]; w8[4] = c[6]; w8[5] = c[7]; w8[6] = c[9]; w8[7] = c[10];
-  return c[11] == (w8[0] ^ w8[1] ^ w8[2] ^ w8[3] ^ w8[4] ^ w8[5] ^ w8[6] ^ w8[7]) + seq * 0x9E3779B9u;
-}
 static int32_t wait_flag(lasso_ctx* c, uint32_t seq, size_t count, lasso_fr* out, bool tagged = false, uint32_t groups = 1, uint32_t K = 0) {
-  if (c->defer_next) { c->defer_next = false; c->pending = true; c->pending_seq = seq; c->pending_count = count; c->pending_tagged = tagged; c->pending_groups = groups; c->pending_K = K; return 0; }
+  if (c->proto.park_deferred(Handoff{seq, count, tagged, groups, K})) return 0;   // lasso_defer_next: collected by lasso_result_wait
   if (groups > 1) {   // every workgroup of a row published its block sums, slot (row * groups + bx) * K + k: the row's K values are the sums over bx
     c->group_tmp.resize(count * groups);
     int32_t rc = wait_flag(c, seq, count * groups, c->group_tmp.data(), tagged); if (rc) return rc;
@@ -243,7 +221,7 @@ static int32_t wait_flag(lasso_ctx* c, uint32_t seq, size_t count, lasso_fr* out
       memcpy(out + y * K + k, acc.v, 32);
     }
     return 0;
-  }   // lasso_defer_next: collected by lasso_result_wait
+  }
   uint64_t spins = 0;
   const double t0 = now_us();
   if (tagged) {
@@ -285,9 +263,9 @@ static int32_t wait_flag(lasso_ctx* c, uint32_t seq, size_t count, lasso_fr* out
 // still publish), zero the tagged result area and the mailbox, and restart at 1.  Costs one stream synchronisation per ~4e9 hand-offs.
 static uint32_t next_seq(lasso_ctx* c, uint32_t span = 1) {
   // not while a result is still uncollected (lasso_defer_next) or a resident tail holds a block of numbers: the 2^20 numbers of slack cover any such stretch
-  if (c->seq > 0xFFF00000u - span && ((!c->pending && !c->tail_active && !c->ahead_active && !c->lay_active) || c->seq > 0xFFFFFF00u - span)) {
+  if (c->seq > 0xFFF00000u - span && (c->proto.idle() || c->seq > 0xFFFFFF00u - span)) {
     (void)hipStreamSynchronize(c->stream);
-    if (c->pmail_h) { memset(c->pmail_h, 0, LASSO_PMAIL_BYTES); c->gate_sent = 0; }
+    if (c->pmail_h) { memset(c->pmail_h, 0, LASSO_PMAIL_BYTES); c->proto.gate_sent = 0; }
     if (c->d_gpoint) (void)hipMemset(c->d_gpoint, 0, LASSO_GPOINT_BYTES);
     if (c->h_tag) memset(c->h_tag, 0, c->small_cap * 48);
     if (c->mail_h) memset(c->mail_h, 0, 96);   // both mailboxes
@@ -381,7 +359,7 @@ int32_t lasso_rccl_shutdown(lasso_ctx* c) { REQUIRE(c, c); (void)hipStreamSynchr
 // pattern on the context's stream and check every byte.  Collective — every rank of the communicator calls it.  The wait is BOUNDED (20 s of polling, not a stream
 // synchronisation): on a time-out the communicator is aborted (ncclCommAbort, when the library has it) and dropped, so the caller falls back instead of hanging.
 int32_t lasso_rccl_selftest(lasso_ctx* c) {
-  REQUIRE(c, c && c->rccl_comm && !c->ahead_active && !c->lay_active && !c->tail_active);
+  REQUIRE(c, c && c->rccl_comm && !c->proto.waiting_on_device() && !c->proto.tail_active);
   RcclApi* a = rccl_api(nullptr);
   const int world = c->rccl_world;
   const size_t bytes = 1024;
@@ -440,27 +418,9 @@ int32_t lasso_points_reduce_compress(lasso_ctx* c, const void* d_parts, uint32_t
   return 0;
 }
 
-// three self-validating chunks [tag, w, w, w] [tag, w, w, w] [tag, w, w, check], each ONE aligned 16-byte store; the check word (result_check's formula) lets the kernel reject a chunk
-// that arrived in pieces
-static inline void mail_chunks(uint32_t* mail, uint32_t tag, const uint32_t w[8]) {
-  const uint32_t chk = (w[0] ^ w[1] ^ w[2] ^ w[3] ^ w[4] ^ w[5] ^ w[6] ^ w[7]) + tag * 0x9E3779B9u;
-#if defined(__SSE2__)
-  _mm_store_si128((__m128i*)(mail + 0), _mm_set_epi32((int)w[2], (int)w[1], (int)w[0], (int)tag));
-  _mm_store_si128((__m128i*)(mail + 4), _mm_set_epi32((int)w[5], (int)w[4], (int)w[3], (int)tag));
-  _mm_store_si128((__m128i*)(mail + 8), _mm_set_epi32((int)chk, (int)w[7], (int)w[6], (int)tag));
-#else   // no 16-byte store: data words first, the tags last (a reader that sees all three tags with a matching check word has the whole message)
-  const uint32_t m[12] = {tag, w[0], w[1], w[2], tag, w[3], w[4], w[5], tag, w[6], w[7], chk};
-  for (int k : {1, 2, 3, 5, 6, 7, 9, 10, 11}) __atomic_store_n(mail + k, m[k], __ATOMIC_RELAXED);
-  for (int k : {0, 4, 8}) __atomic_store_n(mail + k, m[k], __ATOMIC_RELEASE);
-#endif
-}
 static inline void post_mail(lasso_ctx* c, uint32_t tag, const uint32_t w[8]) {
   mail_chunks(c->mail_h, tag, w);
-#if defined(__SSE2__)
-  _mm_sfence();   // release: the chunks are globally visible before anything the host does next
-#else
-  __atomic_thread_fence(__ATOMIC_SEQ_CST);
-#endif
+  mail_fence();
 }
 int32_t lasso_ctx_create(int32_t device, lasso_ctx** out) { return lasso_ctx_create_background(device, 0, out); }
 int32_t lasso_ctx_device_uuid(lasso_ctx* c, uint8_t out[16]) {
@@ -507,15 +467,13 @@ int32_t lasso_ctx_create_background(int32_t device, int32_t background, lasso_ct
 int32_t lasso_abort(lasso_ctx* c) {
   REQUIRE(c, c);
   const uint32_t zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (c->lay_active && c->pmail_h) for (uint32_t j = 0; j < LASSO_POINT_MAX + 2; j++) mail_chunks(c->pmail_h + 12 * j, LASSO_MAIL_POISON, zero8);
-  if (c->tail_active || c->ahead_active || c->lay_active) { mail_chunks(c->mail_h + 12, LASSO_MAIL_POISON, zero8); post_mail(c, LASSO_MAIL_POISON, zero8); }
+  if (c->proto.lay_active && c->pmail_h) for (uint32_t j = 0; j < LASSO_POINT_MAX + 2; j++) mail_chunks(c->pmail_h + 12 * j, LASSO_MAIL_POISON, zero8);
+  if (c->proto.tail_active || c->proto.waiting_on_device()) { mail_chunks(c->mail_h + 12, LASSO_MAIL_POISON, zero8); post_mail(c, LASSO_MAIL_POISON, zero8); }
   (void)hipStreamSynchronize(c->stream);   // bounded: every device-side wait has the poison check and a wall-clock bail-out
   (void)hipGetLastError();
-  if (c->pmail_h) { memset(c->pmail_h, 0, LASSO_PMAIL_BYTES); c->gate_sent = 0; }   // the stream is drained: no gate is left to read or acknowledge anything
+  if (c->pmail_h) memset(c->pmail_h, 0, LASSO_PMAIL_BYTES);   // the stream is drained: no gate is left to read or acknowledge anything (reset below forgets the last one)
   mail_chunks(c->mail_h + 12, 0, zero8); post_mail(c, 0, zero8);
-  c->lay_active = false; c->lay_tail = false; c->no_grow = false;
-  c->ahead_active = false; c->ahead_bullet = false; c->tail_unstarted = false; c->handover_next = 0;
-  c->tail_active = false; c->pending = false; c->defer_next = false; c->events_used = 0; c->pending_groups = 1; c->pending_K = 0;
+  c->proto.reset(); c->events_used = 0;
   HIPCHK(c, hipMemsetAsync(c->d_counters, 0, (LASSO_MAX_PTRS + 40) * 4, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -524,7 +482,7 @@ void lasso_ctx_destroy(lasso_ctx* c) {
   if (!c) return;
   { std::lock_guard<std::mutex> g(g_ctx_mu); for (size_t i = 0; i < g_ctx_live.size(); i++) if (g_ctx_live[i] == c) { g_ctx_live.erase(g_ctx_live.begin() + i); break; } }
   (void)hipSetDevice(c->device);
-  if (c->tail_active || c->pending || c->ahead_active || c->lay_active) (void)lasso_abort(c);   // never block in the synchronise below for a kernel's 5 s bail-out
+  if (!c->proto.idle()) (void)lasso_abort(c);   // never block in the synchronise below for a kernel's 5 s bail-out
   (void)hipStreamSynchronize(c->stream);
   rccl_release(c);
   for (auto& p : c->events) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
@@ -548,24 +506,24 @@ void lasso_ctx_destroy(lasso_ctx* c) {
 const char* lasso_last_error(lasso_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 void* lasso_stream(lasso_ctx* c) { return c ? (void*)c->stream : nullptr; }
 int32_t lasso_alloc(lasso_ctx* c, size_t bytes, void** d_out) { REQUIRE(c, d_out); HIPCHK(c, dmalloc(c, d_out, bytes ? bytes : 1)); return 0; }
-int32_t lasso_free(lasso_ctx* c, void* p) { if (!p) return 0; REQUIRE(c, c && !c->ahead_active && !c->lay_active); HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, p)); return 0; }
+int32_t lasso_free(lasso_ctx* c, void* p) { if (!p) return 0; REQUIRE(c, c && !c->proto.waiting_on_device()); HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, p)); return 0; }
 int32_t lasso_mem_stats(lasso_ctx* c, uint64_t* live_bytes, uint64_t* peak_bytes, int32_t reset_peak) {
   REQUIRE(c, c); std::lock_guard<std::mutex> g(c->mem_mu);
   if (live_bytes) *live_bytes = c->mem_live; if (peak_bytes) *peak_bytes = c->mem_peak; if (reset_peak) c->mem_peak = c->mem_live; return 0;
 }
 int32_t lasso_trim(lasso_ctx* c) {
-  REQUIRE(c, c && !c->pending && !c->tail_active && !c->ahead_active && !c->lay_active);
+  REQUIRE(c, c && c->proto.idle());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->d_pip) { HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
   if (c->scratch_cap <= ((size_t)1 << 22)) return 0;
   HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0;
   return ensure_scratch(c, (size_t)1 << 22);
 }
-int32_t lasso_upload(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s && !c->ahead_active && !c->lay_active); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
-int32_t lasso_download(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s && !c->ahead_active && !c->lay_active); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
+int32_t lasso_upload(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s && !c->proto.waiting_on_device()); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
+int32_t lasso_download(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s && !c->proto.waiting_on_device()); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
 int32_t lasso_copy(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s); ProfScope ps(c, LASSO_K_MISC, 2.0 * n); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, c->stream)); return 0; }
 int32_t lasso_zero(lasso_ctx* c, void* d, size_t n) { REQUIRE(c, d); HIPCHK(c, hipMemsetAsync(d, 0, n, c->stream)); return 0; }
-int32_t lasso_sync(lasso_ctx* c) { REQUIRE(c, c && !c->ahead_active && !c->lay_active); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
+int32_t lasso_sync(lasso_ctx* c) { REQUIRE(c, c && !c->proto.waiting_on_device()); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
 
 int32_t lasso_prof_get_large(lasso_ctx* c, int32_t k, uint64_t* launches, double* ms, double* bytes) {
   REQUIRE(c, k >= 0 && k < LASSO_K_COUNT); prof_flush(c);
@@ -716,7 +674,7 @@ static int32_t cubic_eqw_launch_t(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* 
       static const uint32_t pipe = [] { const char* v = getenv("LASSO_LB_PIPELINE"); return (v && v[0] == '0') ? 0u : 1u; }();
       // what runs in front of the round is outside the round's profiling bracket: the wait for the point (one wave), the two factor tables (their own bracket)
       fr_t* const f_hi = (fr_t*)c->d_scratch + part_elems; fr_t* const f_lo = f_hi + ((size_t)1 << g_hi);
-      if (gated && NT == 2) hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); if (gated && NT == 2) c->gate_sent = seq;
+      if (gated && NT == 2) hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); if (gated && NT == 2) c->proto.gate_sent = seq;
       const uint32_t* const gate_gp = gated ? (const uint32_t*)c->d_gpoint : (const uint32_t*)nullptr;
       if ((gbig || eqg) && NT == 2) {
         ProfScope pe(c, LASSO_K_EQ, big_inline ? 32.0 * (((size_t)1 << g_hi) + ((size_t)1 << g_lo)) : 32.0 * half);
@@ -807,29 +765,27 @@ int32_t lasso_sumcheck_cubic_eqw_round_fused(lasso_ctx* c, lasso_fr* const* d_A,
 // Two-sum form, split into launch and wait so that the host can prepare the round's scalars (one field inversion) while the kernel runs.
 // out (lasso_result_wait) = ncirc pairs (q(0), q_inf) — see cubic_eqw_terms2 in poly_kernels.cuh.  One result may be pending per context.
 int32_t lasso_sumcheck_cubic_eqw2_begin(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n, const lasso_fr* r) {
-  REQUIRE(c, d_A && d_B && d_E && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= (r ? 4u : 2u) && (n & (n - 1)) == 0 && !c->pending);
+  REQUIRE(c, d_A && d_B && d_E && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= (r ? 4u : 2u) && (n & (n - 1)) == 0 && !c->proto.pending);
   uint32_t seq, groups; int32_t rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E, n, r, 2, &seq, nullptr, &groups); if (rc) return rc;
-  c->pending = true; c->pending_seq = seq; c->pending_count = (size_t)ncirc * 2; c->pending_tagged = c->tagged; c->pending_groups = groups; c->pending_K = 2;
+  c->proto.park(Handoff{seq, (size_t)ncirc * 2, c->tagged, groups, 2});
   return 0;
 }
 // The same round enqueued AHEAD of its challenge (k_cubic_eqw_fused<.., AHEAD>): legal while the previous round's result is still pending; the kernel waits on the device for
 // lasso_challenge_post, which turns the launch into the context's pending result.  Only streaming two-sum rounds (n / 4 > 64); LASSO_ERR_UNSUPPORTED otherwise (the caller launches
 // the ordinary round once it has the challenge).
 int32_t lasso_sumcheck_cubic_eqw2_begin_ahead(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n) {
-  REQUIRE(c, d_A && d_B && d_E && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->ahead_active && !c->tail_active && !c->defer_next);
+  REQUIRE(c, d_A && d_B && d_E && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->proto.ahead_active && !c->proto.tail_active && !c->proto.defer_next);
   if (n / 4 <= CUBIC_SMALL_Q) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_ahead: streaming rounds only");
   // everything that could synchronise the stream happens here, BEFORE the launch that waits
   { const unsigned nx = grid_for(n / 4, cubic_nx_cap(ncirc)); int32_t rc0 = ensure_small(c, (size_t)ncirc * 3 * (nx <= direct_nx_max() ? nx : 1)); if (rc0) return rc0; rc0 = ensure_scratch(c, (size_t)nx * ncirc * 3 * sizeof(fr_t)); if (rc0) return rc0; }
   uint32_t seq, groups; int32_t rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E, n, nullptr, 2, &seq, nullptr, &groups, true); if (rc) return rc;
-  c->ahead_active = true; c->ahead_bullet = false; c->ahead_seq = seq; c->ahead_count = (size_t)ncirc * 2; c->ahead_tagged = c->tagged; c->ahead_groups = groups; c->ahead_K = 2;
+  c->proto.arm_ahead(Handoff{seq, (size_t)ncirc * 2, c->tagged, groups, 2}, false);
   return 0;
 }
 // the challenge of the round launched ahead: after this call its sums are the context's pending result (lasso_result_wait)
 int32_t lasso_challenge_post(lasso_ctx* c, const lasso_fr* r) {
-  REQUIRE(c, r && c->ahead_active && !c->ahead_bullet && !c->pending);
-  post_mail(c, c->ahead_seq, (const uint32_t*)r);
-  c->ahead_active = false;
-  c->pending = true; c->pending_seq = c->ahead_seq; c->pending_count = c->ahead_count; c->pending_tagged = c->ahead_tagged; c->pending_groups = c->ahead_groups; c->pending_K = c->ahead_K;
+  REQUIRE(c, r && c->proto.ahead_active && !c->proto.ahead_bullet && !c->proto.pending);
+  post_mail(c, c->proto.post_ahead(), (const uint32_t*)r);
   return 0;
 }
 // 1 when rounds may be launched ahead on this context (LASSO_ROUNDS_AHEAD=0: A/B switch)
@@ -846,7 +802,7 @@ int32_t lasso_rounds_ahead_ok(lasso_ctx* c) { static const bool off = [] { const
 static int32_t cubic_tail_begin_impl(lasso_ctx* c, uint32_t m_stop, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n, const lasso_fr* r, const EqInline* eqi, bool ahead, int gate_ell = -1);
 // lasso_tail_handover_next's one-shot setting is consumed by the NEXT tail entry point whatever its outcome: every public wrapper takes it first thing, before any argument check can
 // return (a REQUIRE in a wrapper used to leave it armed for the next, unrelated tail)
-static uint32_t take_handover(lasso_ctx* c) { if (!c) return 0; const uint32_t m = c->handover_next; c->handover_next = 0; return m; }
+static uint32_t take_handover(lasso_ctx* c) { return c ? c->proto.take_handover() : 0; }
 int32_t lasso_sumcheck_cubic_tail_begin(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n, const lasso_fr* r) {
   const uint32_t ho = take_handover(c);
   REQUIRE(c, d_E);
@@ -860,14 +816,14 @@ static bool make_eq_inline(const lasso_fr* point, uint32_t ell, const lasso_fr* 
 // The first round of a layer with the layer's eq table  E = *scale * EqPolynomial(point[0..ell)).evals()  (2^ell = n/2 entries) built inside the launch (k_cubic_eqw_lb<2, true>):
 // the same pending result as lasso_sumcheck_cubic_eqw2_begin(.., d_E, n, NULL) after lasso_eq_evals_scaled(point, ell, scale, d_E), and d_E holds the same table afterwards.
 int32_t lasso_sumcheck_cubic_eqw2_begin_eq(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, lasso_fr* d_E_out, size_t n, const lasso_fr* point, uint32_t ell, const lasso_fr* scale) {
-  REQUIRE(c, d_A && d_B && d_E_out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0 && !c->pending && ((size_t)1 << ell) == n / 2);
+  REQUIRE(c, d_A && d_B && d_E_out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0 && !c->proto.pending && ((size_t)1 << ell) == n / 2);
   EqInline Q;
   if (n / 2 <= CUBIC_SMALL_Q || (ell && !point) || ell > 32) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_eq: tables of 2^7 .. 2^32 entries only");
   uint32_t seq, groups; int32_t rc;
   if (make_eq_inline(point, ell, scale, Q)) rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E_out, n, nullptr, 2, &seq, &Q, &groups);     // <= 2^14 entries: factor tables in LDS
   else { EqPointArg G; G.point = point; G.ell = ell; G.scale = scale ? to_fr(scale) : fr_one(); rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E_out, n, nullptr, 2, &seq, nullptr, &groups, false, &G); }   // larger: factor tables in memory
   if (rc) return rc;
-  c->pending = true; c->pending_seq = seq; c->pending_count = (size_t)ncirc * 2; c->pending_tagged = c->tagged; c->pending_groups = groups; c->pending_K = 2;
+  c->proto.park(Handoff{seq, (size_t)ncirc * 2, c->tagged, groups, 2});
   return 0;
 }
 // lasso_sumcheck_cubic_tail_begin(.., r = NULL) without a table: the resident kernel derives E = *scale * EqPolynomial(point[0..ell)).evals(), 2^ell = n/2 <= capacity, itself
@@ -882,7 +838,7 @@ template <class TM>
 static int32_t cubic_tail_begin_t(lasso_ctx* c, uint32_t m_stop_arg, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n, const lasso_fr* r, const EqInline* eqi, bool ahead, int gate_ell) {
   const uint32_t m_stop = m_stop_arg ? m_stop_arg : 1u;   // the caller's take_handover(): explicit, not sticky context state
   const bool gated = gate_ell >= 0;   // the whole layer enqueued ahead of its eq point, possibly behind the previous layer's (still active) tail: the point comes through k_gate_point
-  REQUIRE(c, d_A && d_B && (d_E || eqi || gated) && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= ((r || ahead) ? 4u : 2u) && (n & (n - 1)) == 0 && (ahead || gated || !c->pending) && (gated || !c->tail_active) && !c->defer_next && !c->ahead_active && !c->lay_active);
+  REQUIRE(c, d_A && d_B && (d_E || eqi || gated) && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= ((r || ahead) ? 4u : 2u) && (n & (n - 1)) == 0 && (ahead || gated || !c->proto.pending) && (gated || !c->proto.tail_active) && !c->proto.defer_next && !c->proto.ahead_active && !c->proto.lay_active);
   const size_t q = (r || ahead) ? n / 4 : n / 2;
   REQUIRE(c, q >= 1 && q <= CUBIC_TAIL_Q && (m_stop & (m_stop - 1)) == 0 && m_stop <= 128 && 2 * q > m_stop);   // at least one round of sums before the arrays are handed over
   TM A, B; for (uint32_t i = 0; i < ncirc; i++) { REQUIRE(c, d_A[i] && d_B[i]); A.p[i] = (fr_t*)d_A[i]; B.p[i] = (fr_t*)d_B[i]; }
@@ -892,20 +848,18 @@ static int32_t cubic_tail_begin_t(lasso_ctx* c, uint32_t m_stop_arg, lasso_fr* c
   // workgroup = capacity: 256 threads / 74 KB of LDS up to 256 indices per circuit, 512 threads / 147 KB above
 #define LAUNCH_CTAIL(B_, Q_, I_, TE_, R_, EQ_) hipLaunchKernelGGL((k_cubic_tail<B_, Q_, I_, TM, TE_>), dim3(ncirc), dim3(Q_), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)q, R_, (const uint32_t*)c->mail_d, c->d_counters, RES(c), seq0, EQ_, m_stop, ahead ? 1u : 0u)
   if (gated) {
-    hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq0, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); c->gate_sent = seq0;
+    hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq0, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); c->proto.gate_sent = seq0;
     EqInlineMem M; M.gp = c->d_gpoint; M.seq = seq0; M.ell = (uint32_t)gate_ell;
     if (q <= 256) LAUNCH_CTAIL(false, 256, true, EqInlineMem, fr_zero(), M); else LAUNCH_CTAIL(false, 512, true, EqInlineMem, fr_zero(), M);
     HIPCHK(c, hipGetLastError());
-    c->lay_active = true; c->lay_tail = true; c->lay_seq = seq0; c->lay_ell = (uint32_t)gate_ell; c->lay_turns = turns; c->lay_count = (size_t)ncirc * 2; c->lay_final = (size_t)ncirc * 2 * m_stop; c->lay_tagged = c->tagged;
+    c->proto.arm_layer_tail(Handoff{seq0, (size_t)ncirc * 2, c->tagged}, (uint32_t)gate_ell, turns, (size_t)ncirc * 2 * m_stop);
     return 0;   // the tail state of the context still belongs to the previous layer: lasso_point_post installs this one
   }
   if (eqi) { if (q <= 256) LAUNCH_CTAIL(false, 256, true, EqInline, fr_zero(), *eqi); else LAUNCH_CTAIL(false, 512, true, EqInline, fr_zero(), *eqi); }
   else if (q <= 256) { if (r || ahead) LAUNCH_CTAIL(true, 256, false, EqNone, r ? to_fr(r) : fr_zero(), EqNone()); else LAUNCH_CTAIL(false, 256, false, EqNone, fr_zero(), EqNone()); }
   else { if (r || ahead) LAUNCH_CTAIL(true, 512, false, EqNone, r ? to_fr(r) : fr_zero(), EqNone()); else LAUNCH_CTAIL(false, 512, false, EqNone, fr_zero(), EqNone()); }
   HIPCHK(c, hipGetLastError());
-  c->tail_active = true; c->tail_seq0 = seq0; c->tail_turn = 0; c->tail_turns = turns; c->tail_count = (size_t)ncirc * 2; c->tail_final = (size_t)ncirc * 2 * m_stop;
-  if (ahead) { c->tail_unstarted = true; return 0; }   // nothing is pending until the first challenge has been posted (lasso_sumcheck_cubic_tail_next)
-  c->pending = true; c->pending_seq = seq0; c->pending_count = c->tail_count; c->pending_tagged = c->tagged;
+  c->proto.begin_tail(Handoff{seq0, (size_t)ncirc * 2, c->tagged}, turns, (size_t)ncirc * 2 * m_stop, ahead);   // ahead: nothing is pending until the first challenge has been posted (lasso_sumcheck_cubic_tail_next)
   return 0;
 }
 }   // extern "C++"
@@ -922,20 +876,20 @@ static int32_t cubic_tail_begin_impl(lasso_ctx* c, uint32_t m_stop, lasso_fr* co
 // the ONE mailbox area is free when the last gate launched has ended (it acknowledges with its sequence number); until then a new layer may not be enqueued ahead — its
 // post / cancel would overwrite a message that gate has not read yet, and the gate would spin to its 5 s bail-out.  prover.hpp never gets here with a gate in
 // flight (a layer's first result is collected before the next one is enqueued); the entry points enforce it for every other caller: LASSO_ERR_UNSUPPORTED = take the plain path.
-static bool gate_free(lasso_ctx* c) { return !c->gate_sent || __atomic_load_n(c->pmail_h + LASSO_PMAIL_ACK_WORD, __ATOMIC_ACQUIRE) == c->gate_sent; }
+static bool gate_free(lasso_ctx* c) { return !c->proto.gate_sent || __atomic_load_n(c->pmail_h + LASSO_PMAIL_ACK_WORD, __ATOMIC_ACQUIRE) == c->proto.gate_sent; }
 int32_t lasso_layer_ahead_ok(lasso_ctx* c) { static const bool off = [] { const char* v = getenv("LASSO_LAYER_AHEAD"); return v && v[0] == '0'; }(); return c && !off && c->pmail_d && c->d_gpoint ? 1 : 0; }
 int32_t lasso_sumcheck_cubic_eqw2_begin_eq_ahead(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, lasso_fr* d_E_out, size_t n, uint32_t ell) {
-  REQUIRE(c, d_A && d_B && d_E_out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0 && ell < 48 && ((size_t)1 << ell) == n / 2 && !c->lay_active && !c->ahead_active && !c->defer_next);
+  REQUIRE(c, d_A && d_B && d_E_out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0 && ell < 48 && ((size_t)1 << ell) == n / 2 && !c->proto.waiting_on_device() && !c->proto.defer_next);
   if (!lasso_layer_ahead_ok(c) || n / 2 <= CUBIC_SMALL_Q || ell > 32 || ell > LASSO_POINT_MAX) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_eq_ahead: tables of 2^7 .. 2^32 entries only");
   if (!gate_free(c)) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_eq_ahead: the previous point gate has not consumed its message yet");
   uint32_t seq, groups;
-  c->no_grow = true;
+  c->proto.no_grow = true;
   const int32_t rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E_out, n, nullptr, 2, &seq, nullptr, &groups, false, nullptr, (int)ell);
-  c->no_grow = false;
+  c->proto.no_grow = false;
   if (rc == LASSO_ERR_UNSUPPORTED) return fail(c, rc, "lasso_sumcheck_cubic_eqw2_begin_eq_ahead: a buffer would have to grow while kernels are in flight");
   if (rc) return rc;
   HIPCHK(c, hipGetLastError());
-  c->lay_active = true; c->lay_tail = false; c->lay_seq = seq; c->lay_ell = ell; c->lay_count = (size_t)ncirc * 2; c->lay_tagged = c->tagged; c->lay_groups = groups; c->lay_K = 2;
+  c->proto.arm_layer(Handoff{seq, (size_t)ncirc * 2, c->tagged, groups, 2}, ell);
   return 0;
 }
 int32_t lasso_sumcheck_cubic_tail_begin_eq_ahead(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, size_t n, uint32_t ell) {
@@ -943,44 +897,33 @@ int32_t lasso_sumcheck_cubic_tail_begin_eq_ahead(lasso_ctx* c, lasso_fr* const* 
   REQUIRE(c, n >= 2 && ell <= 9 && ((size_t)1 << ell) == n / 2);
   if (!lasso_layer_ahead_ok(c)) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_tail_begin_eq_ahead: switched off");
   if (!gate_free(c)) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_tail_begin_eq_ahead: the previous point gate has not consumed its message yet");
-  c->no_grow = true;
+  c->proto.no_grow = true;
   const int32_t rc = cubic_tail_begin_impl(c, ho, d_A, d_B, ncirc, nullptr, n, nullptr, nullptr, false, (int)ell);
-  c->no_grow = false;
+  c->proto.no_grow = false;
   if (rc == LASSO_ERR_UNSUPPORTED) return fail(c, rc, "lasso_sumcheck_cubic_tail_begin_eq_ahead: a buffer would have to grow while kernels are in flight");
   return rc;
 }
 static void point_mail(lasso_ctx* c, uint32_t ell, const lasso_fr* point, const lasso_fr* scale, uint32_t ctrl) {
   const uint32_t zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const fr_t one = fr_one();
-  for (uint32_t j = 0; j < ell; j++) mail_chunks(c->pmail_h + 12 * j, c->lay_seq, point ? (const uint32_t*)(point + j) : zero8);
-  mail_chunks(c->pmail_h + 12 * ell, c->lay_seq, scale ? (const uint32_t*)scale : one.v);
+  for (uint32_t j = 0; j < ell; j++) mail_chunks(c->pmail_h + 12 * j, c->proto.lay.seq, point ? (const uint32_t*)(point + j) : zero8);
+  mail_chunks(c->pmail_h + 12 * ell, c->proto.lay.seq, scale ? (const uint32_t*)scale : one.v);
   const uint32_t ctl[8] = {ctrl, 0, 0, 0, 0, 0, 0, 0};
-  mail_chunks(c->pmail_h + 12 * (ell + 1), c->lay_seq, ctl);
-#if defined(__SSE2__)
-  _mm_sfence();
-#else
-  __atomic_thread_fence(__ATOMIC_SEQ_CST);
-#endif
+  mail_chunks(c->pmail_h + 12 * (ell + 1), c->proto.lay.seq, ctl);
+  mail_fence();
 }
 // point[0..ell) and *scale (NULL = 1) of the layer enqueued ahead: afterwards the context is where the plain entry point would have left it (first round's sums pending;
 // the resident tail active).  Legal once the previous layer's tail has ended and its last result has been collected.
 int32_t lasso_point_post(lasso_ctx* c, const lasso_fr* point, uint32_t ell, const lasso_fr* scale) {
-  REQUIRE(c, c && c->lay_active && ell == c->lay_ell && (point || !ell) && !c->pending && !c->tail_active && !c->ahead_active);
+  REQUIRE(c, c && c->proto.lay_active && ell == c->proto.lay_ell && (point || !ell) && !c->proto.pending && !c->proto.tail_active && !c->proto.ahead_active);
   point_mail(c, ell, point, scale, 0u);
-  c->lay_active = false;
-  if (c->lay_tail) {
-    c->tail_active = true; c->tail_seq0 = c->lay_seq; c->tail_turn = 0; c->tail_turns = c->lay_turns; c->tail_count = c->lay_count; c->tail_final = c->lay_final; c->tail_unstarted = false;
-    c->pending = true; c->pending_seq = c->lay_seq; c->pending_count = c->lay_count; c->pending_tagged = c->lay_tagged; c->pending_groups = 1; c->pending_K = 0;
-  } else {
-    c->pending = true; c->pending_seq = c->lay_seq; c->pending_count = c->lay_count; c->pending_tagged = c->lay_tagged; c->pending_groups = c->lay_groups; c->pending_K = c->lay_K;
-  }
-  c->lay_tail = false;
+  c->proto.post_layer();
   return 0;
 }
 // the layer enqueued ahead is not wanted after all: its kernels end without touching anything (stream order: whatever is enqueued next runs after them)
 int32_t lasso_point_cancel(lasso_ctx* c) {
-  REQUIRE(c, c && c->lay_active);
-  point_mail(c, c->lay_ell, nullptr, nullptr, 1u);
-  c->lay_active = false; c->lay_tail = false;
+  REQUIRE(c, c && c->proto.lay_active);
+  point_mail(c, c->proto.lay_ell, nullptr, nullptr, 1u);
+  c->proto.cancel_layer();
   return 0;
 }
 // The resident tail enqueued AHEAD of the challenge it binds first (n = 4q): legal while the previous round's result is pending; the first lasso_sumcheck_cubic_tail_next
@@ -994,14 +937,14 @@ int32_t lasso_sumcheck_cubic_tail_begin_ahead(lasso_ctx* c, lasso_fr* const* d_A
 // round) and its LAST publication is the arrays instead of the heads: 2 * ncirc * m_stop values, A_0[0..m_stop), A_1[..], .., B_0[..], ...  m_stop = 1 or 0: the heads.
 int32_t lasso_tail_handover_next(lasso_ctx* c, uint32_t m_stop) {
   REQUIRE(c, c && (m_stop & (m_stop - 1)) == 0 && m_stop <= 128);   // (legal with a tail active: the next begin may be a layer enqueued ahead, lasso_sumcheck_cubic_tail_begin_eq_ahead)
-  c->handover_next = m_stop <= 1 ? 0 : m_stop; return 0;
+  c->proto.handover_next = m_stop <= 1 ? 0 : m_stop; return 0;
 }
 // The same for the primary sumcheck of a linear strategy (k_linear_tail): per round two dot products per polynomial, out[2k] = S0_k, out[2k+1] = S1_k
 // (as lasso_sumcheck_linear_eqw_round, without the unused third slot); after the last challenge the heads out[k] = polys_k[0] (alpha values).
 // d_src is only read (r == NULL: arrays of length n = 2q; otherwise bound with r first, n = 4q).  Challenges go through lasso_sumcheck_cubic_tail_next.
 int32_t lasso_sumcheck_linear_tail_begin(lasso_ctx* c, const lasso_fr* const* d_src, uint32_t alpha, const lasso_fr* d_E, size_t n, const lasso_fr* r) {
   const uint32_t ho = take_handover(c);   // the linear tail has no hand-over form: refused, and the one-shot setting does not survive the refusal
-  REQUIRE(c, d_src && d_E && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= (r ? 4u : 2u) && (n & (n - 1)) == 0 && !c->pending && !c->tail_active && !c->defer_next && !ho && !c->ahead_active);
+  REQUIRE(c, d_src && d_E && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= (r ? 4u : 2u) && (n & (n - 1)) == 0 && !c->proto.pending && !c->proto.tail_active && !c->proto.defer_next && !ho && !c->proto.ahead_active);
   const size_t q = r ? n / 4 : n / 2;
   REQUIRE(c, q >= 1 && q <= CUBIC_TAIL_Q);
   PtrTable Src; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_src[i]); Src.p[i] = (const fr_t*)d_src[i]; }
@@ -1012,35 +955,22 @@ int32_t lasso_sumcheck_linear_tail_begin(lasso_ctx* c, const lasso_fr* const* d_
   if (q <= 256) { if (r) LAUNCH_LTAIL(true, 256, to_fr(r)); else LAUNCH_LTAIL(false, 256, fr_zero()); }
   else { if (r) LAUNCH_LTAIL(true, 512, to_fr(r)); else LAUNCH_LTAIL(false, 512, fr_zero()); }
   HIPCHK(c, hipGetLastError());
-  c->tail_active = true; c->tail_seq0 = seq0; c->tail_turn = 0; c->tail_turns = turns; c->tail_count = (size_t)alpha * 2; c->tail_final = alpha;
-  c->pending = true; c->pending_seq = seq0; c->pending_count = c->tail_count; c->pending_tagged = c->tagged;
+  c->proto.begin_tail(Handoff{seq0, (size_t)alpha * 2, c->tagged}, turns, alpha, false);
   return 0;
 }
 int32_t lasso_sumcheck_cubic_tail_next(lasso_ctx* c, const lasso_fr* r) {
-  REQUIRE(c, r && c->tail_active && !c->pending);
+  REQUIRE(c, r && c->proto.tail_active && !c->proto.pending);
   const fr_t rr = to_fr(r);
-  if (c->tail_unstarted) {   // launched ahead: this is the challenge the kernel binds first; it enables publication tail_seq0 (the first round's sums)
-    c->tail_unstarted = false;
-    post_mail(c, c->tail_seq0, rr.v);
-    c->pending = true; c->pending_seq = c->tail_seq0; c->pending_count = c->tail_count; c->pending_tagged = c->tagged;
-    return 0;
-  }
-  c->tail_turn++;
-  const uint32_t tn = c->tail_seq0 + c->tail_turn;   // = the sequence number of the publication this challenge enables: tags are unique, the mailbox is never reset
-                                                      // (a reset could erase a challenge some workgroup of a multi-workgroup kernel has not read yet)
-  post_mail(c, tn, rr.v);
-  const size_t cnt = c->tail_turn == c->tail_turns ? c->tail_final : c->tail_count;
-  if (cnt) { c->pending = true; c->pending_seq = c->tail_seq0 + c->tail_turn; c->pending_count = cnt; c->pending_tagged = c->tagged; }
-  if (c->tail_turn == c->tail_turns) c->tail_active = false;
+  post_mail(c, c->proto.tail_next(), rr.v);   // (a tail launched ahead: this is the challenge the kernel binds first; it enables the first round's sums)
   return 0;
 }
 // largest q (indices per circuit / polynomial) lasso_sumcheck_{cubic,linear}_tail_begin accept; LASSO_TAIL_Q=256 restores round 2's capacity (A/B measurements)
 uint32_t lasso_sumcheck_tail_capacity(void) { static const uint32_t q = [] { const char* v = getenv("LASSO_TAIL_Q"); const long x = v ? atol(v) : 0; return (uint32_t)(x == 256 ? 256 : CUBIC_TAIL_Q); }(); return q; }
-int32_t lasso_defer_next(lasso_ctx* c) { REQUIRE(c, !c->pending && !c->defer_next); c->defer_next = true; return 0; }
+int32_t lasso_defer_next(lasso_ctx* c) { REQUIRE(c, !c->proto.pending && !c->proto.defer_next); c->proto.defer_next = true; return 0; }
 int32_t lasso_result_wait(lasso_ctx* c, lasso_fr* out, size_t count) {
-  REQUIRE(c, out && c->pending && count == c->pending_count);
-  c->pending = false;
-  { const uint32_t g = c->pending_groups, K = c->pending_K; c->pending_groups = 1; c->pending_K = 0; return wait_flag(c, c->pending_seq, count, out, c->pending_tagged, g, K); }
+  REQUIRE(c, out && c->proto.pending && count == c->proto.result.count);
+  const Handoff h = c->proto.collect();
+  return wait_flag(c, h.seq, count, out, h.tagged, h.groups, h.K);
 }
 // eq-weighted rounds of prove_arbitrary for the linear strategies (k_dot_eqw_* in poly_kernels.cuh)
 int32_t lasso_sumcheck_linear_eqw_round(lasso_ctx* c, const lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n, lasso_fr* out) {
@@ -1078,7 +1008,7 @@ int32_t lasso_sumcheck_linear_eqw_round_fused_from(lasso_ctx* c, const lasso_fr*
 // lasso_sumcheck_linear_eqw_round_fused(.., r, out) enqueued AHEAD of r (in place; gate kernel + k_dot_eqw_fused<AHEAD>): lasso_challenge_post releases it, lasso_result_wait
 // delivers the 3 * alpha values.  Same rules as lasso_sumcheck_cubic_eqw2_begin_ahead.
 int32_t lasso_sumcheck_linear_eqw_round_fused_ahead(lasso_ctx* c, lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n) {
-  REQUIRE(c, d_polys && d_E && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->ahead_active && !c->tail_active && !c->defer_next);
+  REQUIRE(c, d_polys && d_E && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->proto.ahead_active && !c->proto.tail_active && !c->proto.defer_next);
   MutPtrTable P; PtrTable Src; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (fr_t*)d_polys[i]; Src.p[i] = (const fr_t*)d_polys[i]; }
   const size_t q = n / 4; const unsigned ny = alpha, nx = grid_for(q, cubic_nx_cap(ny));
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
@@ -1090,7 +1020,7 @@ int32_t lasso_sumcheck_linear_eqw_round_fused_ahead(lasso_ctx* c, lasso_fr* cons
     hipLaunchKernelGGL(k_dot_eqw_fused<true>, dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Src, P, nx, ny, (const fr_t*)d_E, q, fr_zero(), (fr_t*)c->d_scratch, c->d_counters, RES(c), seq, (const uint32_t*)c->d_gmail);
   }
   HIPCHK(c, hipGetLastError());
-  c->ahead_active = true; c->ahead_bullet = false; c->ahead_seq = seq; c->ahead_count = (size_t)alpha * 3; c->ahead_tagged = c->tagged; c->ahead_groups = 1; c->ahead_K = 0;
+  c->proto.arm_ahead(Handoff{seq, (size_t)alpha * 3, c->tagged}, false);
   return 0;
 }
 // the first round and the first bind of the primary sumcheck from the lookup polynomials' integer values (k_dot_eqw_lb_u32 / k_dot_eqw_fused_from_u32)
@@ -1166,7 +1096,7 @@ static int32_t pack_custom_terms(lasso_ctx* c, const lasso_strategy_custom* s, u
   for (uint32_t j = 0; j < T->num_factors; j++) T->term_mem[j] = (uint8_t)s->term_mem[j];
   if (c->d_terms && buf == c->terms_host) return 0;
   // a new term list: nothing of this context may still be reading the old one
-  if (c->ahead_active || c->lay_active || c->tail_active || c->pending) return fail(c, LASSO_ERR_INVALID, "custom strategy: a new term list cannot be uploaded while a launch of this context is outstanding");
+  if (!c->proto.idle()) return fail(c, LASSO_ERR_INVALID, "custom strategy: a new term list cannot be uploaded while a launch of this context is outstanding");
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (!c->d_terms) HIPCHK(c, dmalloc(c, &c->d_terms, sizeof(CustomTermsDev)));
   c->terms_host.clear();
@@ -1260,7 +1190,7 @@ int32_t lasso_sumcheck_combine_round_lt_scaled(lasso_ctx* c, const lasso_strateg
 // the FIRST round of the LT sumcheck from the polynomials' integer values (entries 0 / 1: the LT and EQ subtables hold bits): exact integer Horner walk, one field product per point for the eq weight
 int32_t lasso_sumcheck_combine_round_lt_u32(lasso_ctx* c, const lasso_strategy* s, const uint32_t* const* d_u32, const lasso_fr* d_eq, size_t n, uint32_t degree, lasso_fr* out) {
   StrategyDev S; WeightTable W; int32_t rc = make_strategy(c, s, S, W); if (rc) return rc;
-  REQUIRE(c, s->kind == LASSO_LT && d_u32 && d_eq && out && n >= 2 && (n & (n - 1)) == 0 && degree == s->c + 1 && s->c <= 16 && !c->defer_next);   // C <= 16: |t| < 2^67 fits the three-limb form (header)
+  REQUIRE(c, s->kind == LASSO_LT && d_u32 && d_eq && out && n >= 2 && (n & (n - 1)) == 0 && degree == s->c + 1 && s->c <= 16 && !c->proto.defer_next);   // C <= 16: |t| < 2^67 fits the three-limb form (header)
   PtrTableU32 P; for (uint32_t i = 0; i < S.alpha; i++) { REQUIRE(c, d_u32[i]); P.p[i] = d_u32[i]; }
   const size_t half = n / 2; const unsigned nx = grid_for(half, 1024); const uint32_t K = degree + 1;
   rc = ensure_scratch(c, (size_t)nx * K * sizeof(fr_t)); if (rc) return rc;
@@ -1632,7 +1562,7 @@ static const niels29* ensure_tab8(lasso_ctx* c, const lasso_bases* cb, uint32_t 
 // the byte-multiple tables the commitments of small scalars read (k_msm_rows8 / k_msm_rows8w), built NOW instead of inside the first commitment that uses them: a caller that times
 // `commit` (benches/bench.rs:54-66) prepares its generators first.  byte_windows = 1 (values < 2^8) or 2 (< 2^16).  A table that cannot be allocated is not an error (the bucket kernel serves).
 int32_t lasso_bases_prepare(lasso_ctx* c, const lasso_bases* b, uint32_t byte_windows) {
-  REQUIRE(c, b && byte_windows >= 1 && byte_windows <= 2 && !c->ahead_active && !c->lay_active && !c->tail_active);
+  REQUIRE(c, b && byte_windows >= 1 && byte_windows <= 2 && !c->proto.waiting_on_device() && !c->proto.tail_active);
   if (!msm_rows8_enabled()) return 0;
   for (uint32_t w = 0; w < byte_windows; w++) if (!ensure_tab8(c, b, w)) break;
   return 0;
@@ -1943,7 +1873,7 @@ static int32_t bullet_round_fused(lasso_ctx* c, const lasso_bases* b, size_t n, 
     else { if (w8) LAUNCH_BULLET(false, 8, b->d_mult8, nullptr, nullptr, nullptr, z, z); else LAUNCH_BULLET(false, 4, b->d_mult, nullptr, nullptr, nullptr, z, z); }
   }
   HIPCHK(c, hipGetLastError());
-  if (ahead) { c->ahead_active = true; c->ahead_bullet = true; c->ahead_seq = seq; c->ahead_tagged = msm_tagged(c); c->ahead_count = 2 * (sizeof(ed_point) / sizeof(fr_t)); return 0; }
+  if (ahead) { c->proto.arm_ahead(Handoff{seq, 2 * (sizeof(ed_point) / sizeof(fr_t)), msm_tagged(c)}, true); return 0; }
   return wait_flag(c, seq, 2 * (sizeof(ed_point) / sizeof(fr_t)), (lasso_fr*)out, msm_tagged(c));
 }
 // slab mode of the opening (include/lasso_hip.h): this rank's share of L and R over its residue class of the generators
@@ -2001,7 +1931,7 @@ int32_t lasso_bullet_ahead_ok(lasso_ctx* c, const lasso_bases* b) { return c && 
 int32_t lasso_bullet_round_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, const lasso_fr* d_a_in, const lasso_fr* d_b_in, const lasso_fr* d_w_in, lasso_fr* d_a_out, lasso_fr* d_b_out,
                                  lasso_fr* d_w_out, size_t nk, const lasso_fr* blinds) {
   REQUIRE(c, b && d_a_in && d_b_in && d_w_in && d_a_out && d_b_out && d_w_out && blinds && n >= 2 && (n & (n - 1)) == 0 && nk >= 2 && 2 * nk <= n && (nk & (nk - 1)) == 0 && n + 2 <= b->n &&
-             d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in && !c->ahead_active && !c->tail_active && !c->defer_next);
+             d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in && !c->proto.ahead_active && !c->proto.tail_active && !c->proto.defer_next);
   if (!bullet_ahead_possible(c, b)) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_bullet_round_ahead: not available for this generator set / configuration (lasso_bullet_ahead_ok)");
   return bullet_round_fused(c, b, n, d_a_in, d_b_in, d_w_in, d_a_out, d_b_out, d_w_out, nk, nullptr, nullptr, blinds, nullptr, 1, 0, true);
 }
@@ -2015,12 +1945,12 @@ int32_t lasso_bullet_tail_ahead_ok(lasso_ctx* c, const lasso_bases* b) {
   return c && !off && bullet_ahead_possible(c, b) && msm_tagged(c) ? 1 : 0;
 }
 int32_t lasso_bullet_tail_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, lasso_fr* d_a, lasso_fr* d_b, const lasso_fr* d_w, size_t nw, lasso_fr* d_w_out, const lasso_fr* scale, const lasso_fr* tail) {
-  REQUIRE(c, b && d_a && d_b && d_w && d_w_out && scale && tail && n >= 2 && (n & (n - 1)) == 0 && 2 * nw == n && n + 2 <= b->n && d_w != d_w_out && !c->ahead_active && !c->tail_active && !c->defer_next && !c->lay_active);
+  REQUIRE(c, b && d_a && d_b && d_w && d_w_out && scale && tail && n >= 2 && (n & (n - 1)) == 0 && 2 * nw == n && n + 2 <= b->n && d_w != d_w_out && !c->proto.waiting_on_device() && !c->proto.tail_active && !c->proto.defer_next);
   if (!lasso_bullet_tail_ahead_ok(c, b)) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_bullet_tail_ahead: not available for this generator set / configuration (lasso_bullet_tail_ahead_ok)");
   const size_t row = n + 2;
-  c->no_grow = true;   // nothing may synchronise the stream here: the previous round's kernel may still be running, its result uncollected
+  c->proto.no_grow = true;   // nothing may synchronise the stream here: the previous round's kernel may still be running, its result uncollected
   int32_t rc = ensure_scratch(c, msm_pts_bytes(1, row) + 512); if (!rc) rc = ensure_small(c, 8);
-  c->no_grow = false;
+  c->proto.no_grow = false;
   if (rc) return rc == LASSO_ERR_UNSUPPORTED ? fail(c, rc, "lasso_bullet_tail_ahead: a buffer would have to grow while kernels are in flight") : rc;
   const uint32_t seq = next_seq(c);
   hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->mail_d, c->d_gmail, seq, 1u);
@@ -2030,15 +1960,13 @@ int32_t lasso_bullet_tail_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, la
   const MsmColMap id = {0, 0, 0, 0};
   const lasso_fr* heads[2] = {d_a, d_b};
   rc = run_msm_direct(c, (const uint8_t*)d_w_out, row * 32, 1, row, id, b, (uint8_t*)c->d_scratch, nullptr, 2, scale, tail, 1, 0, heads, &seq); if (rc) return rc;
-  c->ahead_active = true; c->ahead_bullet = true; c->ahead_seq = seq; c->ahead_tagged = true; c->ahead_count = sizeof(ed_point) / sizeof(fr_t) + 2;
+  c->proto.arm_ahead(Handoff{seq, sizeof(ed_point) / sizeof(fr_t) + 2, true}, true);   // armed only after run_msm_direct has returned: a failure there leaves the gate enqueued and nothing armed (known; changing it is a change of behaviour)
   return 0;
 }
 int32_t lasso_bullet_post(lasso_ctx* c, const lasso_fr* u, const lasso_fr* u_inv) {
-  REQUIRE(c, u && u_inv && c->ahead_active && c->ahead_bullet && !c->pending);
-  mail_chunks(c->mail_h + 12, c->ahead_seq, (const uint32_t*)u_inv);
-  post_mail(c, c->ahead_seq, (const uint32_t*)u);
-  c->ahead_active = false;
-  c->pending = true; c->pending_seq = c->ahead_seq; c->pending_count = c->ahead_count; c->pending_tagged = c->ahead_tagged; c->pending_groups = 1; c->pending_K = 0;
+  REQUIRE(c, u && u_inv && c->proto.ahead_active && c->proto.ahead_bullet && !c->proto.pending);
+  mail_chunks(c->mail_h + 12, c->proto.ahead.seq, (const uint32_t*)u_inv);
+  post_mail(c, c->proto.post_ahead(), (const uint32_t*)u);
   return 0;
 }
 int32_t lasso_bullet_fold(lasso_ctx* c, lasso_fr* d_a, lasso_fr* d_b, size_t nk, const lasso_fr* d_w, size_t nw, lasso_fr* d_w_out, const lasso_fr* u, const lasso_fr* u_inv) {

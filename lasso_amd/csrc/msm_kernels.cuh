@@ -789,7 +789,7 @@ __device__ __forceinline__ void msm_direct_finish(pt29* pts, fe29 (*st)[4], uint
   MSM_STAMP(4);
   if (flag == LASSO_TAGGED) {
     // round 6 (profiles/r06_bullet_phase_*_before.txt: conversion by ONE lane + system fence + ticket + flag = 2.5-3.4 us at the very end of every launch's critical path): the row's
-    // point leaves as four self-validating elements (poly_kernels.cuh result_store: three 16-byte chunks each, tagged with the launch's sequence number), one coordinate per lane —
+    // point leaves as four self-validating elements (handoff_device.cuh result_store: three 16-byte chunks each, tagged with the launch's sequence number), one coordinate per lane —
     // no ticket between the rows, no flag; the host reads the 2 x 4 elements of the launch like any tagged result.  out_mont = the context's tagged area.
     if (t < 4) {
       const fq_t q = pt_coord_abi(pts[0], t);

@@ -1140,6 +1140,149 @@ def test_launch_wait_protocol_errors(devs):
         d.free(pa); d.free(pw)
 
 
+# What the device library refuses in each state of the hand-off protocol (lasso_amd/csrc/handoff.cuh), read off the REQUIREs of lasso_hip.hip: state -> (call, return code).
+# Only refusals: a refused call returns on the host before any launch.  Calls that are legal in a state are not listed — they would act (lasso_sync under a resident tail
+# would sit in the kernel's 5 s bail-out).  -1 = LASSO_ERR_INVALID, -4 = LASSO_ERR_UNSUPPORTED.
+_NOT_POSTABLE = (("challenge_post", -1), ("bullet_post", -1), ("point_post", -1), ("point_cancel", -1), ("tail_next", -1))
+_WAITING = (("sync", -1), ("trim", -1), ("free", -1), ("upload", -1), ("download", -1), ("bases_prepare", -1), ("result_wait", -1))
+_TAIL = (("trim", -1), ("bases_prepare", -1), ("result_wait", -1), ("eqw2_begin_ahead", -1), ("linear_round_ahead", -1), ("tail_begin", -1), ("tail_begin_eq", -1), ("tail_begin_ahead", -1),
+         ("linear_tail_begin", -1), ("bullet_round_ahead", -1), ("bullet_tail_ahead", -1), ("challenge_post", -1), ("bullet_post", -1), ("point_post", -1), ("point_cancel", -1))
+_AHEAD = _WAITING + (("eqw2_begin_ahead", -1), ("linear_round_ahead", -1), ("eqw2_begin_eq_ahead", -1), ("tail_begin", -1), ("tail_begin_eq", -1), ("tail_begin_ahead", -1), ("tail_begin_eq_ahead", -1),
+                     ("linear_tail_begin", -1), ("bullet_round_ahead", -1), ("bullet_tail_ahead", -1), ("point_post", -1), ("point_cancel", -1), ("tail_next", -1))
+PROTOCOL_REFUSALS = {
+    "pending": (("trim", -1), ("defer_next", -1), ("result_wait_wrong_count", -1), ("eqw2_begin", -1), ("eqw2_begin_eq", -1), ("tail_begin", -1), ("tail_begin_eq", -1), ("linear_tail_begin", -1)) + _NOT_POSTABLE,
+    "deferred": (("defer_next", -1), ("result_wait", -1), ("eqw2_begin_ahead", -1), ("linear_round_ahead", -1), ("eqw2_begin_eq_ahead", -1), ("tail_begin", -1), ("tail_begin_eq", -1), ("tail_begin_ahead", -1),
+                 ("tail_begin_eq_ahead", -1), ("linear_tail_begin", -1), ("bullet_round_ahead", -1), ("bullet_tail_ahead", -1)) + _NOT_POSTABLE,
+    "round_ahead": _AHEAD + (("bullet_post", -1),),
+    "bullet_ahead": _AHEAD + (("challenge_post", -1),),
+    "layer_ahead": _WAITING + (("eqw2_begin_eq_ahead", -1), ("tail_begin", -1), ("tail_begin_eq", -1), ("tail_begin_ahead", -1), ("tail_begin_eq_ahead", -4), ("bullet_tail_ahead", -1),
+                               ("challenge_post", -1), ("bullet_post", -1), ("tail_next", -1), ("point_post_wrong_ell", -1)),
+    "tail": _TAIL,
+    "tail_unstarted": _TAIL,
+}
+
+
+def test_protocol_refusals_unchanged(devs):
+    """Every state of the hand-off protocol, entered and left the way the prover does (post, then lasso_result_wait) on the device library and on the mock with the same values
+    collected; in each state the device library refuses every call of PROTOCOL_REFUSALS with the recorded code, and the refusals leave nothing behind."""
+    real, mock = devs
+    L, ctx = real.lib, real.ctx
+    rng = np.random.default_rng(4242)
+    vp = lambda x: np.ascontiguousarray(x, dtype=np.uint64).ctypes.data_as(C.c_void_p)
+    cp = C.c_void_p
+    r1, r2, r3 = rand_fr(rng, 3, edge=False); pt7 = rand_fr(rng, 7, edge=False); sc = rand_fr(rng, 1, edge=False)[0]; two = rand_fr(rng, 2, edge=False)
+    g = gens(mock.lib, b"gens_sparse_poly", 8 + 1)
+    # arguments of the refused calls: valid in everything but the state, on buffers of their own (allocated now: nothing may be uploaded in some of the states)
+    xa = real._ptrs([real.upload(rand_fr(rng, 512))]); xb = real._ptrs([real.upload(rand_fr(rng, 512))]); xe = cp(real.upload(rand_fr(rng, 256)))
+    xo = [cp(real.alloc(32 * 8)) for _ in range(3)]; xbases = cp(real.bases_create(g)); host = np.zeros((8, 4), dtype=np.uint64)
+    calls = {
+        "sync": lambda: L.lasso_sync(ctx), "trim": lambda: L.lasso_trim(ctx), "free": lambda: L.lasso_free(ctx, xe),
+        "upload": lambda: L.lasso_upload(ctx, xe, vp(host), 32), "download": lambda: L.lasso_download(ctx, vp(host), xe, 32), "bases_prepare": lambda: L.lasso_bases_prepare(ctx, xbases, 1),
+        "defer_next": lambda: L.lasso_defer_next(ctx), "result_wait": lambda: L.lasso_result_wait(ctx, vp(host), 2), "result_wait_wrong_count": lambda: L.lasso_result_wait(ctx, vp(host), 3),
+        "challenge_post": lambda: L.lasso_challenge_post(ctx, vp(r1)), "bullet_post": lambda: L.lasso_bullet_post(ctx, vp(r1), vp(r2)),
+        "point_post": lambda: L.lasso_point_post(ctx, vp(pt7), 7, vp(sc)), "point_post_wrong_ell": lambda: L.lasso_point_post(ctx, vp(pt7), 6, vp(sc)), "point_cancel": lambda: L.lasso_point_cancel(ctx),
+        "tail_next": lambda: L.lasso_sumcheck_cubic_tail_next(ctx, vp(r1)),
+        "eqw2_begin": lambda: L.lasso_sumcheck_cubic_eqw2_begin(ctx, xa, xb, 1, xe, 8, None),
+        "eqw2_begin_ahead": lambda: L.lasso_sumcheck_cubic_eqw2_begin_ahead(ctx, xa, xb, 1, xe, 512),
+        "eqw2_begin_eq": lambda: L.lasso_sumcheck_cubic_eqw2_begin_eq(ctx, xa, xb, 1, xe, 256, vp(pt7), 7, vp(sc)),
+        "eqw2_begin_eq_ahead": lambda: L.lasso_sumcheck_cubic_eqw2_begin_eq_ahead(ctx, xa, xb, 1, xe, 256, 7),
+        "tail_begin": lambda: L.lasso_sumcheck_cubic_tail_begin(ctx, xa, xb, 1, xe, 8, None),
+        "tail_begin_eq": lambda: L.lasso_sumcheck_cubic_tail_begin_eq(ctx, xa, xb, 1, 8, vp(pt7), 2, vp(sc)),
+        "tail_begin_ahead": lambda: L.lasso_sumcheck_cubic_tail_begin_ahead(ctx, xa, xb, 1, xe, 8),
+        "tail_begin_eq_ahead": lambda: L.lasso_sumcheck_cubic_tail_begin_eq_ahead(ctx, xa, xb, 1, 8, 2),
+        "linear_tail_begin": lambda: L.lasso_sumcheck_linear_tail_begin(ctx, xa, 1, xe, 8, None),
+        "linear_round_ahead": lambda: L.lasso_sumcheck_linear_eqw_round_fused_ahead(ctx, xa, 1, xe, 512),
+        "bullet_round_ahead": lambda: L.lasso_bullet_round_ahead(ctx, xbases, 8, xa[0], xb[0], xe, xo[0], xo[1], xo[2], 2, vp(two)),
+        "bullet_tail_ahead": lambda: L.lasso_bullet_tail_ahead(ctx, xbases, 8, xa[0], xb[0], xe, 4, xo[2], vp(sc), vp(two)),
+    }
+    assert {name for rows in PROTOCOL_REFUSALS.values() for name, _ in rows} <= set(calls)
+
+    def wait(d, count):
+        out = np.empty((count, 4), dtype=np.uint64); d._chk(d.lib.lasso_result_wait(d.ctx, vp(out), count)); return out
+
+    def arrays(d, seed, n, n_e):
+        rs = np.random.default_rng(seed)
+        return [d.upload(rand_fr(rs, n))], [d.upload(rand_fr(rs, n))], d.upload(rand_fr(rs, n_e))
+
+    # each scenario: enter the state, `check()` (the refusals, on the device library only), leave it by completing the protocol; returns what was collected on the way
+    def pending(d, check):
+        pa, pb, pe = arrays(d, 1, 8, 4)
+        d._chk(d.lib.lasso_sumcheck_cubic_eqw2_begin(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 8, None))
+        check()
+        return [wait(d, 2)], pa + pb + [pe]
+
+    def deferred(d, check):
+        pa, pb, pe = arrays(d, 2, 8, 8)
+        d._chk(d.lib.lasso_defer_next(d.ctx))
+        check()
+        d._chk(d.lib.lasso_multi_dot(d.ctx, d._ptrs(pa), 1, cp(pe), 8, vp(host.copy())))
+        return [wait(d, 1)], pa + pb + [pe]
+
+    def round_ahead(d, check):
+        pa, pb, pe = arrays(d, 3, 512, 256)
+        d._chk(d.lib.lasso_sumcheck_cubic_eqw2_begin(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 512, None))
+        d._chk(d.lib.lasso_sumcheck_cubic_eqw2_begin_ahead(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 512))
+        outs = [wait(d, 2)]
+        check()
+        d._chk(d.lib.lasso_challenge_post(d.ctx, vp(r1)))
+        return outs + [wait(d, 2)], pa + pb + [pe]
+
+    def bullet_ahead(d, check):
+        rs = np.random.default_rng(4)
+        bases = d.bases_create(g)
+        bufs = [d.upload(rand_fr(rs, 4, edge=False)), d.upload(rand_fr(rs, 4, edge=False)), d.upload(rand_fr(rs, 2, edge=False)), d.alloc(32 * 2), d.alloc(32 * 2), d.alloc(32 * 4)]
+        d._chk(d.lib.lasso_bullet_round_ahead(d.ctx, cp(bases), 8, *[cp(p) for p in bufs], 2, vp(two)))
+        check()
+        d._chk(d.lib.lasso_bullet_post(d.ctx, vp(r2), vp(r3)))
+        pts = wait(d, 8)
+        d.bases_destroy(bases)
+        return [np.frombuffer(b"".join(compress_points(mock.lib, pts.reshape(2, -1))), dtype=np.uint8)], bufs
+
+    def layer_ahead(d, check):
+        pa, pb, pe = arrays(d, 5, 256, 128)
+        d._chk(d.lib.lasso_sumcheck_cubic_eqw2_begin_eq_ahead(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 256, 7))
+        check()
+        d._chk(d.lib.lasso_point_post(d.ctx, vp(pt7), 7, vp(sc)))
+        return [wait(d, 2)], pa + pb + [pe]
+
+    def tail(d, check):
+        pa, pb, pe = arrays(d, 6, 8, 4)
+        d._chk(d.lib.lasso_sumcheck_cubic_tail_begin(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 8, None))
+        outs = [wait(d, 2)]
+        check()
+        for r in (r1, r2, r3):
+            d._chk(d.lib.lasso_sumcheck_cubic_tail_next(d.ctx, vp(r))); outs.append(wait(d, 2))
+        return outs, pa + pb + [pe]
+
+    def tail_unstarted(d, check):
+        pa, pb, pe = arrays(d, 7, 16, 8)
+        d._chk(d.lib.lasso_sumcheck_cubic_eqw2_begin(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 16, vp(r3)))     # the round before: binds 16 -> 8, result pending
+        d._chk(d.lib.lasso_sumcheck_cubic_tail_begin_ahead(d.ctx, d._ptrs(pa), d._ptrs(pb), 1, cp(pe), 8))
+        outs = [wait(d, 2)]
+        check()
+        for r in (r1, r2, r3):      # the first one starts the tail
+            d._chk(d.lib.lasso_sumcheck_cubic_tail_next(d.ctx, vp(r))); outs.append(wait(d, 2))
+        return outs, pa + pb + [pe]
+
+    scenarios = {"pending": pending, "deferred": deferred, "round_ahead": round_ahead, "bullet_ahead": bullet_ahead, "layer_ahead": layer_ahead, "tail": tail, "tail_unstarted": tail_unstarted}
+    assert set(scenarios) == set(PROTOCOL_REFUSALS)
+    for state, scenario in scenarios.items():
+        def check():
+            got = [(name, calls[name]()) for name, _ in PROTOCOL_REFUSALS[state]]
+            assert got == list(PROTOCOL_REFUSALS[state]), state
+        want, bufs = scenario(mock, lambda: None)
+        for p in bufs:
+            mock.free(p)
+        got, bufs = scenario(real, check)
+        assert len(got) == len(want) and all(np.array_equal(x, y) for x, y in zip(got, want)), state
+        assert L.lasso_sync(ctx) == 0 and L.lasso_trim(ctx) == 0, state      # idle again
+        for p in bufs:
+            real.free(p)
+    for p in (xa[0], xb[0], xe.value, *[x.value for x in xo]):
+        real.free(p)
+    real.bases_destroy(xbases.value)
+
+
 @pytest.mark.parametrize("n_lookups,c,log_m,mode", [(1, 1, 0, "rand"), (2, 1, 1, "rand"), (5, 2, 4, "rand"), (1000, 3, 8, "rand"), (4096, 1, 16, "rand"), (5000, 2, 12, "rand"),
                                                      (1 << 16, 1, 16, "rand"), (70000, 1, 17, "rand"), (9000, 1, 16, "same"), (1 << 15, 2, 3, "rand"), (12345, 1, 9, "sorted")])
 def test_densify_dim(devs, n_lookups, c, log_m, mode):
