@@ -15,6 +15,7 @@
 // scalar loop and its smaller take-over sizes.
 #pragma once
 #include "field_host.hpp"
+#include "switches.hpp"
 #if defined(__x86_64__) && defined(__GNUC__) && defined(LASSO_HAVE_H4) && !defined(LASSO_NO_HOST_IFMA)
 #include <immintrin.h>
 #include <cstdlib>
@@ -25,7 +26,7 @@
 namespace lasso {
 
 __attribute__((target("arch=x86-64"))) inline bool field52_ok() {
-  static const bool ok = [] { __builtin_cpu_init(); const char* v = getenv("LASSO_HOST_IFMA"); return !(v && v[0] == '0') && __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma"); }();
+  static const bool ok = [] { __builtin_cpu_init(); return sw::host_ifma() && __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma"); }();
   return ok;
 }
 
@@ -214,4 +215,6 @@ class HostRounds52 {
 };
 
 }  // namespace lasso
+#else
+namespace lasso { inline bool field52_ok() { return false; } }   // no vector form in this build: the scalar loop
 #endif

@@ -20,6 +20,8 @@
 #include <vector>
 #include "field_host.hpp"
 #include "field52.hpp"
+#include "switches.hpp"
+#include "sumcheck_phase.hpp"
 #include "hashes.hpp"
 #include "../../include/lasso_prover.h"
 #include "../../include/lasso_custom_check.h"
@@ -33,9 +35,9 @@ namespace lasso {
 // Wall-clock spans with the reference's `tracing` span names, printed when LASSO_TRACE=1 — so a run can be
 // laid next to src/benches/*.log line by line.  Device work is asynchronous: a span closes after a stream sync only when tracing.
 struct Trace {
-  static bool on() { static const bool v = [] { const char* e = getenv("LASSO_TRACE"); return e && e[0] == '1'; }(); return v; }
+  static bool on() { return sw::trace() == 1; }
   // LASSO_TRACE=3: device bytes per span instead (live at entry, the span's own high-water mark; lasso_mem_stats with reset, so an enclosing span reports what followed its last child)
-  static bool mem() { static const bool v = [] { const char* e = getenv("LASSO_TRACE"); return e && e[0] == '3'; }(); return v; }
+  static bool mem() { return sw::trace() == 3; }
   const char* name; lasso_ctx* ctx; std::chrono::steady_clock::time_point t0; static int& depth() { static thread_local int d = 0; return d; }
   uint64_t w0 = 0; double wus0 = 0; uint64_t live0 = 0;
   Trace(const char* n, lasso_ctx* c) : name(n), ctx(c) {
@@ -58,7 +60,7 @@ struct Trace {
 
 // LASSO_TRACE=2: host-side time buckets (where the host spends its share of a proof), printed with the SparsePoly.prove span
 struct HostClock {
-  static bool on() { static const bool v = [] { const char* e = getenv("LASSO_TRACE"); return e && e[0] == '2'; }(); return v; }
+  static bool on() { return sw::trace() == 2; }
   static std::map<std::string, double>& buckets() { static thread_local std::map<std::string, double> b; return b; }
   const char* name; std::chrono::steady_clock::time_point t0;
   explicit HostClock(const char* n) : name(n) { if (on()) t0 = std::chrono::steady_clock::now(); }
@@ -124,14 +126,12 @@ class Dev {
   // (half of every tree: the fingerprints are recomputed strip by strip when the bottom layer's two streaming rounds need them, Prover::leaf_rounds).
   // Round 4 first tried the obvious thing, handing every released buffer straight back to the driver: measured on configs[3] it bought nothing at P <= 4 (the
   // high-water mark is the live set at the tree phase, not the pool) and cost 10x the proof time in hipFree / hipMalloc (profiles/r04_slab_peak_bytes_first_cut.json).
-  // LASSO_CAPACITY=1 turns it on for every host; lasso_host_set_capacity sets it per host; default: off.
-  bool capacity = [] { const char* e = getenv("LASSO_CAPACITY"); return e && e[0] == '1'; }();
+  bool capacity = sw::capacity();   // LASSO_CAPACITY=1 turns it on for every host; lasso_host_set_capacity sets it per host
   bool throughput = false;   // lasso_host_set_throughput_mode: several hosts prove concurrently on this GPU — nothing of this host is launched ahead of its challenge (LASSO_THROUGHPUT_AHEAD=1: launched ahead all the same — since round 5 the wait is one gate wave, not a kernel's worth of compute units; A/B switch)
-  bool no_ahead() const { static const bool keep = [] { const char* e = getenv("LASSO_THROUGHPUT_AHEAD"); return e && e[0] == '1'; }(); return throughput && !keep; }
+  bool no_ahead() const { return throughput && !sw::throughput_ahead(); }
   explicit Dev(int device) : device_(device) {
     if (lasso_ctx_create(device, &ctx) != 0) throw Error(std::string("lasso_ctx_create: ") + lasso_last_error(nullptr));
-    const char* e = getenv("LASSO_SIDE_STREAM");
-    if (!(e && e[0] == '0')) (void)side();   // created up front: a context costs ~9 ms, which must not land inside the first proof
+    if (sw::side_stream()) (void)side();   // created up front: a context costs ~9 ms, which must not land inside the first proof
   }
   ~Dev() { if (side_) lasso_ctx_destroy(side_); if (ctx) { for (auto& kv : pool_) lasso_free(ctx, kv.second); for (auto& kv : live_) lasso_free(ctx, kv.first); lasso_ctx_destroy(ctx); } }
   // A second context on the same device (own stream, scratch and result buffer): streaming work that does not depend on the transcript is
@@ -428,8 +428,7 @@ struct PolyCommitmentGens {
       sub[n / P] = affine[n]; sub[n / P + 1] = affine[n + 1];
       d.chk(lasso_bases_create_opt(d.ctx, sub.data(), sub.size(), d.capacity ? 0 : 1, &bases_slab), "lasso_bases_create");
       // the sharded opening is used only if EVERY rank has the table it needs (an allocation that failed on one rank must not split the ranks between two protocols)
-      static const bool off = [] { const char* e = getenv("LASSO_SLAB_OPEN"); return e && e[0] == '0'; }();
-      std::vector<uint8_t> all(P, 0); const uint8_t mine = (!off && lasso_bases_has_direct(bases_slab) == 1) ? 1 : 0;
+      std::vector<uint8_t> all(P, 0); const uint8_t mine = (sw::slab_open() && lasso_bases_has_direct(bases_slab) == 1) ? 1 : 0;
       d.comm.allgather(&mine, all.data(), 1);
       slab_open = true; for (uint8_t v : all) slab_open = slab_open && v;
     }
@@ -679,9 +678,6 @@ inline void append_poly_commitment(ProofTranscript& t, const char* label, const 
 
 // ------------------------------------------------------------------ DensifiedRepresentation (densified.rs:8-97)
 struct SparsePolynomialCommitment { PolyCommitment l_variate_polys_commitment, log_m_variate_polys_commitment; size_t s, log_m, m; };
-// capacity mode: local lookup count from which the operations' trees are kept without leaves and dim / read are kept compact
-inline size_t capacity_leafless_min() { static const size_t v = [] { const char* e = getenv("LASSO_LEAFLESS_MIN"); const size_t x = e ? (size_t)atoll(e) : ((size_t)1 << 16); return x < 64 ? (size_t)64 : x; }(); return v; }
-inline bool capacity_compact_off() { static const bool v = [] { const char* e = getenv("LASSO_CAPACITY_COMPACT"); return e && e[0] == '0'; }(); return v; }
 struct DensifiedRepresentation {
   const Dev* dev; size_t C, s, log_m, m;               // global sizes
   size_t s_loc, m_loc;                                  // this rank's share (== s, m when not sharded)
@@ -713,7 +709,7 @@ struct DensifiedRepresentation {
     D->nv_l = ceil_log2(n_l); D->nv_m = ceil_log2(n_m);
     if (d.comm.sharded() && (((size_t)1 << (D->nv_m - D->nv_m / 2)) < P || ((size_t)1 << (D->nv_l - D->nv_l / 2)) < P)) throw Error("slab sharding needs every Hyrax matrix to have at least one column per rank");
     // compact form needs a polynomial to be whole rows of the Hyrax matrix (s >= its row length: true from s = 2 * next_pow2(2C) on)
-    D->compact = d.capacity && !capacity_compact_off() && D->s_loc >= capacity_leafless_min() && s >= ((size_t)1 << (D->nv_l - D->nv_l / 2));
+    D->compact = d.capacity && sw::capacity_compact() && D->s_loc >= sw::leafless_min() && s >= ((size_t)1 << (D->nv_l - D->nv_l / 2));
     D->combined_log_m_variate_polys = DBuf(d, n_m / P);
     if (!D->compact) D->combined_l_variate_polys = DBuf(d, n_l / P);
     // DensePolynomial::merge pads with zeros up to the next power of two (dense_mlpoly.rs:251-261)
@@ -787,14 +783,13 @@ class Prover {
   // point (lasso_point_post) instead of launching — or cancels when the layer turns out to have another shape (a zero coordinate: probability 2^-252, scripted tests).
   struct LayerAhead { bool on = false, tail = false; std::vector<lasso_fr*> A, B; lasso_fr* d_table = nullptr; size_t len = 0, m_stop = 1; uint32_t ell = 0; } layer_ahead;
   std::function<void()> next_layer_hook;
-  static bool tail_switched_off() { static const bool off = [] { const char* v = getenv("LASSO_CUBIC_TAIL"); return v && v[0] == '0'; }(); return off; }
-  bool layer_ahead_ok() { return P == 1 && !d.no_ahead() && !eq_inline_off() && !tail_switched_off() && lasso_layer_ahead_ok(d.ctx) == 1; }
-  // what cubic_rounds would launch first for a whole plain layer of k circuits and `len` elements per circuit, enqueued now (mirrors its choices: tail_from, m_stop, the table sizes)
-  void enqueue_layer_ahead(const std::vector<lasso_fr*>& A, const std::vector<lasso_fr*>& B, size_t len, lasso_fr* d_table) {
+  // Layer `layer_id` of whole trees on one GPU (P == 1, no capacity mode): what cubic_rounds would launch first for the arrays bgpa_prove will pass to its sumcheck — k circuits, A = the
+  // layer's first half, B its second, `len` elements each — enqueued now (mirrors its choices: tail_from, m_stop, the table sizes)
+  void enqueue_next_layer(const std::vector<lasso_fr*>& trees, size_t n, size_t layer_id, lasso_fr* d_table) {
     layer_ahead.on = false;
-    if (!layer_ahead_ok() || len < 4) return;
-    const size_t k = A.size(); const uint32_t ell = (uint32_t)ceil_log2(len / 2);
-    LayerAhead la; la.A = A; la.B = B; la.d_table = d_table; la.len = len; la.ell = ell;
+    const size_t len = (n >> layer_id) / 2, off = 2 * n - 4 * len, k = trees.size(); const uint32_t ell = (uint32_t)ceil_log2(len / 2);
+    if (!(P == 1 && !d.no_ahead() && sw::eq_inline() && sw::cubic_tail() && lasso_layer_ahead_ok(d.ctx) == 1) || len < 4) return;
+    LayerAhead la; la.d_table = d_table; la.len = len; la.ell = ell; for (auto* tr : trees) { la.A.push_back(tr + off); la.B.push_back(tr + off + len); }
     int32_t rc;
     if (len / 2 <= tail_q()) {   // the whole layer in the resident kernel (tail_from = 0)
       if (ell > 9) return;
@@ -809,8 +804,6 @@ class Prover {
     d.chk(rc, "lasso_sumcheck_cubic_*_begin_eq_ahead");
     la.on = true; layer_ahead = std::move(la);
   }
-  static bool eq_inline_off() { static const bool v = [] { const char* e = getenv("LASSO_EQ_INLINE"); return e && e[0] == '0'; }(); return v; }
-  static bool side_off() { static const bool v = [] { const char* e = getenv("LASSO_SIDE_STREAM"); return e && e[0] == '0'; }(); return v; }
 
  public:
   std::vector<uint8_t> proof_bytes;
@@ -831,25 +824,19 @@ class Prover {
   }
   // The eq-weighted cubic rounds only ever read the first HALF of a layer's eq table (x_0 = 0; cubic_rounds below), and that half is
   // (1 - point[0]) * eq(point[1..]): build just that (half the field multiplications and HBM writes of EqPolynomial::evals, eq_poly.rs:29-42).
-  void eq_half_local(const ScVec& point, lasso_fr* d_out) {
+  LazyEq eq_half_spec(const ScVec& point, lasso_fr* d_out) {   // the table as a specification; not `on`: no local round reads a table
     LASSO_REQUIRE(point.size() >= lgP);
-    if (point.size() == lgP) return;   // no local round reads a table
-    std::vector<lasso_fr> rr; for (size_t i = 1; i + lgP < point.size(); i++) rr.push_back(point[i].abi());
+    LazyEq z; if (point.size() == lgP) return z;
+    for (size_t i = 1; i + lgP < point.size(); i++) z.rr.push_back(point[i].abi());
     Sc scale = Sc::one() - point[0]; if (P > 1) scale *= d.comm.eq_low(point);
-    lasso_fr sc = scale.abi();
-    d.chk(lasso_eq_evals_scaled(d.ctx, rr.data(), (uint32_t)rr.size(), &sc, d_out), "lasso_eq_evals_scaled");
+    z.scale = scale.abi(); z.d_table = d_out; z.on = true; return z;
   }
-  // the same table as a specification instead of a launch (consumed by cubic_rounds, see LazyEq)
-  void eq_half_lazy(const ScVec& point, lasso_fr* d_out) {
-    LASSO_REQUIRE(point.size() >= lgP);
-    lazy_eq.on = false;
-    if (point.size() == lgP) return;
-    lazy_eq.rr.clear(); for (size_t i = 1; i + lgP < point.size(); i++) lazy_eq.rr.push_back(point[i].abi());
-    Sc scale = Sc::one() - point[0]; if (P > 1) scale *= d.comm.eq_low(point);
-    lazy_eq.scale = scale.abi(); lazy_eq.d_table = d_out; lazy_eq.on = true;
-  }
-  // local arrays are down to ONE element each: all-gather them into P-element replicated arrays (index = rank = the remaining low variables)
-  std::vector<lasso_fr*> gather_tail(const std::vector<lasso_fr*>& polys) {
+  void eq_build(LazyEq& z) { if (z.on) { d.chk(lasso_eq_evals_scaled(d.ctx, z.rr.data(), (uint32_t)z.rr.size(), &z.scale, z.d_table), "lasso_eq_evals_scaled"); z.on = false; } }
+  void eq_half_local(const ScVec& point, lasso_fr* d_out) { LazyEq z = eq_half_spec(point, d_out); eq_build(z); }
+  void eq_half_lazy(const ScVec& point, lasso_fr* d_out) { lazy_eq = eq_half_spec(point, d_out); }   // built later, by cubic_rounds (see LazyEq)
+  // The slab skeleton's middle step, between the local and the replicated rounds.  The local arrays are down to ONE element each: all-gather them into P-element replicated
+  // arrays (index = rank = the remaining low variables); d_eq (optional) receives the whole P-entry eq table over the remaining coordinates point[local_rounds .. num_rounds)
+  std::vector<lasso_fr*> slab_tail(const std::vector<lasso_fr*>& polys, const ScVec& point = ScVec(), size_t local_rounds = 0, size_t num_rounds = 0, lasso_fr** d_eq = nullptr) {
     const size_t k = polys.size();
     std::vector<lasso_fr> mine(k), all(k * P), col(P);
     d.chk(lasso_read_heads(d.ctx, (const lasso_fr* const*)polys.data(), (uint32_t)k, mine.data()), "lasso_read_heads");
@@ -861,8 +848,37 @@ class Prover {
       d.chk(lasso_upload(d.ctx, tail_bufs.back().p, col.data(), P * sizeof(lasso_fr)), "lasso_upload");
       out.push_back(tail_bufs.back().p);
     }
+    if (!d_eq) return out;
+    tail_bufs.emplace_back(d, P); *d_eq = tail_bufs.back().p;
+    std::vector<lasso_fr> rr; for (size_t i = local_rounds; i < num_rounds; i++) rr.push_back(point[i].abi());
+    d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), *d_eq), "lasso_eq_evals");
     return out;
   }
+
+  // ---- what the eq-weighted sumcheck drivers (linear_rounds, cubic_rounds) share besides sumcheck_phase.hpp's plan
+  struct PhaseState {   // where a phase stands between two rounds; at most one launch is ever ahead of its challenge
+    bool in_tail = false;                        // the resident tail kernel is running: a round is lasso_sumcheck_cubic_tail_next
+    bool queued = false, queued_tail = false;   // this round's launch (a streaming round / the resident tail) is in the stream already and waits for the previous challenge
+    void round_enqueued() { queued = true; }      void round_posted() { queued = false; }
+    void tail_enqueued() { queued_tail = true; }  void tail_begun() { queued_tail = false; in_tail = true; }   // begun by its own launch, or the enqueued one was given its challenge
+    bool idle() const { return !queued && !queued_tail; }
+  };
+  Sc round_step(const UniPoly& up, SumcheckProof& proof, ScVec& r_out) {   // one round's Fiat-Shamir step (sumcheck.rs:106-113, :122): the round polynomial in, the challenge out
+    up.append_to_transcript(t, "poly");
+    Sc r_j = t.challenge_scalar("challenge_nextround"); r_out.push_back(r_j);
+    proof.compressed_polys.push_back(up.compress());
+    return r_j;
+  }
+  // a degenerate phase's round j: T_j = eq(point[v0+j+1 .. v0+rounds)) built explicitly into tj (len / 2^(j+1) entries), times the slab factor that is otherwise hidden in d_E[0]
+  const lasso_fr* degenerate_table(const EqPhase& ph, size_t j, bool reduce, const DBuf& tj) {
+    std::vector<lasso_fr> rr; for (size_t t2 = ph.v0 + j + 1; t2 < ph.v0 + ph.rounds; t2++) rr.push_back(ph.point[t2].abi());
+    lasso_fr sc = (reduce ? d.comm.eq_low(ph.point) : Sc::one()).abi();
+    d.chk(lasso_eq_evals_scaled(d.ctx, rr.data(), (uint32_t)rr.size(), &sc, tj.p), "lasso_eq_evals_scaled");
+    return tj.p;
+  }
+  // Rounds LAUNCHED AHEAD of their challenge: plain rounds only (no per-round table).  one_gpu: the caller's condition when no collective sits between the rounds.  With one (reduce,
+  // round 6) the ranks' partial sums meet on the host BEFORE the challenge exists, so posting it is the same step one exchange later: every rank keeps its own next round behind its own gate.
+  bool rounds_ahead_ok(const EqPhase& ph, bool reduce, bool one_gpu) { return sw::rounds_ahead() && !ph.degenerate && (reduce ? (sw::slab_ahead() && !d.ranks_share_a_device()) : one_gpu) && !d.no_ahead() && lasso_rounds_ahead_ok(d.ctx) == 1; }
 
   // ---- SumcheckInstanceProof::prove_arbitrary (sumcheck.rs:150-260); polys[0..alpha) = E clones, polys[alpha] = eq.
   // One phase = `rounds` rounds on arrays of current length len; `reduce` = the arrays are slabs, per-round sums are all-gathered and added.
@@ -879,13 +895,9 @@ class Prover {
       else d.chk(lasso_sumcheck_combine_round_lt_scaled(d.ctx, &S.abi, cp.data(), polys[alpha], len, (uint32_t)combined_degree, ev.data()), "lasso_sumcheck_combine_round_lt_scaled");
       if (reduce) d.comm.sum(ev);
       ScVec evals; for (auto& e : ev) evals.push_back(Sc::from_abi(e));
-      UniPoly up = UniPoly::from_evals(evals);
-      up.append_to_transcript(t, "poly");
-      Sc r_j = t.challenge_scalar("challenge_nextround"); r_out.push_back(r_j);
-      lasso_fr rj = r_j.abi();
+      lasso_fr rj = round_step(UniPoly::from_evals(evals), proof, r_out).abi();
       d.chk(lasso_bind_top(d.ctx, polys.data(), (uint32_t)polys.size(), len, &rj), "lasso_bind_top");
       len /= 2;
-      proof.compressed_polys.push_back(up.compress());
     }
   }
   // The same sumcheck for the LINEAR strategies in eq-weighted form (lasso_sumcheck_linear_eqw_round): the eq polynomial is never bound (prefix of
@@ -903,64 +915,38 @@ class Prover {
       src = nullptr;
     }
     const ScVec w = S.weights();
-    ScVec inv(rounds); bool degenerate = false;
-    {
-      Sc prod = Sc::one();
-      for (size_t j = 0; j < rounds; j++) { Sc om = Sc::one() - point[v0 + j]; if (om.is_zero()) degenerate = true; prod *= om; }
-      if (!degenerate) { Sc pi = prod.inverse(); for (size_t j = rounds; j-- > 0;) { inv[j] = pi; pi *= Sc::one() - point[v0 + j]; } }
-    }
-    DBuf tj; if (degenerate) tj = DBuf(d, len / 2);
+    const EqPhase ph(point, v0, rounds);
+    DBuf tj; if (ph.degenerate) tj = DBuf(d, len / 2);
     Sc r_prev = Sc::zero();
     // the last rounds (<= 256 indices per polynomial) in one resident kernel, as in cubic_rounds
-    static const bool tail_off = [] { const char* v = getenv("LASSO_LINEAR_TAIL"); return v && v[0] == '0'; }();
-    size_t tail_from = rounds;
-    if (tail_heads && !reduce && !degenerate && !tail_off) {
-      size_t j0 = 0, l = len;
-      while (j0 < rounds && (j0 == 0 ? l / 2 : l / 4) > tail_q()) { if (j0) l /= 2; j0++; }
-      if (j0 < rounds) tail_from = j0;
-    }
-    bool in_tail = false;
+    const size_t tail_from = lasso::tail_from(rounds, len, tail_q(), tail_heads && !reduce && !ph.degenerate && sw::linear_tail(), [](size_t) { return true; });
     // streaming rounds launched ahead of their challenge, as in cubic_rounds (in-place rounds only: from round 2 on)
-    static const bool ahead_env_off = [] { const char* v = getenv("LASSO_ROUNDS_AHEAD"); return v && v[0] == '0'; }();
-    static const bool slab_ahead_off = [] { const char* v = getenv("LASSO_SLAB_AHEAD"); return v && v[0] == '0'; }();
-    const bool ahead_ok = !ahead_env_off && !degenerate && (reduce ? (!slab_ahead_off && !d.ranks_share_a_device()) : P == 1) && !d.no_ahead() && lasso_rounds_ahead_ok(d.ctx) == 1;   // with a collective between the rounds too (cubic_rounds says why)
-    bool queued = false;
+    const bool ahead_ok = rounds_ahead_ok(ph, reduce, P == 1);
+    PhaseState st;
     auto enqueue_next = [&](size_t jn, size_t len_now) {   // round jn (>= 2) on arrays of len_now elements, behind the round in flight
       if (!ahead_ok || jn < 2 || jn >= rounds || jn >= tail_from) return;
-      d.chk(lasso_sumcheck_linear_eqw_round_fused_ahead(d.ctx, polys.data(), (uint32_t)alpha, d_E, len_now), "lasso_sumcheck_linear_eqw_round_fused_ahead"); queued = true;
+      d.chk(lasso_sumcheck_linear_eqw_round_fused_ahead(d.ctx, polys.data(), (uint32_t)alpha, d_E, len_now), "lasso_sumcheck_linear_eqw_round_fused_ahead"); st.round_enqueued();
     };
     for (size_t j = 0; j < rounds; j++) {
-      const lasso_fr* table = d_E; Sc scale = degenerate ? Sc::one() : inv[j];
-      if (degenerate) {
-        std::vector<lasso_fr> rr; for (size_t t2 = v0 + j + 1; t2 < v0 + rounds; t2++) rr.push_back(point[t2].abi());
-        lasso_fr sc = (reduce ? d.comm.eq_low(point) : Sc::one()).abi();
-        d.chk(lasso_eq_evals_scaled(d.ctx, rr.data(), (uint32_t)rr.size(), &sc, tj.p), "lasso_eq_evals_scaled");
-        table = tj.p;
-      }
-      std::vector<lasso_fr> ev(3 * alpha);
-      if (queued) {   // this round's kernel is in the stream already: its challenge, the next round behind it, then its sums
-        lasso_fr rp = r_prev.abi();
-        d.chk(lasso_challenge_post(d.ctx, &rp), "lasso_challenge_post"); queued = false;
+      const lasso_fr* table = ph.degenerate ? degenerate_table(ph, j, reduce, tj) : d_E;
+      std::vector<lasso_fr> ev(3 * alpha); size_t per = 3;   // sums per polynomial (the resident tail returns two)
+      lasso_fr rp = r_prev.abi();
+      if (st.queued) {   // this round's kernel is in the stream already: its challenge, the next round behind it, then its sums
+        d.chk(lasso_challenge_post(d.ctx, &rp), "lasso_challenge_post"); st.round_posted();
         len /= 2;
         enqueue_next(j + 1, len);
         d.chk(lasso_result_wait(d.ctx, ev.data(), 3 * alpha), "lasso_result_wait");
-      } else
-      if (j >= tail_from) {
-        lasso_fr rp = r_prev.abi();
-        if (!in_tail) {   // the data is still in src if no bind has moved it yet
-          const bool from_src = src && j <= 1;
-          d.chk(lasso_sumcheck_linear_tail_begin(d.ctx, from_src ? src->data() : (const lasso_fr* const*)polys.data(), (uint32_t)alpha, table, len, j == 0 ? nullptr : &rp), "lasso_sumcheck_linear_tail_begin");
-          in_tail = true;
+      } else if (j >= tail_from) {
+        if (!st.in_tail) {   // the data is still in src if no bind has moved it yet
+          d.chk(lasso_sumcheck_linear_tail_begin(d.ctx, src && j <= 1 ? src->data() : (const lasso_fr* const*)polys.data(), (uint32_t)alpha, table, len, j == 0 ? nullptr : &rp), "lasso_sumcheck_linear_tail_begin");
+          st.tail_begun();
         } else d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, &rp), "lasso_sumcheck_cubic_tail_next");
         if (j) len /= 2;
-        std::vector<lasso_fr> e2(2 * alpha);
-        d.chk(lasso_result_wait(d.ctx, e2.data(), 2 * alpha), "lasso_result_wait");
-        for (size_t k2 = 0; k2 < alpha; k2++) { ev[3 * k2] = e2[2 * k2]; ev[3 * k2 + 1] = e2[2 * k2 + 1]; }
+        per = 2; d.chk(lasso_result_wait(d.ctx, ev.data(), 2 * alpha), "lasso_result_wait");
       } else if (j == 0) {
         if (src && src_u32) d.chk(lasso_sumcheck_linear_eqw_round_u32(d.ctx, src_u32->data(), (uint32_t)alpha, table, len, ev.data()), "lasso_sumcheck_linear_eqw_round_u32");
         else d.chk(lasso_sumcheck_linear_eqw_round(d.ctx, src ? src->data() : (const lasso_fr* const*)polys.data(), (uint32_t)alpha, table, len, ev.data()), "lasso_sumcheck_linear_eqw_round");
       } else {
-        lasso_fr rp = r_prev.abi();
         if (j == 1 && src && src_u32) d.chk(lasso_sumcheck_linear_eqw_round_fused_from_u32(d.ctx, src_u32->data(), polys.data(), (uint32_t)alpha, table, len, &rp, ev.data()), "lasso_sumcheck_linear_eqw_round_fused_from_u32");
         else if (j == 1 && src) d.chk(lasso_sumcheck_linear_eqw_round_fused_from(d.ctx, src->data(), polys.data(), (uint32_t)alpha, table, len, &rp, ev.data()), "lasso_sumcheck_linear_eqw_round_fused_from");
         else d.chk(lasso_sumcheck_linear_eqw_round_fused(d.ctx, polys.data(), (uint32_t)alpha, table, len, &rp, ev.data()), "lasso_sumcheck_linear_eqw_round_fused");
@@ -969,18 +955,13 @@ class Prover {
       }
       if (reduce) d.comm.sum(ev);
       Sc G0 = Sc::zero(), G1 = Sc::zero();
-      for (size_t k2 = 0; k2 < alpha; k2++) { G0 += w[k2] * Sc::from_abi(ev[3 * k2]); G1 += w[k2] * Sc::from_abi(ev[3 * k2 + 1]); }
-      const Sc& rj = point[v0 + j]; const Sc base = s_run * scale, om = Sc::one() - rj;
-      ScVec evals{base * om * G0, base * rj * G1, base * (rj + rj - om) * (G1 + G1 - G0)};   // x = 0, 1, 2: eq1(r_j, x) * G(x)
-      UniPoly up = UniPoly::from_evals(evals);
-      up.append_to_transcript(t, "poly");
-      Sc r_j = t.challenge_scalar("challenge_nextround"); r_out.push_back(r_j);
-      r_prev = r_j;
-      s_run *= om * (Sc::one() - r_j) + rj * r_j;
-      proof.compressed_polys.push_back(up.compress());
+      for (size_t k2 = 0; k2 < alpha; k2++) { G0 += w[k2] * Sc::from_abi(ev[per * k2]); G1 += w[k2] * Sc::from_abi(ev[per * k2 + 1]); }
+      const Sc base = ph.base(j, s_run);
+      r_prev = round_step(UniPoly::from_evals({ph.f0(j, base) * G0, ph.f1(j, base) * G1, ph.f2(j, base) * (G1 + G1 - G0)}), proof, r_out);   // x = 0, 1, 2: eq1(r_j, x) * G(x)
+      ph.advance(s_run, j, r_prev);
     }
     lasso_fr rp = r_prev.abi();   // the last challenge of the phase (len == 2 here)
-    if (in_tail) {
+    if (st.in_tail) {
       d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, &rp), "lasso_sumcheck_cubic_tail_next");
       tail_heads->resize(alpha);
       d.chk(lasso_result_wait(d.ctx, tail_heads->data(), alpha), "lasso_result_wait");
@@ -1017,11 +998,8 @@ class Prover {
       const size_t local_rounds = num_rounds - lgP;
       if (src && local_rounds == 0) { for (size_t i = 0; i < alpha; i++) d.chk(lasso_copy(d.ctx, ep[i], (*src)[i], len_loc * sizeof(lasso_fr)), "lasso_copy"); }
       linear_rounds(local_rounds, len_loc, ep, polys[alpha], point, 0, true, s_run, proof, r_out, src);
-      std::vector<lasso_fr*> tail = gather_tail(ep);
-      tail_bufs.emplace_back(d, P);
-      std::vector<lasso_fr> rr; for (size_t i = local_rounds; i < num_rounds; i++) rr.push_back(point[i].abi());
-      d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), tail_bufs.back().p), "lasso_eq_evals");
-      linear_rounds(lgP, P, tail, tail_bufs.back().p, point, local_rounds, false, s_run, proof, r_out, nullptr, heads_out ? &th : nullptr);
+      lasso_fr* d_eq; std::vector<lasso_fr*> tail = slab_tail(ep, point, local_rounds, num_rounds, &d_eq);
+      linear_rounds(lgP, P, tail, d_eq, point, local_rounds, false, s_run, proof, r_out, nullptr, heads_out ? &th : nullptr);
       finish(tail);
       tail_bufs.clear();
       return proof;
@@ -1032,7 +1010,7 @@ class Prover {
     if (P == 1) { arbitrary_rounds(num_rounds, len_loc, polys, combined_degree, false, proof, r_out, src_u32); read_heads(polys); return proof; }
     LASSO_REQUIRE(num_rounds >= lgP && ((size_t)1 << (num_rounds - lgP)) == len_loc);
     arbitrary_rounds(num_rounds - lgP, len_loc, polys, combined_degree, true, proof, r_out);
-    std::vector<lasso_fr*> tail = gather_tail(polys);
+    std::vector<lasso_fr*> tail = slab_tail(polys);   // polys[alpha] IS the bound eq polynomial here: no table
     arbitrary_rounds(lgP, P, tail, combined_degree, false, proof, r_out);
     read_heads(tail);
     tail_bufs.clear();
@@ -1050,8 +1028,7 @@ class Prover {
     std::vector<lasso_fr*> work_a, work_b;                          // the arrays bound by the first challenge (n_loc / 8 elements each)
   };
   static constexpr size_t kLeafChunks = 8;
-  // below this many leaves per circuit the trees are small and kept whole (LASSO_LEAFLESS_MIN: tests drive the chunked rounds at toy sizes; at least 64 so that a chunk holds an index)
-  static size_t leafless_min() { return capacity_leafless_min(); }
+  // below sw::leafless_min() leaves per circuit the trees are small and kept whole (LASSO_LEAFLESS_MIN: tests drive the chunked rounds at toy sizes; at least 64 so that a chunk holds an index)
   // round j in {0, 1} of the bottom layer from recomputed leaves; len = length of A and B (n_loc / 2); ev receives the 2k sums (q(0), q_inf per circuit)
   void leaf_round(const LeafLayer& L, size_t j, size_t len, const lasso_fr* table, const lasso_fr* rp, std::vector<lasso_fr>& ev) {
     HostClock hc("capacity: chunked leaf rounds");
@@ -1098,22 +1075,10 @@ class Prover {
   // What runs is sumcheck.rs:49-124 literally on (A_c, B_c, C) with C = the bound eq polynomial s * EqPolynomial(rand[first..]).evals(): evaluations at 0, 2, 3 by
   // `prev + hi - lo`, e(1) from the claim (:99-104), UniPoly::from_evals, bind (:116-120) — the same field elements as the device's eq-weighted form, any eq coordinate.
   // The device remains the only place where an O(n) loop runs; this is the O(1) end of the O(log n) host share.
-  // budget = elements per array x circuits the host takes over (LASSO_HOST_TAIL, default 32; 0 switches the host rounds off: A/B measurements, byte-identical)
-  // default: 32 with the scalar loop; 128 where the rounds run eight elements at a time (field52.hpp, AVX-512 IFMA: a layer of 2 x 2 x 32 elements costs the host less than the two
-  // device turns it replaces — profiles/r05_ab_host_ifma.txt)
-  static bool host_ifma() {
-#ifdef LASSO_HOST_IFMA
-    return field52_ok();
-#else
-    return false;
-#endif
-  }
-  static size_t host_tail_budget() { static const size_t v = [] { const char* e = getenv("LASSO_HOST_TAIL"); const long x = e ? atol(e) : (host_ifma() ? 128 : 32); return (size_t)(x < 0 ? 0 : x > 1024 ? 1024 : x); }(); return v; }
-  size_t host_m_stop(size_t k) const {   // elements per array at which the host takes a layer over: a power of two, 1 = never
-    if (P != 1 || !host_tail_budget() || !k) return 1;
-    size_t m0 = 1; while (2 * m0 * k <= host_tail_budget() && 2 * m0 <= 64) m0 *= 2;
-    return m0;
-  }
+  // budget = elements per array x circuits the host takes over (LASSO_HOST_TAIL; 0 switches the host rounds off: A/B measurements, byte-identical).  128 where the rounds run eight elements
+  // at a time (field52.hpp, AVX-512 IFMA: a layer of 2 x 2 x 32 elements costs the host less than the two device turns it replaces — profiles/r05_ab_host_ifma.txt), 32 with the scalar loop
+  static size_t host_tail_budget() { return sw::host_tail(field52_ok()); }
+  size_t host_m_stop(size_t k) const { return P != 1 ? 1 : lasso::host_m_stop(k, host_tail_budget()); }   // elements per array at which the host takes a layer over (one GPU): a power of two, 1 = never
   // a, b: k arrays of m = 2^rounds_left elements; rand[first ..first + rounds_left) the eq coordinates still unbound; s = the running factor prod eq1(rand_t, rho_t) so far
   void host_cubic_rounds(std::vector<ScVec>& a, std::vector<ScVec>& b, size_t rounds_left, const ScVec& rand, size_t first, const ScVec& coeffs, const Sc& s_run, Sc& e, SumcheckProof& proof,
                          ScVec& r_out, std::vector<lasso_fr>& heads) {
@@ -1171,10 +1136,8 @@ class Prover {
       const H4 k2 = h4_sub(h4_mul(h4_add(h4_sub(e2, h4_add(e1, e1)), e0), inv2), h4_add(h4_add(k3, k3), k3));          // (e2 - 2 e1 + e0) / 2 - 3 c3
       const H4 k1 = h4_sub(h4_sub(h4_sub(e1, e0), k2), k3);
       UniPoly poly; poly.coeffs = {to_sc(e0), to_sc(k1), to_sc(k2), to_sc(k3)};
-      poly.append_to_transcript(t, "poly");
-      const Sc r_j = t.challenge_scalar("challenge_nextround"); r_out.push_back(r_j);
+      const Sc r_j = round_step(poly, proof, r_out);
       e = poly.evaluate(r_j);
-      proof.compressed_polys.push_back(poly.compress());
       const H4 rj = h4_from(r_j.v);
 #ifdef LASSO_HOST_IFMA
       if (vec) v52->bind(h, rj); else
@@ -1209,121 +1172,88 @@ class Prover {
     LayerAhead pre = std::move(layer_ahead); layer_ahead.on = false;                 // this layer's first launch, enqueued during the previous layer (or not)
     std::function<void()> hook = std::move(next_layer_hook); next_layer_hook = nullptr;   // the next layer's, to be enqueued once this layer's last launch is in the stream
     if (!rounds) { if (pre.on) d.chk(lasso_point_cancel(d.ctx), "lasso_point_cancel"); return; }
-    // 1 / prod_{t<=j}(1 - rand[v0+t]) for every round of the phase with one inversion; a zero factor (rand_t = 1) takes the explicit-table path
-    ScVec inv(rounds); bool degenerate = false;
-    {
-      Sc prod = Sc::one();
-      for (size_t j = 0; j < rounds; j++) { Sc om = Sc::one() - rand[v0 + j]; if (om.is_zero()) degenerate = true; prod *= om; }
-      if (!degenerate) { Sc pi = prod.inverse(); for (size_t j = rounds; j-- > 0;) { inv[j] = pi; pi *= Sc::one() - rand[v0 + j]; } }
-    }
-    DBuf tj; if (degenerate) tj = DBuf(d, len / 2);
+    const EqPhase ph(rand, v0, rounds);   // 1 / prod_{t<=j}(1 - rand[v0+t]) for every round of the phase; a zero factor (rand_t = 1) takes the explicit-table path
+    DBuf tj; if (ph.degenerate) tj = DBuf(d, len / 2);
     Sc r_prev = Sc::zero();
     // the layer's eq table may still be a specification (eq_half_lazy): it is built inside round 0's launch where that exists, by its own kernels otherwise
-    LazyEq lz; if (lazy_eq.on && lazy_eq.d_table == d_E && v0 == 0) { lz = lazy_eq; } lazy_eq.on = false;
-    auto ensure_table = [&] { if (lz.on) { d.chk(lasso_eq_evals_scaled(d.ctx, lz.rr.data(), (uint32_t)lz.rr.size(), &lz.scale, lz.d_table), "lasso_eq_evals_scaled"); lz.on = false; } };
-    if (degenerate) lz.on = false;   // the explicit per-round tables below replace it
+    LazyEq lz; if (lazy_eq.on && lazy_eq.d_table == d_E && v0 == 0 && !ph.degenerate) { lz = lazy_eq; } lazy_eq.on = false;   // (degenerate: the explicit per-round tables replace it)
     // The last rounds of the phase (<= 256 indices per circuit) are served by ONE resident kernel (lasso_sumcheck_cubic_tail_*): no launch per
     // round, the bound arrays stay on chip, and the final bind + heads come back from it.  Not when a collective sits between the rounds
     // (slab-local phase), nor when one of the remaining eq coordinates is 0 or 1 (the per-round paths handle those).
-    static const bool tail_off = [] { const char* v = getenv("LASSO_CUBIC_TAIL"); return v && v[0] == '0'; }();
-    size_t tail_from = rounds;   // first round served by the resident kernel
-    if (heads_out && !reduce && !degenerate && !tail_off) {
-      size_t j0 = 0; size_t l = len;   // l = array length before round j's bind
-      while (j0 < rounds && (j0 == 0 ? l / 2 : l / 4) > tail_q()) { if (j0) l /= 2; j0++; }   // the resident kernels' capacity
-      bool plain = j0 < rounds;
-      for (size_t j = j0; j < rounds && plain; j++) if (rand[v0 + j].is_zero()) plain = false;
-      if (plain) tail_from = j0;
-    }
-    bool in_tail = false;
+    const size_t tail_from = lasso::tail_from(rounds, len, tail_q(), heads_out && !reduce && !ph.degenerate && sw::cubic_tail(), [&](size_t j0) { return ph.no_zero_from(j0); });
     // the host takes the layer over when its arrays are down to m_stop elements each: the resident tail runs the rounds [tail_from, j_host) and hands the arrays over
-    size_t m_stop = 1, j_host = rounds;
-    if (tail_from < rounds && len == ((size_t)1 << rounds)) {
-      const size_t m0 = host_m_stop(k), lt = len >> tail_from;   // lt = array length at the tail's first round
-      if (m0 >= 2 && m0 < lt) { m_stop = m0; j_host = rounds - ceil_log2(m0); }
-    }
-    // Rounds LAUNCHED AHEAD of their challenge (include/lasso_hip.h lasso_sumcheck_cubic_eqw2_begin_ahead): while round j runs, round j + 1 — a streaming round, or the resident
-    // tail — is already in the stream and waits on the device for the challenge this loop posts.  One GPU, plain rounds only (no collective between rounds, no per-round table).
+    const HostHandover ho = host_handover(rounds, len, tail_from, host_m_stop(k));
     // the launch enqueued during the previous layer is this layer's first launch only if the layer has the shape that was assumed then
     bool use_pre = false;
     if (pre.on) {
-      static const bool three = [] { const char* v = getenv("LASSO_CUBIC_THREE_SUMS"); return v && v[0] == '1'; }();
-      use_pre = lz.on && !degenerate && !leaf && v0 == 0 && heads_out && !reduce && pre.len == len && pre.A == A && pre.B == B && pre.d_table == lz.d_table && pre.ell == lz.rr.size() &&
-                (pre.tail ? (tail_from == 0 && m_stop == pre.m_stop) : (tail_from > 0 && !three && !rand[0].is_zero() && !s_run.is_zero()));
+      use_pre = lz.on && !ph.degenerate && !leaf && v0 == 0 && heads_out && !reduce && pre.len == len && pre.A == A && pre.B == B && pre.d_table == lz.d_table && pre.ell == lz.rr.size() &&
+                (pre.tail ? (tail_from == 0 && ho.m_stop == pre.m_stop) : (tail_from > 0 && !sw::cubic_three_sums() && !rand[0].is_zero() && !s_run.is_zero()));
       if (!use_pre) d.chk(lasso_point_cancel(d.ctx), "lasso_point_cancel");
     }
-    static const bool ahead_env_off = [] { const char* v = getenv("LASSO_ROUNDS_AHEAD"); return v && v[0] == '0'; }();
-    // Slab mode (reduce, round 6): the ranks' partial sums meet on the host (d.comm.sum below) BEFORE the challenge exists, so posting it is the same step one exchange later —
-    // every rank keeps its own next round in its own stream behind its own gate.  (The resident tail is not used with a collective between the rounds: tail_from == rounds.)
-    static const bool slab_ahead_off = [] { const char* v = getenv("LASSO_SLAB_AHEAD"); return v && v[0] == '0'; }();   // A/B switch: round 5's schedule for P > 1
-    const bool ahead_ok = !ahead_env_off && !degenerate && (reduce ? (!slab_ahead_off && !d.ranks_share_a_device()) : (P == 1 && heads_out != nullptr)) && !d.no_ahead() && lasso_rounds_ahead_ok(d.ctx) == 1;
-    bool queued = false, queued_tail = false;   // this round's kernel is already enqueued (a streaming round / the resident tail) and waits for r_prev
+    // Rounds LAUNCHED AHEAD of their challenge (include/lasso_hip.h lasso_sumcheck_cubic_eqw2_begin_ahead): while round j runs, round j + 1 — a streaming round, or the resident
+    // tail — is already in the stream and waits on the device for the challenge this loop posts.  (The resident tail is not used with a collective between the rounds.)
+    const bool ahead_ok = rounds_ahead_ok(ph, reduce, P == 1 && heads_out != nullptr);
+    PhaseState st;
     std::vector<DBuf> leaf_full;   // the leaves after all, for the rare shapes the chunked rounds do not cover
     if (leaf) {
-      static const bool three = [] { const char* v = getenv("LASSO_CUBIC_THREE_SUMS"); return v && v[0] == '1'; }();
-      const bool plain = v0 == 0 && !degenerate && !three && rounds >= 3 && tail_from >= 2 && !rand[0].is_zero() && !rand[1].is_zero() && !s_run.is_zero();
+      const bool plain = v0 == 0 && !ph.degenerate && !sw::cubic_three_sums() && rounds >= 3 && tail_from >= 2 && !rand[0].is_zero() && !rand[1].is_zero() && !s_run.is_zero();
       if (!plain) { leaf_full = leaf_materialise(*leaf, A, B); leaf = nullptr; }
     }
-    hpro.reset();
-    for (size_t j = 0; j < j_host; j++) {
-      const lasso_fr* table = d_E; Sc scale = degenerate ? Sc::one() : inv[j];
-      if (degenerate) {   // T_j = eq(rand[v0+j+1 .. v0+rounds)) built explicitly (size len / 2^(j+1) at this point), times the slab factor hidden in d_E[0] / eq-prefix
-        std::vector<lasso_fr> rr; for (size_t t2 = v0 + j + 1; t2 < v0 + rounds; t2++) rr.push_back(rand[t2].abi());
-        lasso_fr sc = (reduce ? d.comm.eq_low(rand) : Sc::one()).abi();
-        d.chk(lasso_eq_evals_scaled(d.ctx, rr.data(), (uint32_t)rr.size(), &sc, tj.p), "lasso_eq_evals_scaled");
-        table = tj.p;
+    // "Begin the resident tail": the hand-over request, the launch in one of its forms, the state, and — this layer's last launch being in the stream — the next layer's first.
+    enum class Tail { posted, with_eq, plain, ahead };   // posted: launched during the previous layer (enqueue_next_layer made the request), it has just been given its point
+    auto begin_tail = [&](Tail form, const lasso_fr* table, const lasso_fr* rp) {
+      if (form != Tail::posted && ho.m_stop > 1) d.chk(lasso_tail_handover_next(d.ctx, (uint32_t)ho.m_stop), "lasso_tail_handover_next");
+      if (form == Tail::with_eq) { d.chk(lasso_sumcheck_cubic_tail_begin_eq(d.ctx, A.data(), B.data(), (uint32_t)k, len, lz.rr.data(), (uint32_t)lz.rr.size(), &lz.scale), "lasso_sumcheck_cubic_tail_begin_eq"); lz.on = false; }
+      if (form == Tail::plain) d.chk(lasso_sumcheck_cubic_tail_begin(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, rp), "lasso_sumcheck_cubic_tail_begin");
+      if (form == Tail::ahead) d.chk(lasso_sumcheck_cubic_tail_begin_ahead(d.ctx, A.data(), B.data(), (uint32_t)k, table, len), "lasso_sumcheck_cubic_tail_begin_ahead");
+      if (form == Tail::ahead) st.tail_enqueued(); else st.tail_begun();
+      if (hook) { hook(); hook = nullptr; }
+    };
+    // The form of a two-sum round j, first match: its launch is in the stream already (posted challenge / queued tail / the layer pre-enqueued during the previous one), a leaf
+    // chunk round, round 0 with the eq table built in its launch (streaming / the whole layer in the tail), plain streaming, tail begin, tail next.  True: ev holds the sums already.
+    auto launch = [&](size_t j, const lasso_fr* table, const lasso_fr* rp, std::vector<lasso_fr>& ev) {
+      const uint32_t ell = (uint32_t)lz.rr.size();   // table of 2^ell = len / 2 entries
+      const lasso_fr* rp0 = j == 0 ? nullptr : rp;
+      if (st.queued) { d.chk(lasso_challenge_post(d.ctx, rp), "lasso_challenge_post"); st.round_posted(); }
+      else if (st.queued_tail) { d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, rp), "lasso_sumcheck_cubic_tail_next"); st.tail_begun(); }
+      else if (j == 0 && use_pre) {
+        { HostClock hp("layer transition: point post"); d.chk(lasso_point_post(d.ctx, lz.rr.data(), ell, &lz.scale), "lasso_point_post"); } lz.on = false;
+        if (pre.tail) begin_tail(Tail::posted, nullptr, nullptr);
+      } else if (leaf && j < 2) {   // capacity mode: this round's A and B are recomputed chunk by chunk; after round 1 the bound arrays are the working arrays
+        eq_build(lz);
+        leaf_round(*leaf, j, len, table, rp0, ev);
+        if (j == 1) { A = leaf->work_a; B = leaf->work_b; }
+        return true;
+      } else if (j == 0 && lz.on && j < tail_from && ell <= 32 && len / 2 > 64) {   // the table is built in this launch and left in d_E for the later rounds
+        d.chk(lasso_sumcheck_cubic_eqw2_begin_eq(d.ctx, A.data(), B.data(), (uint32_t)k, lz.d_table, len, lz.rr.data(), ell, &lz.scale), "lasso_sumcheck_cubic_eqw2_begin_eq"); lz.on = false;
+      } else if (j == 0 && lz.on && j >= tail_from && ell <= 9) begin_tail(Tail::with_eq, nullptr, nullptr);
+      else {
+        eq_build(lz);
+        if (j < tail_from) d.chk(lasso_sumcheck_cubic_eqw2_begin(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, rp0), "lasso_sumcheck_cubic_eqw2_begin");
+        else if (!st.in_tail) begin_tail(Tail::plain, table, rp0);
+        else d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, rp), "lasso_sumcheck_cubic_tail_next");
       }
-      // e(x) = f(x) * q(x) with f(x) = s * scale * eq1(rand_j, x), eq1(r, x) = (1 - r)(1 - x) + r x, and q(x) = sum_c coeffs_c q_c(x) quadratic
-      const Sc& rj = rand[v0 + j]; const Sc base = s_run * scale, om = Sc::one() - rj;
-      const Sc f0 = base * om, f1 = base * rj;   // f is linear: f(x) = f0 + (f1 - f0) x
+      return false;
+    };
+    hpro.reset();
+    for (size_t j = 0; j < ho.j_host; j++) {
+      const lasso_fr* table = ph.degenerate ? degenerate_table(ph, j, reduce, tj) : d_E;
+      // e(x) = f(x) * q(x) with f(x) = s * scale * eq1(rand_j, x), linear: f(x) = f0 + (f1 - f0) x, and q(x) = sum_c coeffs_c q_c(x) quadratic
+      const Sc base = ph.base(j, s_run), f0 = ph.f0(j, base), f1 = ph.f1(j, base);
+      const lasso_fr rp = r_prev.abi();
       UniPoly poly;
-      static const bool three_sums = [] { const char* v = getenv("LASSO_CUBIC_THREE_SUMS"); return v && v[0] == '1'; }();   // A/B switch for measurements
-      if (j >= tail_from || queued || (!f1.is_zero() && !three_sums)) {
+      if (j >= tail_from || st.queued || (!f1.is_zero() && !sw::cubic_three_sums())) {
         // two sums per circuit, q_c(0) and the leading coefficient; q(1) follows from the claim e = e(0) + e(1) (sumcheck.rs:99-104 derives e(1)
         // the same way) and q(2), q(3) by extrapolation.  The inversion of f(1) overlaps the kernel.
-        lasso_fr rp = r_prev.abi();
-        const uint32_t ell = (uint32_t)lz.rr.size();   // table of 2^ell = len / 2 entries
-        std::vector<lasso_fr> ev(2 * k); bool have_ev = false;
-        if (queued) {          // enqueued while the previous round ran: it only needs its challenge
-          d.chk(lasso_challenge_post(d.ctx, &rp), "lasso_challenge_post"); queued = false;
-        } else if (queued_tail) {
-          d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, &rp), "lasso_sumcheck_cubic_tail_next"); queued_tail = false; in_tail = true;
-        } else
-        if (j == 0 && use_pre) {   // enqueued during the previous layer, waiting on the device for this point
-          { HostClock hp("layer transition: point post"); d.chk(lasso_point_post(d.ctx, lz.rr.data(), ell, &lz.scale), "lasso_point_post"); } lz.on = false;
-          if (pre.tail) { in_tail = true; if (hook) { hook(); hook = nullptr; } }
-        } else
-        if (leaf && j < 2) {   // capacity mode: this round's A and B are recomputed chunk by chunk; after round 1 the bound arrays are the working arrays
-          ensure_table();
-          leaf_round(*leaf, j, len, table, j ? &rp : nullptr, ev); have_ev = true;
-          if (j == 1) { A = leaf->work_a; B = leaf->work_b; }
-        } else
-        if (j == 0 && lz.on && j < tail_from && ell <= 32 && len / 2 > 64) {   // round 0 of a streaming layer: the table is built in this launch and left in d_E for the later rounds
-          d.chk(lasso_sumcheck_cubic_eqw2_begin_eq(d.ctx, A.data(), B.data(), (uint32_t)k, lz.d_table, len, lz.rr.data(), ell, &lz.scale), "lasso_sumcheck_cubic_eqw2_begin_eq"); lz.on = false;
-        } else if (j == 0 && lz.on && j >= tail_from && ell <= 9) {            // the whole layer runs in the resident kernel: no table at all
-          if (m_stop > 1) d.chk(lasso_tail_handover_next(d.ctx, (uint32_t)m_stop), "lasso_tail_handover_next");
-          d.chk(lasso_sumcheck_cubic_tail_begin_eq(d.ctx, A.data(), B.data(), (uint32_t)k, len, lz.rr.data(), ell, &lz.scale), "lasso_sumcheck_cubic_tail_begin_eq"); in_tail = true; lz.on = false;
-          if (hook) { hook(); hook = nullptr; }   // this layer's last launch is in the stream: the next layer's first goes in behind it
-        } else {
-          ensure_table();
-          if (j < tail_from) d.chk(lasso_sumcheck_cubic_eqw2_begin(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, j == 0 ? nullptr : &rp), "lasso_sumcheck_cubic_eqw2_begin");
-          else if (!in_tail) {
-            if (m_stop > 1) d.chk(lasso_tail_handover_next(d.ctx, (uint32_t)m_stop), "lasso_tail_handover_next");
-            d.chk(lasso_sumcheck_cubic_tail_begin(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, j == 0 ? nullptr : &rp), "lasso_sumcheck_cubic_tail_begin"); in_tail = true;
-            if (hook) { hook(); hook = nullptr; }
-          }
-          else d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, &rp), "lasso_sumcheck_cubic_tail_next");
-        }
+        std::vector<lasso_fr> ev(2 * k);
+        const bool have_ev = launch(j, table, &rp, ev);
         if (j) len /= 2;
         // round j + 1 into the stream behind round j, before round j's sums are waited for: a streaming round (bind of the challenge to come + its sums), or the resident tail
-        if (ahead_ok && !in_tail && !lz.on && j + 1 < j_host && !(leaf && j + 1 < 3) && !rand[v0 + j + 1].is_zero()) {
+        if (ahead_ok && !st.in_tail && !lz.on && j + 1 < ho.j_host && !(leaf && j + 1 < 3) && !rand[v0 + j + 1].is_zero()) {
           if (j + 1 < tail_from) {
             const int32_t rc = lasso_sumcheck_cubic_eqw2_begin_ahead(d.ctx, A.data(), B.data(), (uint32_t)k, table, len);
-            if (rc == 0) queued = true; else if (rc != LASSO_ERR_UNSUPPORTED) d.chk(rc, "lasso_sumcheck_cubic_eqw2_begin_ahead");
-          } else if (j + 1 == tail_from) {
-            if (m_stop > 1) d.chk(lasso_tail_handover_next(d.ctx, (uint32_t)m_stop), "lasso_tail_handover_next");
-            d.chk(lasso_sumcheck_cubic_tail_begin_ahead(d.ctx, A.data(), B.data(), (uint32_t)k, table, len), "lasso_sumcheck_cubic_tail_begin_ahead"); queued_tail = true;
-            if (hook) { hook(); hook = nullptr; }
-          }
+            if (rc == 0) st.round_enqueued(); else if (rc != LASSO_ERR_UNSUPPORTED) d.chk(rc, "lasso_sumcheck_cubic_eqw2_begin_ahead");
+          } else if (j + 1 == tail_from) begin_tail(Tail::ahead, table, nullptr);
         }
         // f(1) = 0 inside the tail can only come from a vanished running factor s (probability 2^-252): then f = 0 identically and q is irrelevant
         const Sc f1_inv = f1.is_zero() ? Sc::zero() : f1.inverse();
@@ -1339,42 +1269,33 @@ class Prover {
         poly.coeffs = {c0, f0 * ql + df * q0, f0 * qi + df * ql, df * qi};
       } else {   // rand_j = 0 (or a zero running factor): the claim says nothing about q(1); three sums from the device
         std::vector<lasso_fr> ev(3 * k);
-        ensure_table();
-        if (j == 0) {
-          d.chk(lasso_sumcheck_cubic_eqw_round(d.ctx, (const lasso_fr* const*)A.data(), (const lasso_fr* const*)B.data(), (uint32_t)k, table, len, ev.data()), "lasso_sumcheck_cubic_eqw_round");
-        } else {
-          lasso_fr rp = r_prev.abi();
-          d.chk(lasso_sumcheck_cubic_eqw_round_fused(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, &rp, ev.data()), "lasso_sumcheck_cubic_eqw_round_fused");
-          len /= 2;
-        }
+        eq_build(lz);
+        if (j == 0) d.chk(lasso_sumcheck_cubic_eqw_round(d.ctx, (const lasso_fr* const*)A.data(), (const lasso_fr* const*)B.data(), (uint32_t)k, table, len, ev.data()), "lasso_sumcheck_cubic_eqw_round");
+        else { d.chk(lasso_sumcheck_cubic_eqw_round_fused(d.ctx, A.data(), B.data(), (uint32_t)k, table, len, &rp, ev.data()), "lasso_sumcheck_cubic_eqw_round_fused"); len /= 2; }
         if (reduce) d.comm.sum(ev);
-        const Sc f2 = base * (rj + rj - om), f3 = base * (rj + rj + rj - om - om);
         Sc c0 = Sc::zero(), c2 = Sc::zero(), c3 = Sc::zero();
         for (size_t i = 0; i < k; i++) { c0 += Sc::from_abi(ev[3 * i]) * coeffs[i]; c2 += Sc::from_abi(ev[3 * i + 1]) * coeffs[i]; c3 += Sc::from_abi(ev[3 * i + 2]) * coeffs[i]; }
-        c0 *= f0; c2 *= f2; c3 *= f3;
+        c0 *= f0; c2 *= ph.f2(j, base); c3 *= ph.f3(j, base);
         poly = UniPoly::from_evals({c0, e - c0, c2, c3});
       }
       HostClock hc2("cubic round host work");
-      poly.append_to_transcript(t, "poly");
-      Sc r_j = t.challenge_scalar("challenge_nextround"); r_out.push_back(r_j);
-      r_prev = r_j;
-      e = poly.evaluate(r_j);
-      s_run *= om * (Sc::one() - r_j) + rj * r_j;   // eq1(rand_j, rho_j)
-      proof.compressed_polys.push_back(poly.compress());
+      r_prev = round_step(poly, proof, r_out);
+      e = poly.evaluate(r_prev);
+      ph.advance(s_run, j, r_prev);   // eq1(rand_j, rho_j)
     }
     lasso_fr rp = r_prev.abi();
-    if (in_tail) {   // the resident kernel binds the last challenge itself and hands back the heads A_c[0], B_c[0] — or, stopped early, the arrays of m_stop elements
+    if (st.in_tail) {   // the resident kernel binds the last challenge itself and hands back the heads A_c[0], B_c[0] — or, stopped early, the arrays of ho.m_stop elements
       d.chk(lasso_sumcheck_cubic_tail_next(d.ctx, &rp), "lasso_sumcheck_cubic_tail_next");
-      heads_out->resize(2 * k * m_stop);
-      d.chk(lasso_result_wait(d.ctx, heads_out->data(), 2 * k * m_stop), "lasso_result_wait");
-      if (m_stop > 1) {   // the host finishes the layer: rounds [j_host, rounds) on the handed-over arrays
-        std::vector<ScVec> ha(k, ScVec(m_stop)), hb(k, ScVec(m_stop));
-        for (size_t c = 0; c < k; c++) for (size_t i = 0; i < m_stop; i++) { ha[c][i] = Sc::from_abi((*heads_out)[c * m_stop + i]); hb[c][i] = Sc::from_abi((*heads_out)[(k + c) * m_stop + i]); }
-        host_cubic_rounds(ha, hb, rounds - j_host, rand, v0 + j_host, coeffs, s_run, e, proof, r_out, *heads_out);
+      heads_out->resize(2 * k * ho.m_stop);
+      d.chk(lasso_result_wait(d.ctx, heads_out->data(), 2 * k * ho.m_stop), "lasso_result_wait");
+      if (ho.m_stop > 1) {   // the host finishes the layer: rounds [ho.j_host, rounds) on the handed-over arrays
+        std::vector<ScVec> ha(k, ScVec(ho.m_stop)), hb(k, ScVec(ho.m_stop));
+        for (size_t c = 0; c < k; c++) for (size_t i = 0; i < ho.m_stop; i++) { ha[c][i] = Sc::from_abi((*heads_out)[c * ho.m_stop + i]); hb[c][i] = Sc::from_abi((*heads_out)[(k + c) * ho.m_stop + i]); }
+        host_cubic_rounds(ha, hb, rounds - ho.j_host, rand, v0 + ho.j_host, coeffs, s_run, e, proof, r_out, *heads_out);
       }
       return;
     }
-    LASSO_REQUIRE(j_host == rounds && !queued && !queued_tail);
+    LASSO_REQUIRE(ho.j_host == rounds && st.idle());
     // the last challenge of the phase still has to be bound (len == 2 here)
     std::vector<lasso_fr*> ab(A); ab.insert(ab.end(), B.begin(), B.end());
     d.chk(lasso_bind_top(d.ctx, ab.data(), (uint32_t)ab.size(), len, &rp), "lasso_bind_top");
@@ -1393,28 +1314,21 @@ class Prover {
       const size_t local_rounds = num_rounds - lgP;
       cubic_rounds(local_rounds, (size_t)1 << local_rounds, fa, fb, d_E, rand, 0, coeffs, true, s_run, e, proof, r_out, nullptr, leaf);
       std::vector<lasso_fr*> local_heads(fa); local_heads.insert(local_heads.end(), fb.begin(), fb.end());
-      static const bool slab_host_tail_off = [] { const char* v = getenv("LASSO_SLAB_HOST_TAIL"); return v && v[0] == '0'; }();   // A/B switch: round 5's device phase
-      if (!slab_host_tail_off) {
+      if (sw::slab_host_tail()) {   // (off: round 5's device phase below)
         // Round 6: the remaining log2 P variables live in P-element arrays that every rank holds whole after one all-gather of the local heads — 2 k P field elements.  Round 5
         // uploaded them (2k hipMemcpy), built a P-entry eq table and ran a resident kernel for log2 P rounds: ~100 us of launches and hand-offs per layer for a few dozen field
         // products.  They are the host's: host_cubic_rounds is sumcheck.rs:49-124 literally on (A_c, B_c, eq), every rank computes the same bytes, nothing touches the device.
         std::vector<lasso_fr> mine(2 * k), all(2 * k * P);
         d.chk(lasso_read_heads(d.ctx, (const lasso_fr* const*)local_heads.data(), (uint32_t)(2 * k), mine.data()), "lasso_read_heads");
         d.comm.allgather(mine.data(), all.data(), 2 * k * sizeof(lasso_fr));
-        std::vector<ScVec> ha(k, ScVec(P)), hb(k, ScVec(P));   // element g = rank g's head: the rank index IS the remaining low variables (gather_tail's layout)
+        std::vector<ScVec> ha(k, ScVec(P)), hb(k, ScVec(P));   // element g = rank g's head: the rank index IS the remaining low variables (slab_tail's layout)
         for (size_t g = 0; g < P; g++) for (size_t c = 0; c < k; c++) { ha[c][g] = Sc::from_abi(all[g * 2 * k + c]); hb[c][g] = Sc::from_abi(all[g * 2 * k + k + c]); }
         host_cubic_rounds(ha, hb, lgP, rand, local_rounds, coeffs, s_run, e, proof, r_out, heads);
-        claims_a.clear(); claims_b.clear();
-        for (size_t i = 0; i < k; i++) { claims_a.push_back(Sc::from_abi(heads[i])); claims_b.push_back(Sc::from_abi(heads[k + i])); }
-        return proof;
+      } else {   // the remaining log2 P variables: replicated P-element arrays and the (whole) eq table over rand[local_rounds..]
+        lasso_fr* d_eq; const std::vector<lasso_fr*> tail = slab_tail(local_heads, rand, local_rounds, num_rounds, &d_eq);
+        fa.assign(tail.begin(), tail.begin() + k); fb.assign(tail.begin() + k, tail.begin() + 2 * k);
+        cubic_rounds(lgP, P, fa, fb, d_eq, rand, local_rounds, coeffs, false, s_run, e, proof, r_out, &heads);
       }
-      std::vector<lasso_fr*> tail = gather_tail(local_heads);
-      fa.assign(tail.begin(), tail.begin() + k); fb.assign(tail.begin() + k, tail.begin() + 2 * k);
-      // the remaining log2 P variables: replicated P-element arrays and the (whole) eq table over rand[local_rounds..]
-      tail_bufs.emplace_back(d, P);
-      std::vector<lasso_fr> rr; for (size_t i = local_rounds; i < num_rounds; i++) rr.push_back(rand[i].abi());
-      d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), tail_bufs.back().p), "lasso_eq_evals");
-      cubic_rounds(lgP, P, fa, fb, tail_bufs.back().p, rand, local_rounds, coeffs, false, s_run, e, proof, r_out, &heads);
     }
     if (heads.empty()) {
       std::vector<lasso_fr*> ab(fa); ab.insert(ab.end(), fb.begin(), fb.end());
@@ -1435,11 +1349,20 @@ class Prover {
   // host_tops (one GPU, optional): the top of every tree on the host — tree c's layers of at most host_tops->len elements, back to back as they lie in the arena (the layer of
   // `len` elements first, the two-element layer last): those layers are proved without the device (host_cubic_rounds)
   struct HostTops { size_t len = 0; std::vector<ScVec> run; };   // run[c]: 2 * len - 2 elements
-  // layer `layer_id` of whole trees on one GPU (P == 1, no capacity mode): the arrays bgpa_prove will pass to its sumcheck, enqueued ahead
-  void enqueue_next_layer(const std::vector<lasso_fr*>& trees, size_t n, size_t layer_id, lasso_fr* d_table) {
-    const size_t len = n >> layer_id, off = 2 * n - 2 * len;
-    std::vector<lasso_fr*> A, B; for (auto* tr : trees) { A.push_back(tr + off); B.push_back(tr + off + len / 2); }
-    enqueue_layer_ahead(A, B, len / 2, d_table);   // A = the layer's first half, B its second: arrays of len / 2
+  Sc open_layer(const ScVec& claims_to_verify, ScVec& coeff_vec) {   // a layer's opening (grand_product.rs:113-120): the batching coefficients and the batched claim
+    coeff_vec = t.challenge_vector("rand_coeffs_next_layer", claims_to_verify.size());
+    Sc claim = Sc::zero(); for (size_t i = 0; i < claims_to_verify.size(); i++) claim += claims_to_verify[i] * coeff_vec[i];
+    return claim;
+  }
+  // ... and its closing (:160-190): the claims go into the transcript, r_layer folds them into the next layer's claims and extends the point
+  void close_layer(LayerProofBatched& lp, const ScVec& rand_prod, ScVec& claims_to_verify, ScVec& rand, BatchedGrandProductArgument& out) {
+    const size_t k = lp.claims_prod_left.size();
+    for (size_t i = 0; i < k; i++) { t.append_scalar("claim_prod_left", lp.claims_prod_left[i]); t.append_scalar("claim_prod_right", lp.claims_prod_right[i]); }
+    Sc r_layer = t.challenge_scalar("challenge_r_layer");
+    claims_to_verify.clear();
+    for (size_t i = 0; i < k; i++) claims_to_verify.push_back(lp.claims_prod_left[i] + r_layer * (lp.claims_prod_right[i] - lp.claims_prod_left[i]));
+    rand.assign(1, r_layer); rand.insert(rand.end(), rand_prod.begin(), rand_prod.end());
+    out.proof.push_back(std::move(lp));
   }
   BatchedGrandProductArgument bgpa_prove(std::vector<lasso_fr*>& trees, std::vector<lasso_fr*>& tops, size_t n, const ScVec& roots, ScVec& rand_out, LeafLayer* leaf = nullptr, const HostTops* host_tops = nullptr) {
     Trace tr("BatchedGrandProductArgument.prove", d.ctx);
@@ -1456,17 +1379,11 @@ class Prover {
         std::vector<ScVec> ha(k), hb(k);
         for (size_t c = 0; c < k; c++) { const ScVec& r = host_tops->run[c]; ha[c].assign(r.begin() + off, r.begin() + off + len / 2); hb[c].assign(r.begin() + off + len / 2, r.begin() + off + len); }
         if (P == 1 && layer_id > 0 && 2 * len > host_tops->len && !leaf) enqueue_next_layer(trees, n, layer_id - 1, eq.p);   // the first layer the device proves: its first launch waits for its point from here on
-        ScVec coeff_vec = t.challenge_vector("rand_coeffs_next_layer", claims_to_verify.size());
-        Sc claim = Sc::zero(); for (size_t i = 0; i < claims_to_verify.size(); i++) claim += claims_to_verify[i] * coeff_vec[i];
+        ScVec coeff_vec; Sc claim = open_layer(claims_to_verify, coeff_vec);
         LayerProofBatched lp; ScVec rand_prod; std::vector<lasso_fr> heads;
         host_cubic_rounds(ha, hb, num_rounds_prod, rand, 0, coeff_vec, Sc::one(), claim, lp.proof, rand_prod, heads);
         for (size_t i = 0; i < k; i++) { lp.claims_prod_left.push_back(Sc::from_abi(heads[i])); lp.claims_prod_right.push_back(Sc::from_abi(heads[k + i])); }
-        for (size_t i = 0; i < k; i++) { t.append_scalar("claim_prod_left", lp.claims_prod_left[i]); t.append_scalar("claim_prod_right", lp.claims_prod_right[i]); }
-        Sc r_layer = t.challenge_scalar("challenge_r_layer");
-        claims_to_verify.clear();
-        for (size_t i = 0; i < k; i++) claims_to_verify.push_back(lp.claims_prod_left[i] + r_layer * (lp.claims_prod_right[i] - lp.claims_prod_left[i]));
-        ScVec ext{r_layer}; ext.insert(ext.end(), rand_prod.begin(), rand_prod.end()); rand = ext;
-        out.proof.push_back(std::move(lp));
+        close_layer(lp, rand_prod, claims_to_verify, rand, out);
         continue;
       }
       const bool slab = P > 1 && len >= 2 * P;              // this layer lives in the local trees; smaller ones in the replicated tops
@@ -1477,19 +1394,18 @@ class Prover {
         // layer 1's storage (n_loc / 2 elements, at the start of the leafless arena) is dead: layer 1's sumcheck is over.  It receives the bound arrays A', B' (n_loc / 4 each).
         leaf->work_a.clear(); leaf->work_b.clear();
         for (auto* tr : trees) { leaf->work_a.push_back(tr); leaf->work_b.push_back(tr + n_loc / 4); }
-        if (eq_inline_off()) eq_half_local(rand, eq.p); else eq_half_lazy(rand, eq.p);
+        if (!sw::eq_inline()) eq_half_local(rand, eq.p); else eq_half_lazy(rand, eq.p);
       } else if (slab || P == 1) {
         const size_t len_l = len / P, off = 2 * n_loc - 2 * len_l - (leaf ? n_loc : 0);
         for (auto* tr : trees) { A.push_back(tr + off); B.push_back(tr + off + len_l / 2); }
-        if (eq_inline_off()) eq_half_local(rand, eq.p); else eq_half_lazy(rand, eq.p);        // poly_C_par :122 (the half the rounds read), built inside round 0's launch where possible
+        if (!sw::eq_inline()) eq_half_local(rand, eq.p); else eq_half_lazy(rand, eq.p);        // poly_C_par :122 (the half the rounds read), built inside round 0's launch where possible
       } else {
         const size_t off = 2 * P - 2 * len;
         for (auto* tp : tops) { A.push_back(tp + off); B.push_back(tp + off + len / 2); }
         std::vector<lasso_fr> rr; for (auto& x : rand) rr.push_back(x.abi());
         d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), eq.p), "lasso_eq_evals");
       }
-      ScVec coeff_vec = t.challenge_vector("rand_coeffs_next_layer", claims_to_verify.size());
-      Sc claim = Sc::zero(); for (size_t i = 0; i < claims_to_verify.size(); i++) claim += claims_to_verify[i] * coeff_vec[i];
+      ScVec coeff_vec; const Sc claim = open_layer(claims_to_verify, coeff_vec);
       LayerProofBatched lp; ScVec rand_prod;
       hco.reset();
       next_layer_hook = nullptr;
@@ -1497,12 +1413,7 @@ class Prover {
       lp.proof = prove_cubic_batched(claim, num_rounds_prod, slab, A, B, eq.p, rand, coeff_vec, rand_prod, lp.claims_prod_left, lp.claims_prod_right, bottom_leafless ? leaf : nullptr);
       next_layer_hook = nullptr;
       HostClock hcl("layer transition: closing claims + r_layer");
-      for (size_t i = 0; i < k; i++) { t.append_scalar("claim_prod_left", lp.claims_prod_left[i]); t.append_scalar("claim_prod_right", lp.claims_prod_right[i]); }
-      Sc r_layer = t.challenge_scalar("challenge_r_layer");
-      claims_to_verify.clear();
-      for (size_t i = 0; i < k; i++) claims_to_verify.push_back(lp.claims_prod_left[i] + r_layer * (lp.claims_prod_right[i] - lp.claims_prod_left[i]));
-      ScVec ext{r_layer}; ext.insert(ext.end(), rand_prod.begin(), rand_prod.end()); rand = ext;
-      out.proof.push_back(std::move(lp));
+      close_layer(lp, rand_prod, claims_to_verify, rand, out);
     }
     rand_out = rand; return out;
   }
@@ -1725,7 +1636,7 @@ class Prover {
   OpenPrep prep_open(const lasso_fr* d_poly, size_t k, const ScVec& r) {
     OpenPrep pr; const size_t nv = k + r.size();
     pr.k = k; pr.left = nv / 2; pr.right = nv - pr.left;
-    if (P != 1 || pr.left < k || side_off()) return pr;
+    if (P != 1 || pr.left < k || !sw::side_stream()) return pr;
     lasso_ctx* sc = d.side();
     const size_t lrows = (size_t)1 << (pr.left - k), Rn = (size_t)1 << pr.right, nb = (size_t)1 << k;
     pr.M = DBuf(d, nb * Rn); pr.R = DBuf(d, Rn);
@@ -1799,14 +1710,14 @@ class Prover {
         d.chk(lasso_eq_evals(d.ctx, tv.data(), (uint32_t)tv.size(), tables.back().p), "lasso_eq_evals");
       }
     }
-    if (side_off() || P != 1) {} else d.chk(lasso_sync(d.ctx), "lasso_sync");   // the side context reads them
+    if (!sw::side_stream() || P != 1) {} else d.chk(lasso_sync(d.ctx), "lasso_sync");   // the side context reads them
     size_t n_E = next_pow2(alpha * s); nv_derefs = ceil_log2(n_E);
     combined_E = DBuf(d, n_E / P);
     DBuf eq(d, s_loc);
     // The commitment of E needs only E's INTEGER values (a 4-byte gather per lookup), so on one GPU the field-element side of Subtables::new — the
     // tables lifted to Fr, E = T[dim] as 32-byte elements — and the eq table of r run on the side context UNDER the commitment's MSM (VALU-bound;
     // these are HBM-bound) instead of in front of it.
-    const bool side_new = P == 1 && !side_off() && ints;
+    const bool side_new = P == 1 && !!sw::side_stream() && ints;
     lasso_ctx* fc = side_new ? d.side() : d.ctx;
     auto fchk = [&](int32_t rc, const char* what) { if (side_new) d.chk_side(rc, what); else d.chk(rc, what); };
     auto field_side = [&] {
@@ -1868,9 +1779,8 @@ class Prover {
       std::vector<DBuf> work; for (size_t i = 0; i < n_pieces; i++) work.emplace_back(d, d.capacity ? s_loc : alpha * wl);
       // LT: the clone of surge.rs:151 and the scaling of the LT memories are one pass (lasso_lt_prescale with a source): E itself is only read
       std::vector<lasso_fr*> polys; for (size_t i = 0; i < alpha; i++) polys.push_back(work[i / per_piece].p + (i % per_piece) * wl); polys.push_back(eq.p);
-      static const bool u32_off = [] { const char* e = getenv("LASSO_SUMCHECK_U32"); return e && e[0] == '0'; }();   // A/B switch
       // linear strategies: any table values; LT: only because its subtables hold bits (the integer round needs entries 0 / 1)
-      std::vector<const uint32_t*> Eu32; if (P == 1 && (no_clone || table_max <= 1) && E_u32.p && !u32_off && ceil_log2(s) > 0) for (size_t i = 0; i < alpha; i++) Eu32.push_back(E_u32.p + i * s);
+      std::vector<const uint32_t*> Eu32; if (P == 1 && (no_clone || table_max <= 1) && E_u32.p && sw::sumcheck_u32() && ceil_log2(s) > 0) for (size_t i = 0; i < alpha; i++) Eu32.push_back(E_u32.p + i * s);
       SumcheckProof sp = prove_arbitrary(ceil_log2(s), s_loc, polys, S.sumcheck_poly_degree(), r, r_z, &sumcheck_heads, &Eptr, Eu32.empty() ? nullptr : &Eu32);
       sp.write(W);
     }
@@ -1908,7 +1818,7 @@ class Prover {
     std::unique_ptr<Trace> sp(new Trace("Subtables.to_grand_products", d.ctx));
     std::vector<DBuf> t_init, t_read, t_write, t_final;
     // capacity mode: the read / write trees without their leaf layers (half of each tree); the bottom layer's sumcheck recomputes the fingerprints (LeafLayer above)
-    const bool leafless = (d.capacity || dense.compact) && s_loc >= leafless_min();   // a compact representation implies the leafless trees (same size condition)
+    const bool leafless = (d.capacity || dense.compact) && s_loc >= sw::leafless_min();   // a compact representation implies the leafless trees (same size condition)
     // the chi table is next needed after the operations' argument (re-allocated there); and what the earlier phases parked in the recycling pool goes back to the driver
     // before the peak (the primary sumcheck's work arrays: no later buffer has their size) — except buffers of a tree's size, which the loop below takes
     // (+ 1 when the chunked leaf rounds' mini-layers, alpha * s_loc / 4 elements, happen to be of a tree's size — alpha = 4 — or they are allocated anew every proof: tests/test_buffer_policy_cpu.py)
@@ -1958,8 +1868,7 @@ class Prover {
     // Slab mode (round 6): the global layers of P, P/2, .., 2 elements are built from the all-gathered local roots — which arrive ON THE HOST.  Round 5 uploaded them, built the
     // layers on the device and proved them with device rounds (log2 P layers per argument, each a launch or a resident kernel's worth of hand-offs for <= P field products);
     // now the layers are P - 1 host products and bgpa_prove proves them through host_cubic_rounds, as it does a single GPU's tree tops.  LASSO_SLAB_HOST_TOPS=0: round 5's form.
-    static const bool slab_host_tops_off = [] { const char* v = getenv("LASSO_SLAB_HOST_TOPS"); return v && v[0] == '0'; }();
-    const bool slab_host_tops = P > 1 && !slab_host_tops_off;
+    const bool slab_host_tops = P > 1 && sw::slab_host_tops();
     auto root_and_host_top = [&](const DBuf& tree, size_t n_loc, size_t missing, HostTops& T, size_t c, size_t kk) {
       lasso_fr two[2]; const lasso_fr* last[2] = {tree.p + (2 * n_loc - 4 - missing), tree.p + (2 * n_loc - 3 - missing)};
       d.chk(lasso_read_heads(d.ctx, last, 2, two), "lasso_read_heads");
@@ -2023,7 +1932,7 @@ class Prover {
     std::vector<const lasso_fr*> at_ops(Eptr);
     if (!dense.compact) { for (size_t i = 0; i < C; i++) at_ops.push_back(dense.dim(i)); for (size_t i = 0; i < C; i++) at_ops.push_back(dense.read(i)); }
     OpenPrep prep_derefs, prep_ops, prep_mem;
-    const bool side = P == 1 && !side_off() && !dense.compact;   // compact form: dim / read exist as field elements one at a time, on the main context
+    const bool side = P == 1 && !!sw::side_stream() && !dense.compact;   // compact form: dim / read exist as field elements one at a time, on the main context
     if (side) {
       lasso_ctx* sc = d.side();
       std::vector<lasso_fr> rr; for (auto& x : rand_ops) rr.push_back(x.abi());

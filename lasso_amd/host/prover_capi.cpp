@@ -11,12 +11,9 @@ using namespace lasso;
 // The device decoder of compressed points is an OPTIONAL part of the device library (include/lasso_hip_wire.h, not lasso_hip.h): a weak reference, null when these
 // sources are linked against an implementation of lasso_hip.h alone — the verifier then decodes on the host, and lasso_host_points_decompress(where = 1) says so.
 extern "C" int32_t lasso_points_decompress(lasso_ctx*, const uint8_t*, size_t, lasso_affine*, uint8_t*, uint8_t*) __attribute__((weak));
-// Read once per process.  LASSO_VERIFY_DEVICE_POINTS=0: the verifier decodes every point on the host, as it did before the device decoder existed.
+// switches.hpp: LASSO_VERIFY_DEVICE_POINTS=0: the verifier decodes every point on the host, as it did before the device decoder existed.
 // LASSO_WIRE_DEVICE_MIN: the smallest batch the verifier hands to the device.  The default is the smallest batch MEASURED with the device ahead (376 points: AND, C = 1,
 // 2^10 lookups on curve25519, 91 ms -> 59 ms; profiles/verify_device_points.json) — smaller batches have not been measured and stay on the host.
-#define LASSO_WIRE_DEVICE_MIN_DEFAULT 376
-static bool wire_device_on() { static const bool on = [] { const char* e = getenv("LASSO_VERIFY_DEVICE_POINTS"); return !(e && e[0] == '0'); }(); return on; }
-static size_t wire_device_min() { static const size_t v = [] { const char* e = getenv("LASSO_WIRE_DEVICE_MIN"); const long long x = e ? atoll(e) : LASSO_WIRE_DEVICE_MIN_DEFAULT; return (size_t)(x < 1 ? 1 : x); }(); return v; }
 
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
@@ -25,7 +22,7 @@ struct lasso_host {
   Dev dev; std::atomic<int> refs{1};
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
   uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
-  WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && wire_device_on()) { w.fn = &lasso_points_decompress; w.min_points = wire_device_min(); w.counter = &wire_device_points; } return w; }
+  WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
   explicit lasso_host(int device) : dev(device) {}
   void retain() { refs.fetch_add(1, std::memory_order_relaxed); }
   void release() { if (refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete this; }
@@ -86,14 +83,14 @@ int32_t lasso_host_set_comm_shm(lasso_host* h, int32_t rank, int32_t world, cons
     //   1. every rank publishes whether IT can use RCCL at all (librccl loads, LASSO_SLAB_RCCL != 0) — ncclCommInitRank is only entered if ALL can;
     //   2. rank 0 draws the unique id and publishes it with its status — the others read it, and all enter ncclCommInitRank or none does;
     //   3. every rank publishes its ncclCommInitRank outcome — the communicator is kept only if it came up on every rank.
-    const char* e = getenv("LASSO_SLAB_RCCL");
+    const bool rccl_on = sw::slab_rccl();
     if (world > 1) {
       auto all_ok = [&](uint8_t mine, const char* what) {
         std::vector<uint8_t> all((size_t)world, 0);
         if (h->shm->allgather(&mine, all.data(), 1) != 0) throw Error(std::string("lasso_host_set_comm_shm: ranks did not agree on ") + what);
         bool every = true; for (uint8_t v : all) every = every && v; return every;
       };
-      const uint8_t can = (!(e && e[0] == '0') && lasso_rccl_available() == 1) ? 1 : 0;
+      const uint8_t can = (rccl_on && lasso_rccl_available() == 1) ? 1 : 0;
       if (all_ok(can, "RCCL availability")) {
         uint8_t blob[129] = {0};
         if (rank == 0) blob[128] = lasso_rccl_unique_id(blob) == 0 ? 1 : 0;
@@ -254,8 +251,8 @@ int32_t lasso_host_debug_cubic_batched(lasso_host* h, lasso_host_dense* dn, lass
       (c < k ? pa : pb).push_back(bufs.back().p);
     }
     ScVec rv, cv; for (size_t i = 0; i < ell; i++) rv.push_back(Sc::from_abi(rand[i])); for (size_t i = 0; i < k; i++) cv.push_back(Sc::from_abi(coeffs[i]));
-    { const char* e = getenv("LASSO_DEBUG_CUBIC_HOST");   // read per call: the tests drive the HOST rounds (Prover::host_cubic_rounds: the tree tops' layers) through the same scripted points
-      if (e && e[0] == '1') {
+    {   // read per call: the tests drive the HOST rounds (Prover::host_cubic_rounds: the tree tops' layers) through the same scripted points
+      if (sw::debug_cubic_host()) {
         std::vector<ScVec> ha(k, ScVec(n)), hb(k, ScVec(n));
         for (size_t c = 0; c < k; c++) for (size_t i = 0; i < n; i++) { ha[c][i] = Sc::from_abi(A[c * n + i]); hb[c][i] = Sc::from_abi(B[c * n + i]); }
         SumcheckProof sp; ScVec r_out; std::vector<lasso_fr> heads; Sc e0 = Sc::from_abi(*claim);
