@@ -157,6 +157,16 @@ int32_t lasso_host_points_decompress(lasso_host* h, const uint8_t* wire32, size_
 /* *device_points = compressed points this host has decoded on the device so far (verifier and lasso_host_points_decompress(where = 1) together);
  * *device_available = 1 when the device decoder exists; either may be NULL; reset != 0 zeroes the counter. */
 int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* device_available, int32_t reset);
+/* VariableBaseMSM::msm(bases, scalars) (src/msm/mod.rs:36-40) over the caller's own points, with nothing prepared (lasso_msm_points, include/lasso_hip_msm.h): points = n
+ * affine points in the form lasso_host_gens_from_points takes (any multiset of group points; an all-zero entry is the identity), scalars = n Montgomery-form field
+ * elements; n = 0 gives the identity.  The result leaves in wire form (serialize_compressed, 32 bytes), like every point that crosses this ABI.  -1 with a message when
+ * the device library this host was linked against has no such entry.
+ * lasso_host_verify* takes its MSMs over commitment rows (C_LZ = <L, C>, one per opening: four per proof) through the same entry when it exists; LASSO_VERIFY_MSM_POINTS=0 keeps
+ * lasso_bases_create + lasso_msm per call.  Verdicts, return codes and error texts do not depend on the path. */
+int32_t lasso_host_msm_points(lasso_host* h, const lasso_affine* points, const lasso_fr* scalars, size_t n, uint8_t* out_compressed32);
+/* *points_calls = MSMs over commitment rows this host's verifier has run through lasso_msm_points so far; *available = 1 when the device library has the entry; either may
+ * be NULL; reset != 0 zeroes the counter. */
+int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* available, int32_t reset);
 /* Validate a strategy descriptor without proving anything: 0, or LASSO_ERR_INVALID (-1) with the reason in lasso_host_last_error().  For kind = LASSO_CUSTOM
  * (include/lasso_hip.h lasso_strategy_custom, passed as (const lasso_strategy*)&custom) this is the check lasso_host_prove* / lasso_host_verify* make on entry: table pointers,
  * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (2^log_m products per memory): THE TABLES ARE PART OF THE STATEMENT,

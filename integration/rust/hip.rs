@@ -258,6 +258,19 @@ impl HipProver {
     let probe = key_of(gens, [0; 4]);
     self.gens_cache.borrow_mut().retain(|(k, g)| { let same = k.addrs == probe.addrs && k.sizes == probe.sizes && k.probe == probe.probe; if same { unsafe { lasso_host_gens_free(*g) } } !same });
   }
+
+  /// `VariableBaseMSM::msm(bases, scalars)` (src/msm/mod.rs:36-40) on the device over the caller's own points, with nothing prepared (lasso_host_msm_points): no tables are
+  /// built, so it suits points that are used once.  The identity among `bases` is passed as the all-zero entry the library skips.  Err on a length mismatch, as the reference.
+  pub fn msm<G: CurveGroup>(&self, bases: &[G::Affine], scalars: &[G::ScalarField]) -> Result<G, usize> {
+    use ark_ec::AffineRepr;
+    use ark_serialize::CanonicalDeserialize;
+    if bases.len() != scalars.len() { return Err(bases.len().min(scalars.len())); }
+    let pts: Vec<lasso_affine> = bases.iter().map(|p| if p.is_zero() { lasso_affine { x: [0; 4], y: [0; 4] } } else { affine_to_abi::<G>(p) }).collect();
+    assert!(std::mem::size_of::<G::ScalarField>() == std::mem::size_of::<lasso_fr>());
+    let mut wire = [0u8; 32];
+    chk(unsafe { lasso_host_msm_points(self.h, pts.as_ptr(), scalars.as_ptr() as *const lasso_fr, pts.len(), wire.as_mut_ptr()) }, "lasso_host_msm_points");
+    Ok(G::Affine::deserialize_compressed(&wire[..]).expect("the library returned a point that does not deserialize").into())
+  }
 }
 /// ark-ec affine point -> `lasso_affine`: x, y as ark-ff's Montgomery limbs; generators are never the point at infinity
 fn affine_to_abi<G: CurveGroup>(p: &G::Affine) -> lasso_affine {

@@ -159,4 +159,14 @@ def declare_wire(lib):
     return ["lasso_points_decompress"]
 
 
+def declare_msm_points(lib):
+    """include/lasso_hip_msm.h — the MSM over the caller's own points, no lasso_bases.  Declared apart from declare(), as declare_wire is: an implementation of
+    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
+    for name in ("lasso_msm_points", "lasso_msm_points_dev"):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp, vp, vp, sz, vp]
+    return ["lasso_msm_points", "lasso_msm_points_dev"]
+
+
 HEADER_SYMBOLS = None

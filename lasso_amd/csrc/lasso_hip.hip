@@ -15,6 +15,8 @@
 #include "densify_kernels.cuh"
 #include "../../include/lasso_hip_wire.h"
 #include "wire_kernels.cuh"
+#include "../../include/lasso_hip_msm.h"
+#include "msm_points_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1810,6 +1812,38 @@ int32_t lasso_msm_dev(lasso_ctx* c, const lasso_bases* b, const lasso_fr* d_scal
   hipLaunchKernelGGL(k_fr_to_canonical, dim3(grid_for(n)), dim3(256), 0, c->stream, (const fr_t*)d_scalars, n, d_can);
   return run_msm(c, (const uint8_t*)d_can, 32, MSM_WINDOWS, n * 32, 1, n, b, (uint8_t*)(d_can + n), out);
 }
+// include/lasso_hip_msm.h: the MSM over the caller's own points (msm_points_kernels.cuh).  Device layout in the context's scratch, every region on a 256-byte boundary:
+// [points 64 n][scalars 32 n] (host form only) [Niels entries 128 n][digits 33 n][chunk sums 33 K][window sums 33][result], K = ceil(n / 1024) chunks.
+static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static int32_t msm_points_impl(lasso_ctx* c, const char* who, const lasso_affine* points, const lasso_fr* scalars, size_t n, bool on_host, lasso_point* out) {
+  REQUIRE(c, out && n < ((size_t)1 << 28) && (n == 0 || (points && scalars)));
+  const size_t K = n ? (n + MSMP_CHUNK - 1) / MSMP_CHUNK : 1;
+  const size_t o_pts = 0, o_scal = o_pts + (on_host ? up256(n * sizeof(lasso_affine)) : 0), o_nl = o_scal + (on_host ? up256(n * sizeof(lasso_fr)) : 0), o_dig = o_nl + up256(n * sizeof(niels29));
+  const size_t o_part = o_dig + up256(n * MSMP_NW), o_wsum = o_part + up256(MSMP_NW * K * sizeof(pt29)), o_out = o_wsum + up256(MSMP_NW * sizeof(pt29));
+  int32_t rc = ensure_scratch(c, o_out + 256);
+  if (rc) return rc == LASSO_ERR_UNSUPPORTED ? fail(c, rc, std::string(who) + ": the scratch buffer cannot grow while a resident kernel is active") : rc;
+  uint8_t* base = (uint8_t*)c->d_scratch;
+  const fq_t* d_aff = (const fq_t*)points; const fr_t* d_scal = (const fr_t*)scalars;
+  if (on_host && n) {
+    HIPCHK(c, hipMemcpyAsync(base + o_pts, points, n * sizeof(lasso_affine), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(base + o_scal, scalars, n * sizeof(lasso_fr), hipMemcpyHostToDevice, c->stream));
+    d_aff = (const fq_t*)(base + o_pts); d_scal = (const fr_t*)(base + o_scal);
+  }
+  {
+    ProfScope ps(c, LASSO_K_MSM, (double)n * (sizeof(lasso_affine) + sizeof(lasso_fr)), msm_ref_adds(1, n, FR_MODULUS_BITS), false, (double)n * MSMP_NW);
+    if (n) hipLaunchKernelGGL(k_msmp_prepare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_aff, d_scal, (uint32_t)n, (niels29*)(base + o_nl), (int8_t*)(base + o_dig));
+    hipLaunchKernelGGL(k_msmp_buckets, dim3(MSMP_NW, (unsigned)K), dim3(MSM_THREADS), 0, c->stream, (const int8_t*)(base + o_dig), (uint32_t)n, (const niels29*)(base + o_nl), (pt29*)(base + o_part));
+    hipLaunchKernelGGL(k_points_sum, dim3(MSMP_NW), dim3(MSM_THREADS), 0, c->stream, (const pt29*)(base + o_part), (uint32_t)K, (ed_point*)nullptr, (uint32_t*)(base + o_wsum),
+                       (uint32_t*)nullptr, (uint32_t*)nullptr, 0u);
+    hipLaunchKernelGGL(k_msmp_horner, dim3(1), dim3(64), 0, c->stream, (const pt29*)(base + o_wsum), (ed_point*)(base + o_out));
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, base + o_out, sizeof(ed_point), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+int32_t lasso_msm_points(lasso_ctx* c, const lasso_affine* points, const lasso_fr* scalars, size_t n, lasso_point* out) { return msm_points_impl(c, "lasso_msm_points", points, scalars, n, true, out); }
+int32_t lasso_msm_points_dev(lasso_ctx* c, const lasso_affine* d_points, const lasso_fr* d_scalars, size_t n, lasso_point* out) { return msm_points_impl(c, "lasso_msm_points_dev", d_points, d_scalars, n, false, out); }
 __global__ void __launch_bounds__(256) k_scale_to_integers(const fr_t* __restrict__ src, size_t n, fr_t scale, fr_t t0, fr_t t1, fr_t* __restrict__ dst) {
   const fr29 ss = fr29_unpack_s(scale); fr29 k32 = fr29_zero(); k32.v[0] = 32;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = fr29_store(fr29_mul(fr29_mul(fr29_unpack_u(src[i]), ss), k32));   // (u * s) = u-form, then -> integer

@@ -340,6 +340,35 @@ class Device:
         self._chk(self.lib.lasso_msm(self.ctx, C.c_void_p(bases), _vp(scalars), scalars.shape[0], _vp(out)))
         return out
 
+    def _msm_points_fn(self, name):
+        if not hasattr(self, "_msm_points_ok"):
+            try:
+                _abi.declare_msm_points(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_msm_points (include/lasso_hip_msm.h)")
+            self._msm_points_ok = True
+        return getattr(self.lib, name)
+
+    def msm_points(self, points, scalars):
+        """sum_j scalars[j] * points[j] over the caller's own points, nothing prepared (include/lasso_hip_msm.h lasso_msm_points): `points` = (n, 8) uint64 affine
+        Montgomery limbs as bases_create takes them (an all-zero row is the identity), `scalars` = (n, 4) uint64.  Returns a (1, 16) projective point, as msm does.
+        A library without the entry point is an error, not a fall-back."""
+        fn = self._msm_points_fn("lasso_msm_points")
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        if points.shape[0] != scalars.shape[0]:
+            raise LassoError("msm_points: as many scalars as points are needed")
+        out = np.empty((1, 16), dtype=np.uint64)
+        self._chk(fn(self.ctx, _vp(points), _vp(scalars), points.shape[0], _vp(out)))
+        return out
+
+    def msm_points_dev(self, d_points, d_scalars, n):
+        """msm_points over arrays that are already on the device (lasso_msm_points_dev)"""
+        fn = self._msm_points_fn("lasso_msm_points_dev")
+        out = np.empty((1, 16), dtype=np.uint64)
+        self._chk(fn(self.ctx, C.c_void_p(d_points), C.c_void_p(d_scalars), n, _vp(out)))
+        return out
+
     def msm_dev(self, bases, d_scalars, n):
         out = np.empty((1, 16), dtype=np.uint64)
         self._chk(self.lib.lasso_msm_dev(self.ctx, C.c_void_p(bases), C.c_void_p(d_scalars), n, _vp(out)))

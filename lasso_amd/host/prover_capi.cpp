@@ -5,6 +5,7 @@
 #include <atomic>
 #include "../../include/lasso_prover.h"
 #include "../../include/lasso_hip_wire.h"
+#include "../../include/lasso_hip_msm.h"
 
 using namespace lasso;
 
@@ -15,6 +16,11 @@ extern "C" int32_t lasso_points_decompress(lasso_ctx*, const uint8_t*, size_t, l
 // LASSO_WIRE_DEVICE_MIN: the smallest batch the verifier hands to the device.  The default is the smallest batch MEASURED with the device ahead (376 points: AND, C = 1,
 // 2^10 lookups on curve25519, 91 ms -> 59 ms; profiles/verify_device_points.json) — smaller batches have not been measured and stay on the host.
 
+// The table-free MSM over caller points (include/lasso_hip_msm.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone — the
+// verifier's MSMs over commitment rows then build a lasso_bases per call as before.  LASSO_VERIFY_MSM_POINTS=0 keeps that path where the entry point exists (A/B switch).
+// No size threshold (LASSO_MSM_POINTS_MIN) yet: tools/verify_bench.py --ab msm_points is what one would be set from.
+extern "C" int32_t lasso_msm_points(lasso_ctx*, const lasso_affine*, const lasso_fr*, size_t, lasso_point*) __attribute__((weak));
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -22,6 +28,8 @@ struct lasso_host {
   Dev dev; std::atomic<int> refs{1};
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
   uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
+  uint64_t msm_points_calls = 0;     // Verifier::msm_points calls of this host that took lasso_msm_points (lasso_host_msm_stats)
+  PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
   WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
   explicit lasso_host(int device) : dev(device) {}
   void retain() { refs.fetch_add(1, std::memory_order_relaxed); }
@@ -217,8 +225,9 @@ int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_stra
     ProofTranscript t(tv, tu);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder());
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
+    HostClock::dump();
     return 0;)
 }
 int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strategy* st, size_t s, const lasso_fr* r, size_t r_len, const char* tl,
@@ -229,8 +238,9 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
     ProofTranscript t(tl);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder());
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
+    HostClock::dump();
     return 0;)
 }
 // Test support: Prover::prove_cubic_batched (sumcheck.rs:27-135 with C = EqPolynomial(rand).evals(), grand_product.rs:122-128) on caller-supplied
@@ -290,6 +300,23 @@ int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* d
     if (device_points) *device_points = h->wire_device_points;
     if (device_available) *device_available = lasso_points_decompress ? 1 : 0;
     if (reset) h->wire_device_points = 0;
+    return 0;)
+}
+int32_t lasso_host_msm_points(lasso_host* h, const lasso_affine* points, const lasso_fr* scalars, size_t n, uint8_t* out_compressed32) {
+  GUARD(
+    if (!h || !out_compressed32 || (n && (!points || !scalars))) throw Error("lasso_host_msm_points: null argument");
+    if (!lasso_msm_points) throw Error("lasso_host_msm_points: the MSM over caller points (lasso_msm_points, include/lasso_hip_msm.h) is not available in the device library this host was linked against");
+    lasso_point out;
+    h->dev.chk(lasso_msm_points(h->dev.ctx, points, scalars, n, &out), "lasso_msm_points");
+    compress_one(Pt::from_abi(out), out_compressed32);
+    return 0;)
+}
+int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_msm_stats: null host");
+    if (points_calls) *points_calls = h->msm_points_calls;
+    if (available) *available = lasso_msm_points ? 1 : 0;
+    if (reset) h->msm_points_calls = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

@@ -21,6 +21,7 @@
 #pragma once
 #include "prover.hpp"
 #include "../../include/lasso_hip_wire.h"
+#include "../../include/lasso_hip_msm.h"
 
 namespace lasso {
 
@@ -100,6 +101,12 @@ struct WireDecoder {
   int32_t (*fn)(lasso_ctx*, const uint8_t*, size_t, lasso_affine*, uint8_t*, uint8_t*) = nullptr;
   size_t min_points = 0;          // batches below this stay on the host (LASSO_WIRE_DEVICE_MIN)
   uint64_t* counter = nullptr;    // points decoded on the device, per host (lasso_host_wire_stats)
+};
+
+// The table-free MSM over caller points as the verifier sees it (prover_capi.cpp fills it in: lasso_msm_points is a weak reference too, include/lasso_hip_msm.h)
+struct PointsMsm {
+  int32_t (*fn)(lasso_ctx*, const lasso_affine*, const lasso_fr*, size_t, lasso_point*) = nullptr;
+  uint64_t* counter = nullptr;    // Verifier::msm_points calls that took it, per host (lasso_host_msm_stats)
 };
 
 // ------------------------------------------------------------------ reader of the ark-serialize byte stream
@@ -223,7 +230,7 @@ inline Sc combine_lookups(const Strategy& S, const ScVec& vals) {
 
 // ------------------------------------------------------------------ the verifier
 class Verifier {
-  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t; WireDecoder decoder;
+  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t; WireDecoder decoder; PointsMsm points_msm;
 
   // sumcheck.rs:286-328
   bool sumcheck_verify(const SumcheckProof& proof, const Sc& claim, size_t num_rounds, size_t degree_bound, Sc& e_out, ScVec& r_out) {
@@ -264,16 +271,25 @@ class Verifier {
     }
     claims_out = claims; rand_out = rand; return true;
   }
-  // VariableBaseMSM::msm over arbitrary points (the commitment rows): a base table built for this call, then the device MSM
+  // VariableBaseMSM::msm over arbitrary points (the commitment rows).  The rows are used once, so the table-free MSM takes them where the device library has it
+  // (points_msm, LASSO_VERIFY_MSM_POINTS); otherwise a base table is built for this call, then the device MSM.  Same group element either way.
   Pt msm_points(const std::vector<WirePoint>& pts, const ScVec& scalars) {
     LASSO_REQUIRE(pts.size() == scalars.size());
     std::vector<lasso_affine> aff; std::vector<lasso_fr> sc;
     for (size_t i = 0; i < pts.size(); i++) { if (pts[i].infinity) continue; lasso_affine a; affine_to_abi(pts[i].p, a); aff.push_back(a); sc.push_back(scalars[i].abi()); }
     if (aff.empty()) return Pt::identity();
+    lasso_point out;
+    if (points_msm.fn) {
+      HostClock hc("verify: msm_points (table-free)");
+      d.chk(points_msm.fn(d.ctx, aff.data(), sc.data(), sc.size(), &out), "lasso_msm_points");
+      if (points_msm.counter) ++*points_msm.counter;
+      return Pt::from_abi(out);
+    }
     lasso_bases* b = nullptr;
-    d.chk(lasso_bases_create(d.ctx, aff.data(), aff.size(), &b), "lasso_bases_create");
-    lasso_point out; const int32_t rc = lasso_msm(d.ctx, b, sc.data(), sc.size(), &out);
-    lasso_bases_destroy(d.ctx, b);
+    { HostClock hc("verify: msm_points create"); d.chk(lasso_bases_create(d.ctx, aff.data(), aff.size(), &b), "lasso_bases_create"); }
+    int32_t rc;
+    { HostClock hc("verify: msm_points msm"); rc = lasso_msm(d.ctx, b, sc.data(), sc.size(), &out); }
+    { HostClock hc("verify: msm_points destroy"); lasso_bases_destroy(d.ctx, b); }
     d.chk(rc, "lasso_msm");
     return Pt::from_abi(out);
   }
@@ -308,7 +324,7 @@ class Verifier {
     for (size_t i = 1; i < n; i++) { const size_t lg_i = 31 - (size_t)__builtin_clz((uint32_t)i), k = (size_t)1 << lg_i; s[i] = s[i - k] * ch[(lg_n - 1) - lg_i]; }
     // G_hat = <s, G>: the generators' device table (first n entries of [G.., Q, h])
     std::vector<lasso_fr> s_abi(n); for (size_t i = 0; i < n; i++) s_abi[i] = s[i].abi();
-    lasso_point gh; d.chk(lasso_msm(d.ctx, g.bases, s_abi.data(), n, &gh), "lasso_msm");
+    lasso_point gh; { HostClock hc("verify: G_hat msm"); d.chk(lasso_msm(d.ctx, g.bases, s_abi.data(), n, &gh), "lasso_msm"); }
     const Pt G_hat = Pt::from_abi(gh);
     Sc a_hat = Sc::zero(); for (size_t i = 0; i < n; i++) a_hat += R[i] * s[i];
     Pt Gamma_hat = Gamma;   // <u^2, L> + <u^-2, R> + Gamma: 2 lg n + 1 terms, host
@@ -337,7 +353,7 @@ class Verifier {
   }
 
  public:
-  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_) {}
+  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder(), const PointsMsm& m_ = PointsMsm()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_), points_msm(m_) {}
 
   // Proof and commitment with every point decoded in ONE device call.  false = not taken (no device decoder, a batch below the threshold) or not clean (the bytes do
   // not walk, a scalar is not canonical, some encoding is rejected): the caller then runs the sequential reader, which finds the FIRST error in stream order and

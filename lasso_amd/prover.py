@@ -67,6 +67,8 @@ def declare_prover(lib):
     lib.lasso_host_strategy_check.argtypes = [C.POINTER(_abi.Strategy)]
     lib.lasso_host_points_decompress.argtypes = [vp, vp, sz, i32, vp, vp, vp]
     lib.lasso_host_wire_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
+    lib.lasso_host_msm_points.argtypes = [vp, vp, vp, sz, vp]
+    lib.lasso_host_msm_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
     lib.lasso_host_gen_indices.argtypes = [sz, sz, vp]
     lib.lasso_host_gen_random_point.argtypes = [sz, vp]
     return lib
@@ -203,6 +205,25 @@ class HostProver:
         k, a = C.c_uint64(), C.c_int32()
         self._chk(self.lib.lasso_host_wire_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
         return {"device_points": k.value, "device_available": bool(a.value)}
+
+    def msm_points(self, points, scalars):
+        """VariableBaseMSM::msm over the caller's own points, nothing prepared (lasso_host_msm_points): `points` = (n, 8) uint64 affine Montgomery limbs (an all-zero row
+        is the identity), `scalars` = (n, 4) uint64.  Returns the 32 wire bytes of the sum; LassoError when the device library has no such entry."""
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        if points.shape[0] != scalars.shape[0]:
+            raise LassoError("msm_points: as many scalars as points are needed")
+        out = np.zeros(32, dtype=np.uint8)
+        vpt = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.lasso_host_msm_points(self.h, vpt(points), vpt(scalars), points.shape[0], vpt(out)))
+        return out.tobytes()
+
+    def msm_stats(self, reset=False):
+        """{"points_calls": the verifier's MSMs over commitment rows that ran table-free on this host so far, "available": whether the device library has
+        lasso_msm_points} (lasso_host_msm_stats)"""
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(self.lib.lasso_host_msm_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"points_calls": k.value, "available": bool(a.value)}
 
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""

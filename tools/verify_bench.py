@@ -7,7 +7,12 @@ so every (instance, setting) is measured in a fresh child process: it proves onc
 reports the kernel's own time from the library's event brackets (lasso_prof_*, family LASSO_K_MISC, in an extra verify that is not among the timed ones).
 
 Writes one JSON file (default profiles/verify_device_points.json) with, per instance, median / min / max of both settings, the ratio, and whether the acceptance condition
-holds: the default is not slower than the host path by more than the host path's own spread.  Needs the built libraries and a GPU; nothing here falls back to a CPU."""
+holds: the default is not slower than the host path by more than the host path's own spread.  Needs the built libraries and a GPU; nothing here falls back to a CPU.
+
+--ab msm_points: the same five instances with the verifier's MSMs over commitment rows table-free (the default: lasso_msm_points, include/lasso_hip_msm.h) against
+LASSO_VERIFY_MSM_POINTS=0 (lasso_bases_create + lasso_msm + lasso_bases_destroy per call, the only path before).  Per setting, beside the verify times: the host timers
+of Verifier::msm_points' phases and of the G_hat MSM (LASSO_TRACE=2 buckets, mean per verify over the timed runs) and the peak device bytes during a verify
+(lasso_host_mem_stats).  Default output: profiles/verify_msm_points.json."""
 import argparse
 import ctypes as C
 import json
@@ -36,14 +41,19 @@ def child(curve, log_s, runs):
     comm = hp.commit(dense, gens); proof = hp.prove(dense, gens, S, r)
     hp.free(dense)
     assert hp.verify(gens, S, s, r, proof, comm) is True      # warm-up: buffers, tables
-    hp.wire_stats(reset=True)
+    hp.wire_stats(reset=True); hp.msm_stats(reset=True)
+    live_before = hp.mem_stats(reset=True)["live_bytes"]
+    sys.stderr.write("VERIFY_BENCH_TIMED_BEGIN\n"); sys.stderr.flush()
     ms = []
     for _ in range(runs):
         t0 = time.perf_counter()
         ok = hp.verify(gens, S, s, r, proof, comm)
         ms.append((time.perf_counter() - t0) * 1e3)
         assert ok is True
+    sys.stderr.write("VERIFY_BENCH_TIMED_END\n"); sys.stderr.flush()
+    mem = hp.mem_stats()
     points = hp.wire_stats()["device_points"] // runs
+    msm_calls = hp.msm_stats()["points_calls"] // runs
     kernel_ms = None
     if points:
         lib = load_device_library(curve=curve)      # the same shared object the host library is linked against
@@ -56,34 +66,86 @@ def child(curve, log_s, runs):
         kernel_ms = t.value
     hp.free(None, gens); hp.close()
     print("VERIFY_BENCH " + json.dumps({"curve": curve, "log_s": log_s, "verify_ms": ms, "device_points_per_verify": points, "kernel_ms": kernel_ms, "proof_bytes": len(proof),
-                                        "commitment_bytes": len(comm)}))
+                                        "commitment_bytes": len(comm), "msm_points_calls_per_verify": msm_calls, "live_bytes_before": live_before,
+                                        "peak_bytes_during_verifies": mem["peak_bytes"]}))
 
 
 def run_child(curve, log_s, runs, env_extra):
     env = dict(os.environ)
-    env.pop("LASSO_VERIFY_DEVICE_POINTS", None)
+    env.pop("LASSO_VERIFY_DEVICE_POINTS", None); env.pop("LASSO_VERIFY_MSM_POINTS", None); env.pop("LASSO_TRACE", None)
     env.update(env_extra)
     res = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", curve, str(log_s), "--runs", str(runs)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     if res.returncode != 0:
         raise SystemExit(f"child failed ({curve}, 2^{log_s}, {env_extra}):\n{res.stdout[-2000:]}\n{res.stderr[-4000:]}")
     line = [ln for ln in res.stdout.split("\n") if ln.startswith("VERIFY_BENCH ")][-1]
-    return json.loads(line[len("VERIFY_BENCH "):])
+    out = json.loads(line[len("VERIFY_BENCH "):])
+    # LASSO_TRACE=2: the host time buckets ("[host] <name> <ms> ms" on stderr, dumped after every verify) of the timed runs, mean per verify
+    err = res.stderr
+    if "VERIFY_BENCH_TIMED_BEGIN" in err:
+        timed = err.split("VERIFY_BENCH_TIMED_BEGIN", 1)[1].split("VERIFY_BENCH_TIMED_END", 1)[0]
+        buckets = {}
+        for ln in timed.split("\n"):
+            if ln.startswith("[host] ") and ln.endswith(" ms"):
+                name, val = ln[len("[host] "):-len(" ms")].rsplit(None, 1)
+                buckets[name.strip()] = buckets.get(name.strip(), 0.0) + float(val)
+        out["host_buckets_ms_per_verify"] = {k: v / runs for k, v in sorted(buckets.items())}
+    return out
 
 
 def summary(ms):
     return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "spread_ms": max(ms) - min(ms), "all_ms": ms}
 
 
+PHASES = ["verify: msm_points create", "verify: msm_points msm", "verify: msm_points destroy", "verify: msm_points (table-free)", "verify: G_hat msm"]
+
+
+def main_msm_points(a, runs):
+    rows = []
+    for curve, log_s in INSTANCES:
+        name = f"{curve}-2p{log_s}"
+        if a.only and name not in a.only.split(","):
+            continue
+        off = run_child(curve, log_s, runs, {"LASSO_VERIFY_MSM_POINTS": "0", "LASSO_TRACE": "2"})
+        on = run_child(curve, log_s, runs, {"LASSO_VERIFY_MSM_POINTS": "1", "LASSO_TRACE": "2"})
+        assert off["msm_points_calls_per_verify"] == 0 and on["msm_points_calls_per_verify"] > 0
+        so, sn = summary(off["verify_ms"]), summary(on["verify_ms"])
+        row = {"instance": name, "strategy": "and", "C": 1, "log_m": 16, "commitment_rows": (on["commitment_bytes"] - 16) // 32, "msm_points_calls_per_verify": on["msm_points_calls_per_verify"],
+               "table_path": so, "table_free": sn,
+               "table_path_phases_ms_per_verify": {k: off.get("host_buckets_ms_per_verify", {}).get(k) for k in PHASES if k != "verify: msm_points (table-free)"},
+               "table_free_phases_ms_per_verify": {k: on.get("host_buckets_ms_per_verify", {}).get(k) for k in PHASES[3:]},
+               "table_path_peak_device_bytes": off["peak_bytes_during_verifies"], "table_free_peak_device_bytes": on["peak_bytes_during_verifies"],
+               "peak_device_bytes_saved": off["peak_bytes_during_verifies"] - on["peak_bytes_during_verifies"],
+               "speedup": so["median_ms"] / sn["median_ms"],
+               "no_slower_than_table_path_within_its_spread": sn["median_ms"] <= so["median_ms"] + so["spread_ms"]}
+        rows.append(row)
+        print(f"{name}: table path {so['median_ms']:.2f} ms [{so['min_ms']:.2f}, {so['max_ms']:.2f}] peak {row['table_path_peak_device_bytes'] / 1e6:.1f} MB   table-free {sn['median_ms']:.2f} ms "
+              f"[{sn['min_ms']:.2f}, {sn['max_ms']:.2f}] peak {row['table_free_peak_device_bytes'] / 1e6:.1f} MB   x{row['speedup']:.2f}", flush=True)
+        print("   phases (ms per verify): table path", row["table_path_phases_ms_per_verify"], " table-free", row["table_free_phases_ms_per_verify"], flush=True)
+    out = {"what": "HostProver.verify, the MSMs over commitment rows through lasso_bases_create + lasso_msm + lasso_bases_destroy per call (LASSO_VERIFY_MSM_POINTS=0: the only "
+                   "path of the parent commit, here with host timers around its phases) against table-free (the default, lasso_msm_points); same session, same machine, a fresh "
+                   "process per setting, LASSO_TRACE=2 for the phase timers in both", "runs_per_setting": runs, "rows": rows,
+           "table_free_ahead_at_every_instance": all(r["table_free"]["median_ms"] < r["table_path"]["median_ms"] for r in rows)}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--child", nargs=2, metavar=("CURVE", "LOG_S"))
     ap.add_argument("--runs", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_device_points.json"))
+    ap.add_argument("--ab", choices=["device_points", "msm_points"], default="device_points", help="which switch is compared (see above)")
+    ap.add_argument("--out", default=None, help="default: profiles/verify_device_points.json, or profiles/verify_msm_points.json with --ab msm_points")
     ap.add_argument("--only", default="", help="comma-separated subset, e.g. curve25519-2p10,bn254-2p20")
     a = ap.parse_args()
     if a.child:
         return child(a.child[0], int(a.child[1]), a.runs)
     runs = max(a.runs, 5)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "verify_msm_points.json" if a.ab == "msm_points" else "verify_device_points.json")
+    if a.ab == "msm_points":
+        return main_msm_points(a, max(a.runs, 7))
     rows = []
     for curve, log_s in INSTANCES:
         name = f"{curve}-2p{log_s}"
