@@ -10,6 +10,8 @@
 #include <cstdlib>
 #include <ctime>
 #include "../../include/lasso_hip.h"
+#include "device_switches.cuh"   // every LASSO_* environment variable this library reads
+#include "launch_plan.cuh"       // which kernel serves a shape, its grid and its scratch: pure functions of shape and switches
 #include "poly_kernels.cuh"
 #include "msm_kernels.cuh"
 #include "densify_kernels.cuh"
@@ -30,8 +32,9 @@ __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, co
 }
 
 static_assert(sizeof(lasso_fr) == 32 && sizeof(fr_t) == 32, "Fr layout");
-static_assert(sizeof(lasso_affine) == 64 && sizeof(lasso_point) == 128 && sizeof(ed_point) == 128 && sizeof(niels29) == (MSM_NIELS_ALIGN > 16 ? 128 : 112) && sizeof(pt29) == 144, "curve layouts");
+static_assert(sizeof(lasso_affine) == 64 && sizeof(lasso_point) == 128 && sizeof(ed_point) == 128 && sizeof(niels29) == (MSM_NIELS_ALIGN > 16 ? 128 : 112) && sizeof(pt29) == MSM_PT29_BYTES, "curve layouts");
 
+namespace dsw = lasso::dsw;
 struct EventPair { hipEvent_t a, b; int kid; double bytes, units, units2; bool large; bool counted; };
 #define LASSO_PROF_COUNT_SLOTS 4096   // device counters of exactly executed additions, one group of 64 words per bracketed launch of the fully-profiled step (the waves of a launch spread their atomics over the group)
 struct lasso_ctx {
@@ -206,7 +209,6 @@ static void prof_flush(lasso_ctx* c) {
   }
   c->events_used = 0;
 }
-static inline unsigned grid_for(size_t n, unsigned cap = 2048) { size_t g = (n + LASSO_BLOCK - 1) / LASSO_BLOCK; if (g < 1) g = 1; if (g > cap) g = cap; return (unsigned)g; }
 static inline fr_t to_fr(const lasso_fr* p) { fr_t r; memcpy(r.v, p, 32); return r; }
 // Wait until the device has stored sequence number `seq` to the mapped flag, then copy `count` results out of the mapped buffer.
 // The producer's stores to h_small are ordered before the flag by a system-scope release on the device (k_publish / publish_flag).
@@ -450,8 +452,8 @@ int32_t lasso_ctx_create_background(int32_t device, int32_t background, lasso_ct
   if (hipMalloc((void**)&c->d_counters, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess || hipMemset(c->d_counters, 0, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "counters alloc"); }
   if (hipHostMalloc((void**)&c->h_flag, 256, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer((void**)&c->d_flag, c->h_flag, 0) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "mapped flag alloc"); }
   *c->h_flag = 0;
-  { const char* v = getenv("LASSO_TAGGED_RESULTS"); c->tagged = !(v && v[0] == '0'); }   // A/B switch: the flag protocol for every hand-off
-  { const char* v = getenv("LASSO_SEQ_START"); if (v) c->seq = (uint32_t)strtoul(v, nullptr, 0); }   // tests: start close to the end of a sequence epoch (next_seq)
+  c->tagged = dsw::tagged_results();   // A/B switch: the flag protocol for every hand-off
+  if (dsw::seq_start() >= 0) c->seq = (uint32_t)dsw::seq_start();   // tests: start close to the end of a sequence epoch (next_seq)
   c->mail_h = c->h_flag + 32; c->mail_d = c->d_flag + 32;   // 128-byte offset: 16-byte aligned chunks
   memset(c->h_flag, 0, 256);   // the flag word, the LT round's "not a bit" word and BOTH mailboxes (hipHostMalloc does not promise zeroed memory: a stale poison tag in the second mailbox ended the first launched-ahead round)
   int32_t rc = ensure_small(c, (size_t)1 << 16); if (rc) { g_create_err = c->err; delete c; return rc; }   // 2 MiB of mapped result buffer: the largest a-vector / row-commitment hand-off without a reallocation
@@ -615,12 +617,7 @@ int32_t lasso_bind_top(lasso_ctx* c, lasso_fr* const* d_polys, uint32_t npolys, 
   hipLaunchKernelGGL(k_bind_top, dim3(grid_for(half, 4096), npolys), dim3(LASSO_BLOCK), 0, c->stream, T, half, to_fr(r));
   HIPCHK(c, hipGetLastError()); return 0;
 }
-// x-extent of the cubic-round grids: ~512 workgroups over the whole grid.  Inside a proof (random data, tools/gpu_sweep_roofline.sh) 512 total beats 1024 by 3-10% and 256 by 10%
-// for both the cubic (ny = 2) and the linear (ny = 1) rounds, although in isolation on constant data 1024 is 6% faster (profiles/r01_microbench_v2.txt); the kernels are VALU-bound
-// and every extra workgroup adds a reduction epilogue), LASSO_CUBIC_NX overrides for experiments
-static unsigned cubic_nx_cap(unsigned ny) { static const long e = [] { const char* v = getenv("LASSO_CUBIC_NX"); return v ? atol(v) : 0L; }(); if (e > 0) return (unsigned)e; unsigned c = 512 / (ny ? ny : 1); return c < 64 ? 64 : c; }
-static bool cubic_wide() { static const bool on = [] { const char* v = getenv("LASSO_CUBIC_WIDE"); return !(v && v[0] == '0'); }(); return on; }   // double-width accumulators in the two-sum fused round (A/B switch)
-#define CUBIC_SMALL_Q 64   // rounds with at most this many indices per circuit take the latency-shaped kernel
+static unsigned round_nx(size_t items, unsigned ny) { return round_nx(items, ny, dsw::cubic_nx()); }   // x-extent of the round grids (launch_plan.cuh)
 // the reference's loop with an explicit third polynomial (any C): kept as the literal counterpart of sumcheck.rs:49-93
 int32_t lasso_sumcheck_cubic_round(lasso_ctx* c, const lasso_fr* const* d_A, const lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_C, size_t n, lasso_fr* out) {
   REQUIRE(c, d_A && d_B && d_C && out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0);
@@ -628,7 +625,7 @@ int32_t lasso_sumcheck_cubic_round(lasso_ctx* c, const lasso_fr* const* d_A, con
   int32_t rc = ensure_small(c, (size_t)ncirc * 3); if (rc) return rc;
   const uint32_t seq = next_seq(c);
   PtrTable A, B; for (uint32_t i = 0; i < ncirc; i++) { REQUIRE(c, d_A[i] && d_B[i]); A.p[i] = (const fr_t*)d_A[i]; B.p[i] = (const fr_t*)d_B[i]; }
-  const unsigned ny = ncirc, nx = grid_for(half, cubic_nx_cap(ny));
+  const unsigned ny = ncirc, nx = round_nx(half, ny);
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   {
     ProfScope ps(c, LASSO_K_CUBIC, 32.0 * n * (2.0 * ncirc + 1.0));
@@ -643,108 +640,85 @@ int32_t lasso_sumcheck_cubic_round(lasso_ctx* c, const lasso_fr* const* d_A, con
 // previous challenge is bound first (length n -> n/2) and the sums are those of the next round.  NT sums per circuit land in the mapped
 // result buffer under sequence number *seq_out.
 // eqi (first round of a layer, two-sum form, streaming size only): the layer's eq table is built inside the launch and WRITTEN to d_E (k_cubic_eqw_lb<2, true>)
-// a launch of a few workgroups per circuit hands over EVERY workgroup's block sums (LASSO_TAGGED_DIRECT; the host adds them in wait_flag) instead of running the in-launch second stage
-static unsigned direct_nx_max() { static const unsigned v = [] { const char* e = getenv("LASSO_DIRECT_NX"); const long x = e ? atol(e) : 16; return (unsigned)(x < 0 ? 0 : x > 64 ? 64 : x); }(); return v; }
-#define CUBIC_RESULT_ARGS(nx_) \
-  const bool direct = groups_out && c->tagged && (nx_) > 1 && (nx_) <= direct_nx_max(); \
-  if (direct) { *groups_out = (nx_); rc = ensure_small(c, (size_t)ncirc * 3 * (nx_)); if (rc) return rc; } \
-  fr_t* const r_out = c->tagged ? (fr_t*)c->d_tag : c->d_small; uint32_t* const r_flag = direct ? LASSO_TAGGED_DIRECT : c->tagged ? LASSO_TAGGED : c->d_flag
+// a launch of a few workgroups per circuit hands over EVERY workgroup's block sums (LASSO_TAGGED_DIRECT; the host adds them in wait_flag) instead of running the in-launch second stage: CubicPlan::direct
 extern "C++" {
 struct EqPointArg { const lasso_fr* point; uint32_t ell; fr_t scale; };   // a table too large for the in-LDS build: factor tables by k_eq_small2 into the scratch, the product inside round 0 (EqGlobal)
+static CubicPlan cubic_plan_for(lasso_ctx* c, uint32_t ncirc, size_t n, bool has_r, int NT, bool has_eqi, bool want_groups, bool ahead, const EqPointArg* eqg, int gate_ell) {
+  const CubicShape s = {n, ncirc, NT, ahead, has_r, has_eqi, eqg != nullptr, eqg ? eqg->ell : 0u, gate_ell, c->prof_mask, want_groups && c->tagged};
+  const CubicSwitches sw = {dsw::cubic_nx(), dsw::cubic_wide(), dsw::direct_nx(), dsw::eq_inline_big(), dsw::lb_pipeline(), dsw::lb_nt(), dsw::ahead_inkernel_wgs()};
+  return cubic_plan(s, sw);
+}
 template <class TM, class TP>   // pointer tables sized for the number of circuits (MutPtrTable8 / PtrTable8 up to 8: 64 bytes of kernel arguments each instead of 1088)
 static int32_t cubic_eqw_launch_t(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n, const lasso_fr* r, int NT, uint32_t* seq_out, const EqInline* eqi, uint32_t* groups_out, bool ahead = false, const EqPointArg* eqg = nullptr, int gate_ell = -1) {
   if (groups_out) *groups_out = 1;
-  if (ahead && (NT != 2 || n / 4 <= CUBIC_SMALL_Q)) return fail(c, LASSO_ERR_UNSUPPORTED, "a round launched ahead of its challenge: two-sum streaming rounds only (more than 64 index quadruples per circuit)");
+  const CubicPlan P = cubic_plan_for(c, ncirc, n, r != nullptr, NT, eqi != nullptr, groups_out != nullptr, ahead, eqg, gate_ell);
+  if (P.form == CUBIC_REFUSED) return fail(c, LASSO_ERR_UNSUPPORTED, P.refusal);
   TM A, B; for (uint32_t i = 0; i < ncirc; i++) { REQUIRE(c, d_A[i] && d_B[i]); A.p[i] = (fr_t*)d_A[i]; B.p[i] = (fr_t*)d_B[i]; }
   int32_t rc = ensure_small(c, (size_t)ncirc * 3); if (rc) return rc;
   const uint32_t seq = next_seq(c); *seq_out = seq;
-  if (!r && !ahead) {
-    const size_t half = n / 2;
-    if (half <= CUBIC_SMALL_Q) {   // arrays are read-only in this mode
-      ProfScope ps(c, LASSO_K_CUBIC, 32.0 * n * (2.0 * ncirc + 1.0));
-      if (NT == 3) hipLaunchKernelGGL((k_cubic_eqw_small<false, 3, TM>), dim3(ncirc), dim3(LASSO_BLOCK), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)half, fr_zero(), c->d_counters, RES(c), seq);
-      else hipLaunchKernelGGL((k_cubic_eqw_small<false, 2, TM>), dim3(ncirc), dim3(LASSO_BLOCK), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)half, fr_zero(), c->d_counters, RES(c), seq);
-    } else {
-      TP Ac, Bc; for (uint32_t i = 0; i < ncirc; i++) { Ac.p[i] = A.p[i]; Bc.p[i] = B.p[i]; }
-      const unsigned ny = ncirc, nx = grid_for(half, cubic_nx_cap(ny));
-      static const bool big_inline = [] { const char* v = getenv("LASSO_EQ_INLINE_BIG"); return v && v[0] == '1'; }();   // A/B switch: tables above 2^14 entries formed inside round 0 (EqGlobal) instead of by k_eq_outer in front of it
-      const bool gated = gate_ell >= 0, gbig = gated && gate_ell > 14;   // the point comes through the gate (the layer is enqueued ahead of it); above 2^14 entries with factor tables in memory
-      const uint32_t g_ell = gbig ? (uint32_t)gate_ell : eqg ? eqg->ell : 0, g_lo = g_ell / 2, g_hi = g_ell - g_lo;
-      const size_t part_elems = (size_t)nx * ny * 3;
-      rc = ensure_scratch(c, (part_elems + ((eqg || gbig) ? ((size_t)1 << g_hi) + ((size_t)1 << g_lo) : 0)) * sizeof(fr_t)); if (rc) return rc;
-      CUBIC_RESULT_ARGS(nx);
-      static const uint32_t pipe = [] { const char* v = getenv("LASSO_LB_PIPELINE"); return (v && v[0] == '0') ? 0u : 1u; }();
-      // what runs in front of the round is outside the round's profiling bracket: the wait for the point (one wave), the two factor tables (their own bracket)
-      fr_t* const f_hi = (fr_t*)c->d_scratch + part_elems; fr_t* const f_lo = f_hi + ((size_t)1 << g_hi);
-      if (gated && NT == 2) hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); if (gated && NT == 2) c->proto.gate_sent = seq;
-      const uint32_t* const gate_gp = gated ? (const uint32_t*)c->d_gpoint : (const uint32_t*)nullptr;
-      if ((gbig || eqg) && NT == 2) {
-        ProfScope pe(c, LASSO_K_EQ, big_inline ? 32.0 * (((size_t)1 << g_hi) + ((size_t)1 << g_lo)) : 32.0 * half);
-        const unsigned hb = grid_for((size_t)1 << g_hi), lb2 = grid_for((size_t)1 << g_lo);
-        if (gbig) hipLaunchKernelGGL(k_eq_small2_mem, dim3(hb + lb2), dim3(LASSO_BLOCK), 0, c->stream, (const uint32_t*)c->d_gpoint, seq, g_hi, f_hi, hb, g_lo, f_lo);
-        else {
-          RTable16 Rh, Rl; for (uint32_t j = 0; j < 16; j++) { Rh.r[j] = j < g_hi ? to_fr(eqg->point + j) : fr_zero(); Rl.r[j] = j < g_lo ? to_fr(eqg->point + g_hi + j) : fr_zero(); }
-          hipLaunchKernelGGL(k_eq_small2, dim3(hb + lb2), dim3(LASSO_BLOCK), 0, c->stream, Rh, g_hi, eqg->scale, f_hi, hb, Rl, g_lo, f_lo);
-        }
-        if (!big_inline) hipLaunchKernelGGL(k_eq_outer, dim3(grid_for(half, 4096)), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)f_hi, (const fr_t*)f_lo, g_lo, half, (fr_t*)d_E, gate_gp, seq);   // the table itself, as lasso_eq_evals_scaled writes it
-      }
-      ProfScope ps(c, LASSO_K_CUBIC, 32.0 * n * (2.0 * ncirc + 1.0));
-      if ((gbig || eqg) && NT == 2 && !big_inline) {   // round 0 reads the table the kernels above left in d_E
-        EqNone EN; EN.ell = 0; EN.gp = gate_gp; EN.seq = seq;
-        hipLaunchKernelGGL((k_cubic_eqw_lb<2, false, TP, EqNone>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)d_E, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, pipe, EN, (fr_t*)nullptr);
-      } else
-      if (gated && NT == 2) {
-        if (gbig) {
-          fr_t* hi = f_hi; fr_t* lo = f_lo;
-          EqGlobal G; G.hi = hi; G.lo = lo; G.lo_bits = g_lo; G.ell = g_ell; G.gp = c->d_gpoint; G.seq = seq;
-          hipLaunchKernelGGL((k_cubic_eqw_lb<2, true, TP, EqGlobal>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)nullptr, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, 1u, G, (fr_t*)d_E);
-        } else {
-          EqInlineMem M; M.gp = c->d_gpoint; M.seq = seq; M.ell = (uint32_t)gate_ell;
-          hipLaunchKernelGGL((k_cubic_eqw_lb<2, true, TP, EqInlineMem>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)nullptr, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, 1u, M, (fr_t*)d_E);
-        }
-      } else
-      if (eqg && NT == 2) {   // factor tables behind the partials in the scratch (above), then round 0 with the product inside (the table goes to d_E on the way)
-        fr_t* hi = f_hi; fr_t* lo = f_lo;
-        EqGlobal G; G.hi = hi; G.lo = lo; G.lo_bits = g_lo; G.ell = eqg->ell; G.gp = nullptr; G.seq = 0;
-        hipLaunchKernelGGL((k_cubic_eqw_lb<2, true, TP, EqGlobal>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)nullptr, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, 1u, G, (fr_t*)d_E);
-      } else
-      if (NT == 3) hipLaunchKernelGGL((k_cubic_eqw_lb<3, false, TP, EqNone>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)d_E, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, 0u, EqNone(), (fr_t*)nullptr);
-      else if (eqi) hipLaunchKernelGGL((k_cubic_eqw_lb<2, true, TP, EqInline>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)nullptr, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, 1u, *eqi, (fr_t*)d_E);
-      else {
-        static const bool lb_nt = [] { const char* v = getenv("LASSO_LB_NT"); return v && v[0] == '1'; }();   // A/B switch: non-temporal loads of A and B in the evaluation-only round
-        if (lb_nt && pipe) hipLaunchKernelGGL((k_cubic_eqw_lb<2, false, TP, EqNone, true>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)d_E, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, pipe, EqNone(), (fr_t*)nullptr);
-        else hipLaunchKernelGGL((k_cubic_eqw_lb<2, false, TP, EqNone>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)d_E, half, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, pipe, EqNone(), (fr_t*)nullptr);
-      }
-    }
-  } else if (ahead) {
-    const size_t q = n / 4;
-    const unsigned ny = ncirc, nx = grid_for(q, cubic_nx_cap(ny));
-    rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
-    CUBIC_RESULT_ARGS(nx);
-    // where the wait lives: in a one-wave gate kernel in front of the round (many workgroups), or in the round's own kernel (few: the gate's second launch costs the host more
-    // than a handful of spinning workgroups cost the device — profiles/r05_ahead_wait_forms.txt).  LASSO_AHEAD_INKERNEL_WGS: the bound (default 32; 0 = always the gate)
-    static const unsigned inkernel_max = [] { const char* v = getenv("LASSO_AHEAD_INKERNEL_WGS"); const long x = v ? atol(v) : 32; return (unsigned)(x < 0 ? 0 : x > 4096 ? 4096 : x); }();
-    const bool bracketed = ((c->prof_mask >> LASSO_K_CUBIC) & 1u) && !(c->prof_mask & 0x40000000u);   // every launch of the family is between profiling events: the wait must not be inside them -> always the gate
-    const bool inkernel = nx * ny <= inkernel_max && !bracketed;
-    const uint32_t* wait_mail = inkernel ? (const uint32_t*)c->mail_d : (const uint32_t*)nullptr;
-    if (!inkernel) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->mail_d, c->d_gmail, seq, 0u);   // the wait: one wave; the round starts when it ends
-    ProfScope ps(c, LASSO_K_CUBIC, 48.0 * n * (2.0 * ncirc + 1.0));   // the events bracket the round's kernel, not the gate's wait for the host
-    if (cubic_wide()) hipLaunchKernelGGL((k_cubic_eqw_fused<2, true, TM, true>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, q, fr_zero(), (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, (const uint32_t*)c->d_gmail, wait_mail);
-    else hipLaunchKernelGGL((k_cubic_eqw_fused<2, false, TM, true>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, q, fr_zero(), (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, (const uint32_t*)c->d_gmail, wait_mail);
+  const unsigned nx = P.nx, ny = P.ny;
+  const fr_t rr = r ? to_fr(r) : fr_zero();
+  // evaluation only: 32n per polynomial; with the bind: read 32n + write 16n (SURVEY.md §8d's "fused bind+next-eval" over the reference's 2*ncirc + 1 polynomials)
+  const double bytes = (P.bind ? 48.0 : 32.0) * n * (2.0 * ncirc + 1.0);
+  // the streaming forms: block partials (and factor tables) in the scratch; the result area, with room for every workgroup's block sums where they go out direct
+  fr_t* r_out = nullptr; uint32_t* r_flag = nullptr;
+  auto reserve = [&]() -> int32_t {
+    int32_t e = ensure_scratch(c, P.scratch_elems * sizeof(fr_t)); if (e) return e;
+    if (P.direct) { *groups_out = nx; e = ensure_small(c, (size_t)ncirc * 3 * nx); if (e) return e; }
+    r_out = c->tagged ? (fr_t*)c->d_tag : c->d_small; r_flag = P.direct ? LASSO_TAGGED_DIRECT : c->tagged ? LASSO_TAGGED : c->d_flag;
+    return 0;
+  };
+  if (P.form == CUBIC_SMALL) {   // arrays are read-only without the bind
+    ProfScope ps(c, LASSO_K_CUBIC, bytes);
+#define LAUNCH_CSMALL(BIND_, NT_) hipLaunchKernelGGL((k_cubic_eqw_small<BIND_, NT_, TM>), dim3(ncirc), dim3(LASSO_BLOCK), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)P.items, rr, c->d_counters, RES(c), seq)
+    if (P.bind) { if (NT == 3) LAUNCH_CSMALL(true, 3); else LAUNCH_CSMALL(true, 2); }
+    else { if (NT == 3) LAUNCH_CSMALL(false, 3); else LAUNCH_CSMALL(false, 2); }
+  } else if (P.form == CUBIC_FUSED) {
+    // a round launched ahead: where the wait lives — in a one-wave gate kernel in front of the round (many workgroups), or in the round's own kernel (few: the gate's second launch
+    // costs the host more than a handful of spinning workgroups cost the device — profiles/r05_ahead_wait_forms.txt).  The events bracket the round's kernel, not the gate's wait for the host
+    if (ahead) { if ((rc = reserve())) return rc; if (P.gate) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->mail_d, c->d_gmail, seq, 0u); }
+    ProfScope ps(c, LASSO_K_CUBIC, bytes);
+    if (!ahead && (rc = reserve())) return rc;
+    const uint32_t* const gmail = ahead ? (const uint32_t*)c->d_gmail : (const uint32_t*)nullptr; const uint32_t* const wait_mail = P.inkernel ? (const uint32_t*)c->mail_d : (const uint32_t*)nullptr;
+#define LAUNCH_CFUSED(NT_, WIDE_, AHEAD_) hipLaunchKernelGGL((k_cubic_eqw_fused<NT_, WIDE_, TM, AHEAD_>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, P.items, rr, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, gmail, wait_mail)
+    if (ahead) { if (P.wide) LAUNCH_CFUSED(2, true, true); else LAUNCH_CFUSED(2, false, true); }
+    else if (NT == 3) LAUNCH_CFUSED(3, false, false);
+    else if (P.wide) LAUNCH_CFUSED(2, true, false);
+    else LAUNCH_CFUSED(2, false, false);
   } else {
-    const size_t q = n / 4;
-    // bind: read 32n + write 16n per polynomial (SURVEY.md §8d's "fused bind+next-eval" over the reference's 2*ncirc + 1 polynomials)
-    ProfScope ps(c, LASSO_K_CUBIC, 48.0 * n * (2.0 * ncirc + 1.0));
-    if (q <= CUBIC_SMALL_Q) {
-      if (NT == 3) hipLaunchKernelGGL((k_cubic_eqw_small<true, 3, TM>), dim3(ncirc), dim3(LASSO_BLOCK), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)q, to_fr(r), c->d_counters, RES(c), seq);
-      else hipLaunchKernelGGL((k_cubic_eqw_small<true, 2, TM>), dim3(ncirc), dim3(LASSO_BLOCK), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)q, to_fr(r), c->d_counters, RES(c), seq);
-    } else {
-      const unsigned ny = ncirc, nx = grid_for(q, cubic_nx_cap(ny));
-      rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
-      CUBIC_RESULT_ARGS(nx);
-      if (NT == 3) hipLaunchKernelGGL((k_cubic_eqw_fused<3, false, TM>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, q, to_fr(r), (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq);
-      else if (cubic_wide()) hipLaunchKernelGGL((k_cubic_eqw_fused<2, true, TM>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, q, to_fr(r), (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq);
-      else hipLaunchKernelGGL((k_cubic_eqw_fused<2, false, TM>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, A, B, nx, ny, (const fr_t*)d_E, q, to_fr(r), (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq);
+    const CubicLbPlan& L = P.lb;
+    TP Ac, Bc; for (uint32_t i = 0; i < ncirc; i++) { Ac.p[i] = A.p[i]; Bc.p[i] = B.p[i]; }
+    if ((rc = reserve())) return rc;
+    // what runs in front of the round is outside the round's profiling bracket: the wait for the point (one wave), the two factor tables (their own bracket)
+    fr_t* const f_hi = (fr_t*)c->d_scratch + P.part_elems; fr_t* const f_lo = f_hi + ((size_t)1 << L.g_hi);
+    if (L.gate) { hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); c->proto.gate_sent = seq; }
+    const uint32_t* const gate_gp = L.gate ? (const uint32_t*)c->d_gpoint : (const uint32_t*)nullptr;
+    if (L.factors) {
+      ProfScope pe(c, LASSO_K_EQ, L.eq_outer ? 32.0 * P.items : 32.0 * (((size_t)1 << L.g_hi) + ((size_t)1 << L.g_lo)));
+      const unsigned hb = grid_for((size_t)1 << L.g_hi), lb2 = grid_for((size_t)1 << L.g_lo);
+      if (L.factors_gated) hipLaunchKernelGGL(k_eq_small2_mem, dim3(hb + lb2), dim3(LASSO_BLOCK), 0, c->stream, (const uint32_t*)c->d_gpoint, seq, L.g_hi, f_hi, hb, L.g_lo, f_lo);
+      else {
+        RTable16 Rh, Rl; for (uint32_t j = 0; j < 16; j++) { Rh.r[j] = j < L.g_hi ? to_fr(eqg->point + j) : fr_zero(); Rl.r[j] = j < L.g_lo ? to_fr(eqg->point + L.g_hi + j) : fr_zero(); }
+        hipLaunchKernelGGL(k_eq_small2, dim3(hb + lb2), dim3(LASSO_BLOCK), 0, c->stream, Rh, L.g_hi, eqg->scale, f_hi, hb, Rl, L.g_lo, f_lo);
+      }
+      if (L.eq_outer) hipLaunchKernelGGL(k_eq_outer, dim3(grid_for(P.items, 4096)), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)f_hi, (const fr_t*)f_lo, L.g_lo, P.items, (fr_t*)d_E, gate_gp, seq);   // the table itself, as lasso_eq_evals_scaled writes it
+    }
+    ProfScope ps(c, LASSO_K_CUBIC, bytes);
+    // E_: the table the round reads; EQ_: the point it builds its table from instead, written to OUT_ on the way
+#define LAUNCH_CLB(NT_, EQI_, TE_, NTL_, E_, EQ_, OUT_) hipLaunchKernelGGL((k_cubic_eqw_lb<NT_, EQI_, TP, TE_, NTL_>), dim3(nx * ny), dim3(LASSO_BLOCK), 0, c->stream, Ac, Bc, nx, ny, (const fr_t*)(E_), P.items, (fr_t*)c->d_scratch, c->d_counters, r_out, r_flag, seq, L.pipe, EQ_, (fr_t*)(OUT_))
+    switch (L.eq) {
+      case CUBIC_EQ_TABLE: {
+        EqNone EN; if (L.eq_outer) { EN.gp = gate_gp; EN.seq = seq; }   // round 0 reads the table the kernels above left in d_E
+        if (NT == 3) LAUNCH_CLB(3, false, EqNone, false, d_E, EN, nullptr);
+        else if (L.nt) LAUNCH_CLB(2, false, EqNone, true, d_E, EN, nullptr);
+        else LAUNCH_CLB(2, false, EqNone, false, d_E, EN, nullptr);
+      } break;
+      case CUBIC_EQ_LDS: LAUNCH_CLB(2, true, EqInline, false, nullptr, *eqi, d_E); break;
+      case CUBIC_EQ_GATED: { EqInlineMem M; M.gp = c->d_gpoint; M.seq = seq; M.ell = (uint32_t)gate_ell; LAUNCH_CLB(2, true, EqInlineMem, false, nullptr, M, d_E); } break;
+      case CUBIC_EQ_FACTORS: {   // factor tables behind the partials in the scratch (above), then round 0 with the product inside (the table goes to d_E on the way)
+        EqGlobal G; G.hi = f_hi; G.lo = f_lo; G.lo_bits = L.g_lo; G.ell = L.g_ell; G.gp = L.gate ? c->d_gpoint : nullptr; G.seq = L.gate ? seq : 0;
+        LAUNCH_CLB(2, true, EqGlobal, false, nullptr, G, d_E);
+      } break;
     }
   }
   HIPCHK(c, hipGetLastError());
@@ -777,9 +751,10 @@ int32_t lasso_sumcheck_cubic_eqw2_begin(lasso_ctx* c, lasso_fr* const* d_A, lass
 // the ordinary round once it has the challenge).
 int32_t lasso_sumcheck_cubic_eqw2_begin_ahead(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n) {
   REQUIRE(c, d_A && d_B && d_E && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->proto.ahead_active && !c->proto.tail_active && !c->proto.defer_next);
-  if (n / 4 <= CUBIC_SMALL_Q) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_ahead: streaming rounds only");
+  const CubicPlan P = cubic_plan_for(c, ncirc, n, false, 2, false, true, true, nullptr, -1);   // the plan the launch below follows
+  if (P.form == CUBIC_REFUSED) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_ahead: streaming rounds only");
   // everything that could synchronise the stream happens here, BEFORE the launch that waits
-  { const unsigned nx = grid_for(n / 4, cubic_nx_cap(ncirc)); int32_t rc0 = ensure_small(c, (size_t)ncirc * 3 * (nx <= direct_nx_max() ? nx : 1)); if (rc0) return rc0; rc0 = ensure_scratch(c, (size_t)nx * ncirc * 3 * sizeof(fr_t)); if (rc0) return rc0; }
+  { int32_t rc0 = ensure_small(c, (size_t)ncirc * 3 * (P.direct ? P.nx : 1)); if (rc0) return rc0; rc0 = ensure_scratch(c, P.scratch_elems * sizeof(fr_t)); if (rc0) return rc0; }
   uint32_t seq, groups; int32_t rc = cubic_eqw_launch(c, d_A, d_B, ncirc, d_E, n, nullptr, 2, &seq, nullptr, &groups, true); if (rc) return rc;
   c->proto.arm_ahead(Handoff{seq, (size_t)ncirc * 2, c->tagged, groups, 2}, false);
   return 0;
@@ -791,7 +766,7 @@ int32_t lasso_challenge_post(lasso_ctx* c, const lasso_fr* r) {
   return 0;
 }
 // 1 when rounds may be launched ahead on this context (LASSO_ROUNDS_AHEAD=0: A/B switch)
-int32_t lasso_rounds_ahead_ok(lasso_ctx* c) { static const bool off = [] { const char* v = getenv("LASSO_ROUNDS_AHEAD"); return v && v[0] == '0'; }(); return c && !off && c->mail_d && c->d_gmail ? 1 : 0; }
+int32_t lasso_rounds_ahead_ok(lasso_ctx* c) { return c && dsw::rounds_ahead() && c->mail_d && c->d_gmail ? 1 : 0; }
 // The next entry point that hands its result over through the mapped buffer (the sumcheck rounds, the few-row MSMs, lasso_bullet_round ...)
 // returns right after its launch; its `out` argument is ignored and lasso_result_wait(ctx, out, count) delivers the same values
 // (count in field-element units: a point is 4).  Lets the host absorb transcript data or do scalar work while the device computes.
@@ -847,18 +822,18 @@ static int32_t cubic_tail_begin_t(lasso_ctx* c, uint32_t m_stop_arg, lasso_fr* c
   int32_t rc = ensure_small(c, (size_t)ncirc * 2 * (m_stop > 2 ? m_stop : 2)); if (rc) return rc;
   uint32_t turns = 0; while (((size_t)m_stop << turns) < 2 * q) turns++;   // rounds of sums; one more publication carries the heads (or the arrays of m_stop elements)
   const uint32_t seq0 = next_seq(c, turns + 1);
-  // workgroup = capacity: 256 threads / 74 KB of LDS up to 256 indices per circuit, 512 threads / 147 KB above
+  // workgroup = capacity (tail_threads)
 #define LAUNCH_CTAIL(B_, Q_, I_, TE_, R_, EQ_) hipLaunchKernelGGL((k_cubic_tail<B_, Q_, I_, TM, TE_>), dim3(ncirc), dim3(Q_), 0, c->stream, A, B, (const fr_t*)d_E, (uint32_t)q, R_, (const uint32_t*)c->mail_d, c->d_counters, RES(c), seq0, EQ_, m_stop, ahead ? 1u : 0u)
   if (gated) {
     hipLaunchKernelGGL(k_gate_point, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->pmail_d, c->d_gpoint, seq0, (uint32_t)gate_ell + 2u, c->pmail_d + LASSO_PMAIL_ACK_WORD); c->proto.gate_sent = seq0;
     EqInlineMem M; M.gp = c->d_gpoint; M.seq = seq0; M.ell = (uint32_t)gate_ell;
-    if (q <= 256) LAUNCH_CTAIL(false, 256, true, EqInlineMem, fr_zero(), M); else LAUNCH_CTAIL(false, 512, true, EqInlineMem, fr_zero(), M);
+    if (tail_threads(q) == 256) LAUNCH_CTAIL(false, 256, true, EqInlineMem, fr_zero(), M); else LAUNCH_CTAIL(false, 512, true, EqInlineMem, fr_zero(), M);
     HIPCHK(c, hipGetLastError());
     c->proto.arm_layer_tail(Handoff{seq0, (size_t)ncirc * 2, c->tagged}, (uint32_t)gate_ell, turns, (size_t)ncirc * 2 * m_stop);
     return 0;   // the tail state of the context still belongs to the previous layer: lasso_point_post installs this one
   }
-  if (eqi) { if (q <= 256) LAUNCH_CTAIL(false, 256, true, EqInline, fr_zero(), *eqi); else LAUNCH_CTAIL(false, 512, true, EqInline, fr_zero(), *eqi); }
-  else if (q <= 256) { if (r || ahead) LAUNCH_CTAIL(true, 256, false, EqNone, r ? to_fr(r) : fr_zero(), EqNone()); else LAUNCH_CTAIL(false, 256, false, EqNone, fr_zero(), EqNone()); }
+  if (eqi) { if (tail_threads(q) == 256) LAUNCH_CTAIL(false, 256, true, EqInline, fr_zero(), *eqi); else LAUNCH_CTAIL(false, 512, true, EqInline, fr_zero(), *eqi); }
+  else if (tail_threads(q) == 256) { if (r || ahead) LAUNCH_CTAIL(true, 256, false, EqNone, r ? to_fr(r) : fr_zero(), EqNone()); else LAUNCH_CTAIL(false, 256, false, EqNone, fr_zero(), EqNone()); }
   else { if (r || ahead) LAUNCH_CTAIL(true, 512, false, EqNone, r ? to_fr(r) : fr_zero(), EqNone()); else LAUNCH_CTAIL(false, 512, false, EqNone, fr_zero(), EqNone()); }
   HIPCHK(c, hipGetLastError());
   c->proto.begin_tail(Handoff{seq0, (size_t)ncirc * 2, c->tagged}, turns, (size_t)ncirc * 2 * m_stop, ahead);   // ahead: nothing is pending until the first challenge has been posted (lasso_sumcheck_cubic_tail_next)
@@ -879,7 +854,7 @@ static int32_t cubic_tail_begin_impl(lasso_ctx* c, uint32_t m_stop, lasso_fr* co
 // post / cancel would overwrite a message that gate has not read yet, and the gate would spin to its 5 s bail-out.  prover.hpp never gets here with a gate in
 // flight (a layer's first result is collected before the next one is enqueued); the entry points enforce it for every other caller: LASSO_ERR_UNSUPPORTED = take the plain path.
 static bool gate_free(lasso_ctx* c) { return !c->proto.gate_sent || __atomic_load_n(c->pmail_h + LASSO_PMAIL_ACK_WORD, __ATOMIC_ACQUIRE) == c->proto.gate_sent; }
-int32_t lasso_layer_ahead_ok(lasso_ctx* c) { static const bool off = [] { const char* v = getenv("LASSO_LAYER_AHEAD"); return v && v[0] == '0'; }(); return c && !off && c->pmail_d && c->d_gpoint ? 1 : 0; }
+int32_t lasso_layer_ahead_ok(lasso_ctx* c) { return c && dsw::layer_ahead() && c->pmail_d && c->d_gpoint ? 1 : 0; }
 int32_t lasso_sumcheck_cubic_eqw2_begin_eq_ahead(lasso_ctx* c, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, lasso_fr* d_E_out, size_t n, uint32_t ell) {
   REQUIRE(c, d_A && d_B && d_E_out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0 && ell < 48 && ((size_t)1 << ell) == n / 2 && !c->proto.waiting_on_device() && !c->proto.defer_next);
   if (!lasso_layer_ahead_ok(c) || n / 2 <= CUBIC_SMALL_Q || ell > 32 || ell > LASSO_POINT_MAX) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_sumcheck_cubic_eqw2_begin_eq_ahead: tables of 2^7 .. 2^32 entries only");
@@ -954,7 +929,7 @@ int32_t lasso_sumcheck_linear_tail_begin(lasso_ctx* c, const lasso_fr* const* d_
   uint32_t turns = 0; while (((size_t)1 << turns) < 2 * q) turns++;
   const uint32_t seq0 = next_seq(c, turns + 1);
 #define LAUNCH_LTAIL(B_, Q_, R_) hipLaunchKernelGGL((k_linear_tail<B_, Q_>), dim3(alpha), dim3(Q_), 0, c->stream, Src, (const fr_t*)d_E, (uint32_t)q, R_, (const uint32_t*)c->mail_d, c->d_counters, RES(c), seq0)
-  if (q <= 256) { if (r) LAUNCH_LTAIL(true, 256, to_fr(r)); else LAUNCH_LTAIL(false, 256, fr_zero()); }
+  if (tail_threads(q) == 256) { if (r) LAUNCH_LTAIL(true, 256, to_fr(r)); else LAUNCH_LTAIL(false, 256, fr_zero()); }
   else { if (r) LAUNCH_LTAIL(true, 512, to_fr(r)); else LAUNCH_LTAIL(false, 512, fr_zero()); }
   HIPCHK(c, hipGetLastError());
   c->proto.begin_tail(Handoff{seq0, (size_t)alpha * 2, c->tagged}, turns, alpha, false);
@@ -967,7 +942,7 @@ int32_t lasso_sumcheck_cubic_tail_next(lasso_ctx* c, const lasso_fr* r) {
   return 0;
 }
 // largest q (indices per circuit / polynomial) lasso_sumcheck_{cubic,linear}_tail_begin accept; LASSO_TAIL_Q=256 restores round 2's capacity (A/B measurements)
-uint32_t lasso_sumcheck_tail_capacity(void) { static const uint32_t q = [] { const char* v = getenv("LASSO_TAIL_Q"); const long x = v ? atol(v) : 0; return (uint32_t)(x == 256 ? 256 : CUBIC_TAIL_Q); }(); return q; }
+uint32_t lasso_sumcheck_tail_capacity(void) { return dsw::tail_q_256() ? 256 : CUBIC_TAIL_Q; }
 int32_t lasso_defer_next(lasso_ctx* c) { REQUIRE(c, !c->proto.pending && !c->proto.defer_next); c->proto.defer_next = true; return 0; }
 int32_t lasso_result_wait(lasso_ctx* c, lasso_fr* out, size_t count) {
   REQUIRE(c, out && c->proto.pending && count == c->proto.result.count);
@@ -978,7 +953,7 @@ int32_t lasso_result_wait(lasso_ctx* c, lasso_fr* out, size_t count) {
 int32_t lasso_sumcheck_linear_eqw_round(lasso_ctx* c, const lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n, lasso_fr* out) {
   REQUIRE(c, d_polys && d_E && out && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0);
   PtrTable P; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const size_t half = n / 2; const unsigned ny = alpha, nx = grid_for(half, cubic_nx_cap(ny));
+  const size_t half = n / 2; const unsigned ny = alpha, nx = round_nx(half, ny);
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   const uint32_t seq = next_seq(c);
@@ -995,7 +970,7 @@ int32_t lasso_sumcheck_linear_eqw_round_fused(lasso_ctx* c, lasso_fr* const* d_p
 int32_t lasso_sumcheck_linear_eqw_round_fused_from(lasso_ctx* c, const lasso_fr* const* d_src, lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n, const lasso_fr* r, lasso_fr* out) {
   REQUIRE(c, d_src && d_polys && d_E && r && out && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0);
   MutPtrTable P; PtrTable Src; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_polys[i] && d_src[i]); P.p[i] = (fr_t*)d_polys[i]; Src.p[i] = (const fr_t*)d_src[i]; }
-  const size_t q = n / 4; const unsigned ny = alpha, nx = grid_for(q, cubic_nx_cap(ny));
+  const size_t q = n / 4; const unsigned ny = alpha, nx = round_nx(q, ny);
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   const uint32_t seq = next_seq(c);
@@ -1012,7 +987,7 @@ int32_t lasso_sumcheck_linear_eqw_round_fused_from(lasso_ctx* c, const lasso_fr*
 int32_t lasso_sumcheck_linear_eqw_round_fused_ahead(lasso_ctx* c, lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n) {
   REQUIRE(c, d_polys && d_E && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0 && !c->proto.ahead_active && !c->proto.tail_active && !c->proto.defer_next);
   MutPtrTable P; PtrTable Src; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (fr_t*)d_polys[i]; Src.p[i] = (const fr_t*)d_polys[i]; }
-  const size_t q = n / 4; const unsigned ny = alpha, nx = grid_for(q, cubic_nx_cap(ny));
+  const size_t q = n / 4; const unsigned ny = alpha, nx = round_nx(q, ny);
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   const uint32_t seq = next_seq(c);
@@ -1029,7 +1004,7 @@ int32_t lasso_sumcheck_linear_eqw_round_fused_ahead(lasso_ctx* c, lasso_fr* cons
 int32_t lasso_sumcheck_linear_eqw_round_u32(lasso_ctx* c, const uint32_t* const* d_u32, uint32_t alpha, const lasso_fr* d_E, size_t n, lasso_fr* out) {
   REQUIRE(c, d_u32 && d_E && out && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0);
   PtrTableU32 P; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_u32[i]); P.p[i] = d_u32[i]; }
-  const size_t half = n / 2; const unsigned ny = alpha, nx = grid_for(half, cubic_nx_cap(ny));
+  const size_t half = n / 2; const unsigned ny = alpha, nx = round_nx(half, ny);
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   const uint32_t seq = next_seq(c);
@@ -1043,7 +1018,7 @@ int32_t lasso_sumcheck_linear_eqw_round_u32(lasso_ctx* c, const uint32_t* const*
 int32_t lasso_sumcheck_linear_eqw_round_fused_from_u32(lasso_ctx* c, const uint32_t* const* d_u32, lasso_fr* const* d_polys, uint32_t alpha, const lasso_fr* d_E, size_t n, const lasso_fr* r, lasso_fr* out) {
   REQUIRE(c, d_u32 && d_polys && d_E && r && out && alpha >= 1 && alpha <= LASSO_MAX_PTRS && n >= 4 && (n & (n - 1)) == 0);
   MutPtrTable P; PtrTableU32 Src; for (uint32_t i = 0; i < alpha; i++) { REQUIRE(c, d_polys[i] && d_u32[i]); P.p[i] = (fr_t*)d_polys[i]; Src.p[i] = d_u32[i]; }
-  const size_t q = n / 4; const unsigned ny = alpha, nx = grid_for(q, cubic_nx_cap(ny));
+  const size_t q = n / 4; const unsigned ny = alpha, nx = round_nx(q, ny);
   int32_t rc = ensure_small(c, (size_t)alpha * 3); if (rc) return rc;
   rc = ensure_scratch(c, (size_t)nx * ny * 3 * sizeof(fr_t)); if (rc) return rc;
   const uint32_t seq = next_seq(c);
@@ -1298,7 +1273,7 @@ int32_t lasso_fingerprint_ops_gp(lasso_ctx* c, const lasso_fr* d_table, const ui
   {
     ProfScope ps(c, LASSO_K_FINGERPRINT, (32.0 * 3 + 64.0) * s + 2 * 48.0 * s);   // the fingerprints + the first layer of two trees (48 n per layer)
     // LASSO_EXP_NO_LEAF_STORE=1: TIMING EXPERIMENT ONLY (the proof that follows is invalid): the kernel without its 2 x 32 s bytes of leaf stores = what "compact leaves" would leave of it
-    static const uint32_t store_leaves = [] { const char* v = getenv("LASSO_EXP_NO_LEAF_STORE"); return (v && v[0] == '1') ? 0u : 1u; }();
+    const uint32_t store_leaves = dsw::exp_no_leaf_store() ? 0u : 1u;
     hipLaunchKernelGGL(k_fingerprint_ops_l1<false>, dim3(grid_for(s / 2, 4096)), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)d_table, d_dim, (const void*)d_read, s, g, g2, t, tr, tw, tr + s, tw + s, store_leaves);
   }
   {
@@ -1516,8 +1491,7 @@ int32_t lasso_bases_create_opt(lasso_ctx* c, const lasso_affine* points, size_t 
   if (e != hipSuccess) { (void)dfree(c, b->d_table); delete b; return fail(c, LASSO_ERR_HIP, hipGetErrorString(e)); }
   // digit multiples for the few-row full-width MSMs of the opening tail: 8 x the window table (57 KB per generator).  Optional: if the
   // allocation fails or the generator set is larger than LASSO_MSM_DIRECT_MAX_N the bucket kernel serves those MSMs too.
-  static const size_t direct_max = [] { const char* v = getenv("LASSO_MSM_DIRECT_MAX_N"); return v ? (size_t)atoll(v) : (((size_t)1 << 17) + 64); }();
-  if (n <= direct_max) {
+  if (n <= dsw::msm_direct_max_n()) {
     if (dmalloc(c, (void**)&b->d_mult, n * MSM_WINDOWS * MSM_MULTS * sizeof(niels29)) == hipSuccess) {
       hipLaunchKernelGGL(k_precompute_multiples, dim3((unsigned)((n * MSM_WINDOWS + 63) / 64)), dim3(64), 0, c->stream, (const niels29*)b->d_table, n, b->d_mult);
       e = hipGetLastError(); if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1526,8 +1500,7 @@ int32_t lasso_bases_create_opt(lasso_ctx* c, const lasso_affine* points, size_t 
   }
   // ... and their byte multiples (8x the bytes of d_mult: 459 KB per generator, 3.8 GB for the 8194 generators of the headline's widest opening; HBM is 288 GB and the
   // generators are fixed for the life of the object).  LASSO_MSM_DIRECT8=0 turns them off, LASSO_MSM_DIRECT8_MAX_N moves the size limit; a failed allocation is not an error.
-  static const size_t direct8_max = [] { const char* off = getenv("LASSO_MSM_DIRECT8"); if (off && off[0] == '0') return (size_t)0; const char* v = getenv("LASSO_MSM_DIRECT8_MAX_N"); return v ? (size_t)atoll(v) : (((size_t)1 << 14) + 64); }();
-  if (b->d_mult && byte_multiples && n <= direct8_max) {
+  if (b->d_mult && byte_multiples && n <= dsw::msm_direct8_max_n()) {
     typedef MsmD<8> D8;
     if (dmalloc(c, (void**)&b->d_mult8, n * D8::WINDOWS * D8::MULTS * sizeof(niels29)) == hipSuccess) {
       hipLaunchKernelGGL(k_precompute_tab8, dim3((unsigned)((n + 63) / 64), D8::WINDOWS), dim3(64), 0, c->stream, (const niels29*)b->d_table, n, 0u, b->d_mult8, D8::MULTS);   // all 32 windows in one launch
@@ -1546,7 +1519,6 @@ void lasso_bases_destroy(lasso_ctx* c, lasso_bases* b) {
 }
 // the byte-multiple table of window w8 (k_precompute_tab8), built the first time a commitment asks for it: 255 * n * 112 bytes (117 MB for n = 4096).
 // LASSO_MSM_ROWS8=0 switches the path off (A/B measurements); an allocation failure falls back to the bucket kernel for the life of the bases object.
-static bool msm_rows8_enabled() { static const bool on = [] { const char* v = getenv("LASSO_MSM_ROWS8"); return !(v && v[0] == '0'); }(); return on; }
 static const niels29* ensure_tab8(lasso_ctx* c, const lasso_bases* cb, uint32_t w8) {
   lasso_bases* b = const_cast<lasso_bases*>(cb);
   std::lock_guard<std::mutex> lock(b->tab8_mu);   // one builder at a time; the pointer is published only after the build has been waited for (below)
@@ -1565,59 +1537,15 @@ static const niels29* ensure_tab8(lasso_ctx* c, const lasso_bases* cb, uint32_t 
 // `commit` (benches/bench.rs:54-66) prepares its generators first.  byte_windows = 1 (values < 2^8) or 2 (< 2^16).  A table that cannot be allocated is not an error (the bucket kernel serves).
 int32_t lasso_bases_prepare(lasso_ctx* c, const lasso_bases* b, uint32_t byte_windows) {
   REQUIRE(c, b && byte_windows >= 1 && byte_windows <= 2 && !c->proto.waiting_on_device() && !c->proto.tail_active);
-  if (!msm_rows8_enabled()) return 0;
+  if (!dsw::msm_rows8()) return 0;
   for (uint32_t w = 0; w < byte_windows; w++) if (!ensure_tab8(c, b, w)) break;
   return 0;
 }
 
-// chunks per row.  Measured on MI355X (profiles/): the bucket kernel is VALU-issue-bound even at one wave per SIMD (the 81 independent
-// multiply-adds of a field product pipeline back to back), so extra workgroups beyond one per CU only multiply the fixed per-workgroup
-// reduction tree (2 rows x 482 chunks ran 310 us, 2 x 129 ran 180 us).  Aim for rows*K = 256 workgroups, never below 1024 pairs a chunk.
-// group additions the REFERENCE's msm_bigint_wnaf (msm/mod.rs:91-164) performs for `rows` MSMs of n terms with num_bits-bit scalars:
-// bucket accumulation n*W + bucket reduction W*2*2^c + window combine (W-1)*(c+1), c = ln_without_floats(n)+2 (:112-119,:322-325), W = ceil(num_bits/c).
-// This is the algorithmic work unit of the MSM families' roofline (bench.py roofline_msm); the kernels here execute a different schedule
-// (precomputed 4-bit window tables: one mixed addition per non-zero nibble, no per-window reduction, no doubling chain).
-#ifdef LASSO_BN254
-#define FR_MODULUS_BITS 254u
-#else
-#define FR_MODULUS_BITS 253u
-#endif
-static double msm_ref_adds(size_t rows, size_t n, uint32_t num_bits) {
-  size_t lg = n <= 1 ? 0 : 64 - (size_t)__builtin_clzll((unsigned long long)(n - 1));
-  const size_t cw = n < 32 ? 3 : lg * 69 / 100 + 2, W = (num_bits + cw - 1) / cw;
-  return (double)rows * ((double)n * W + (double)W * 2.0 * (double)((size_t)1 << cw) + (double)(W > 0 ? W - 1 : 0) * (cw + 1.0));
-}
-static size_t msm_chunks(size_t rows, size_t n_cols, uint32_t W) {
-  size_t pairs = n_cols * W, K = 1;
-  if (rows < 256) { K = 256 / rows; size_t kmax = (pairs + 1023) / 1024; if (kmax < 1) kmax = 1; if (K > kmax) K = kmax; }
-  size_t cols_per_chunk = (n_cols + K - 1) / K;
-  return (n_cols + cols_per_chunk - 1) / cols_per_chunk;
-}
-// shared tail: bucket kernel over `rows` rows of `n_cols` scalars, then per-row sum of the chunk partials, then hand the points to the host
-#define MSM_SMALL_ROWS 16   // results of up to this many rows return through the mapped buffer + flag (no memcpy, no stream sync)
-// latency-shaped path (k_msm_direct): rows <= MSM_SMALL_ROWS of full-width canonical scalars, results through the mapped buffer + flag.
-// Chunking: one workgroup per CU over all rows, whole multiples of 256 items per workgroup (every thread the same number of mixed adds),
-// at most 8192 items (128 columns of LDS-staged scalars).  Scratch after the scalars: rows * K partial points.
-static bool msm_direct_enabled() { static const bool on = [] { const char* v = getenv("LASSO_MSM_DIRECT"); return !(v && v[0] == '0'); }(); return on; }
-static size_t msm_direct_chunks(size_t rows, size_t n_cols, uint32_t* items_per_chunk, size_t windows = MSM_WINDOWS) {
-  const size_t total = n_cols * windows;
-  // workgroups per launch: one per CU by default.  LASSO_MSM_DIRECT_WGS overrides it for tuning (more workgroups = shorter per-thread addition chains,
-  // a larger cross-workgroup tree): the BN254 build's additions cost ~2.5x the Edwards ones and its balance point has not been measured yet
-  static const size_t wgs = [] { const char* v = getenv("LASSO_MSM_DIRECT_WGS"); const long x = v ? atol(v) : 0; return (size_t)(x >= 1 && x <= 4096 ? x : 256); }();
-  size_t K = wgs / rows; if (K < 1) K = 1;
-  size_t ipc = ((total + K - 1) / K + 255) / 256 * 256;
-  const size_t ipc_max = windows * 128;   // 128 columns of LDS-staged scalars
-  if (ipc > ipc_max) ipc = ipc_max;
-  *items_per_chunk = (uint32_t)ipc;
-  return (total + ipc - 1) / ipc;
-}
-// bytes of point scratch an MSM of `rows` x `n_cols` may need after its scalars (whichever kernel serves it)
-static size_t msm_pts_bytes(size_t rows, size_t n_cols) {
-  uint32_t ipc; const size_t kd = rows <= MSM_SMALL_ROWS ? msm_direct_chunks(rows, n_cols, &ipc) : 0, kb = msm_chunks(rows, n_cols, MSM_WINDOWS);
-  return (rows * (kd > kb ? kd : kb) + 2 * rows + 4) * sizeof(pt29) + 512;
-}
+// chunking, scratch bytes and the kernel choice of the MSMs: launch_plan.cuh
+static size_t msm_pts_bytes(size_t rows, size_t n_cols) { return msm_pts_bytes(rows, n_cols, msm_direct_wgs(dsw::msm_direct_wgs())); }
 // round 6: the few-row MSMs hand their points over as tagged elements (msm_direct_finish) when the context is in tagged mode; LASSO_MSM_TAGGED=0: the flag protocol (A/B switch)
-static bool msm_tagged(lasso_ctx* c) { static const bool off = [] { const char* v = getenv("LASSO_MSM_TAGGED"); return v && v[0] == '0'; }(); return c->tagged && !off; }
+static bool msm_tagged(lasso_ctx* c) { return c->tagged && dsw::msm_tagged(); }
 #define MSM_RES(c) (msm_tagged(c) ? (ed_point*)(c)->d_tag : (ed_point*)(c)->d_small), (c)->d_counters + LASSO_MAX_PTRS + 8, (msm_tagged(c) ? LASSO_TAGGED : (c)->d_flag)
 // mode 0: d_scal = canonical integers; 1: field elements in memory (Montgomery) form, converted by the kernel; 2: as 1 with the first n_cols - 2 columns
 // multiplied by *scale and the last two columns = tail[0], tail[1] (k_msm_direct<MODE>)
@@ -1626,17 +1554,17 @@ static bool msm_tagged(lasso_ctx* c) { static const bool off = [] { const char* 
 static int32_t run_msm_direct(lasso_ctx* c, const uint8_t* d_scal, size_t row_stride, size_t rows, size_t n_cols, const MsmColMap& cm, const lasso_bases* b, uint8_t* scratch_after, lasso_point* out,
                               int mode = 0, const lasso_fr* scale = nullptr, const lasso_fr* tail = nullptr, uint32_t sstride = 1, uint32_t soffset = 0,
                               const lasso_fr* const* heads = nullptr, const uint32_t* gate_seq = nullptr) {
-  const bool w8 = b->d_mult8 != nullptr; const size_t windows = w8 ? MsmD<8>::WINDOWS : MsmD<4>::WINDOWS;
-  uint32_t ipc = 0; const size_t K = msm_direct_chunks(rows, n_cols, &ipc, windows);
+  const MsmDirectPlan P = msm_direct_plan(rows, n_cols, b->d_mult8 != nullptr, dsw::msm_direct_wgs());
+  const size_t K = P.K; const uint32_t ipc = P.ipc;
   const uint32_t seq = gate_seq ? *gate_seq : next_seq(c);
   const fr_t* const h0 = heads ? (const fr_t*)heads[0] : nullptr; const fr_t* const h1 = heads ? (const fr_t*)heads[1] : nullptr;
   const uint32_t* const ggm = gate_seq ? (const uint32_t*)c->d_gmail : nullptr;
   {
-    ProfScope ps(c, LASSO_K_MSM_DIRECT, (double)rows * n_cols * 32, msm_ref_adds(rows, n_cols, FR_MODULUS_BITS), false, (double)rows * n_cols * windows);
+    ProfScope ps(c, LASSO_K_MSM_DIRECT, (double)rows * n_cols * 32, P.ref_adds, false, P.adds);
     const fr_t z = fr_zero();
 #define LAUNCH_DIRECT(M, WB_, TAB_, SC, T0, T1) hipLaunchKernelGGL((k_msm_direct<M, WB_>), dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4, (uint32_t)n_cols, ipc, cm, \
                        (const niels29*)TAB_, b->n, (pt29*)scratch_after, MSM_RES(c), seq, SC, T0, T1, ps.counter(), sstride, soffset, h0, h1, ggm)
-    if (w8) {
+    if (P.w8) {
       if (mode == 0) LAUNCH_DIRECT(0, 8, b->d_mult8, z, z, z);
       else if (mode == 1) LAUNCH_DIRECT(1, 8, b->d_mult8, z, z, z);
       else LAUNCH_DIRECT(2, 8, b->d_mult8, to_fr(scale), to_fr(tail), to_fr(tail + 1));
@@ -1650,95 +1578,82 @@ static int32_t run_msm_direct(lasso_ctx* c, const uint8_t* d_scal, size_t row_st
   if (gate_seq) return 0;   // released by lasso_bullet_post, collected by lasso_result_wait
   return wait_flag(c, seq, rows * (sizeof(ed_point) / sizeof(fr_t)), (lasso_fr*)out, msm_tagged(c));
 }
-static bool msm_direct_fused() { static const bool on = [] { const char* v = getenv("LASSO_MSM_FUSED"); return !(v && v[0] == '0'); }(); return on; }   // A/B switch: conversions and the bullet fold inside the MSM launch
 // d_rows_out (device, rows x sizeof(pt29)): leave the row sums on the device in the kernels' own point form instead of handing them to the host —
 // slab mode's partial row commitments, which go through lasso_rccl_allgather and lasso_points_reduce_compress
 static int32_t run_msm(lasso_ctx* c, const uint8_t* d_scal, uint32_t bps, uint32_t W, size_t row_stride, size_t rows, size_t n_cols, const lasso_bases* b, uint8_t* scratch_after, lasso_point* out,
                        uint8_t* out_compressed = nullptr, void* d_rows_out = nullptr) {
+  const MsmShape shape = {bps, W, rows, n_cols, out_compressed != nullptr, d_rows_out != nullptr};
+  // (the three LASSO_MSM_PIP* switches are read per call — a commitment of that size is milliseconds — so that one test process can run both forms)
+  const MsmSwitches sw = {dsw::msm_direct(), dsw::msm_rows8(), dsw::msm_rows8w(), dsw::msm_full8(), dsw::msm_pip(), dsw::msm_rows8w_waves(), dsw::msm_pip_min_cols(), dsw::msm_pip_scratch_mb(), dsw::msm_direct_wgs()};
+  MsmHave have = {b->n, b->d_mult != nullptr, b->d_mult8 != nullptr, true, true};
+  MsmPlan P = msm_plan(shape, have, sw);
+  if (P.kernel == MSM_K_DIRECT) { const MsmColMap id = {0, 0, 0, 0}; return run_msm_direct(c, d_scal, row_stride, rows, n_cols, id, b, scratch_after, out); }
+  // the plan's two wishes: byte-multiple tables built on first use, the scratch of the 12-bit-window kernels.  Refused: plan again without (the bucket kernel serves)
+  const niels29* t8[2] = {nullptr, nullptr};
+  if (P.kernel == MSM_K_ROWS8W || P.kernel == MSM_K_ROWS8) {
+    t8[0] = ensure_tab8(c, b, 0); t8[1] = P.W8 > 1 && t8[0] ? ensure_tab8(c, b, 1) : t8[0];
+    if (!t8[1]) { have.tab8 = false; P = msm_plan(shape, have, sw); }
+  } else if (P.kernel == MSM_K_PIP && ensure_pip(c, P.pip_group * P.pip_row_bytes + 256) != 0) { have.pip_scratch = false; P = msm_plan(shape, have, sw); }
   if (d_rows_out) out_compressed = (uint8_t*)d_rows_out;   // same kernel path as the compressed form: k_points_sum leaves pt29 row sums in d_final
-  if (bps == 32 && rows <= MSM_SMALL_ROWS && !out_compressed && b->d_mult && msm_direct_enabled()) { const MsmColMap id = {0, 0, 0, 0}; return run_msm_direct(c, d_scal, row_stride, rows, n_cols, id, b, scratch_after, out); }
-  const size_t K = msm_chunks(rows, n_cols, W);
-  const size_t cols_per_chunk = (n_cols + K - 1) / K;
+  const size_t K = P.K;
   pt29* d_partial = (pt29*)scratch_after;
-  const bool small = rows <= MSM_SMALL_ROWS && !out_compressed;
+  const bool small = P.result == MSM_R_FLAG;
   ed_point* d_final = small ? (ed_point*)c->d_small : (ed_point*)(((uintptr_t)(d_partial + rows * K) + 15) & ~(uintptr_t)15);
   const uint32_t seq = small ? next_seq(c) : 0;
-  // many rows of small scalars (<= 16 bits): one table entry per non-zero byte (k_msm_rows8) instead of nibble buckets
-  const niels29* t8[2] = {nullptr, nullptr};
-  const uint32_t W8 = (W + 1) / 2;
-  if (bps == 4 && W <= 4 && rows >= 32 && msm_rows8_enabled()) { t8[0] = ensure_tab8(c, b, 0); t8[1] = W8 > 1 && t8[0] ? ensure_tab8(c, b, 1) : t8[0]; if (!t8[1]) t8[0] = nullptr; }
-  // full-width scalars over the signed byte-multiple table (k_msm_rows_full: 32 additions per scalar, no buckets) — MEASURED AND NOT THE DEFAULT (round 6, LASSO_MSM_FULL8=1 turns
-  // it on): Spark C=16 2^22's E commitment 198 ms against the bucket kernel's 182 ms.  Half the additions, but every one of them reads its own 128-byte line of a 4.3 GB table
-  // (8194 generators x 32 windows x 128 multiples): 2.1e9 random line reads = 1.38 TB/s, the rate HBM serves random lines at; the bucket kernel's 64-window table is 67 MB and
-  // stays in the Infinity Cache.  profiles/r06_full_width_commit_ab.txt
-  static const bool full8_on = [] { const char* v = getenv("LASSO_MSM_FULL8"); return v && v[0] == '1'; }();
-  const bool full8 = bps == 32 && b->d_mult8 != nullptr && full8_on && !t8[0];
-  // many long rows of full-width scalars: 12-bit signed windows over the SAME nibble-window table, 2048 buckets per row, 22 additions per scalar instead of 60
-  // (msm_kernels.cuh k_msm_pip_*; round 6).  Rows go through in groups that keep the scratch (sorted pairs 84 B per column, bucket sums 288 KB per row) near 1.2 GB
-  // (LASSO_MSM_PIP_SCRATCH_MB).  From 256 rows of 512 columns on (measured, profiles/r06_full_width_commit_ab.txt: 512 x 512 0.69 against 1.12 ms, 1024 x 1024 1.86 against 3.70,
-  // 4096 x 4096 23.5 against 47.9).  LASSO_MSM_PIP=0: the bucket kernel (A/B switch).  A refused allocation falls back to it as well.
-  // (both switches are read per call — a commitment of this size is milliseconds — so that one test process can run both forms)
-  const bool pip_on = [] { const char* v = getenv("LASSO_MSM_PIP"); return !(v && v[0] == '0'); }();
-  const size_t pip_min_cols = [] { const char* v = getenv("LASSO_MSM_PIP_MIN_COLS"); const long x = v ? atol(v) : 512; return (size_t)(x < 1 ? 1 : x); }();
-  size_t pip_group = 0, pip_row_bytes = 0, pip_items = 0;
-  if (bps == 32 && pip_on && !full8 && K == 1 && rows >= 256 && n_cols >= pip_min_cols && n_cols < ((size_t)1 << 26) && b->n * MSM_WINDOWS < ((size_t)1 << 31)) {
-    pip_items = n_cols * MSM_PIP_WINDOWS;
-    pip_row_bytes = ((pip_items * 4 + (MSM_PIP_BUCKETS + 1) * 4 + MSM_PIP_BUCKETS * 2 + MSM_PIP_BUCKETS * sizeof(pt29) + n_cols) + 255) & ~(size_t)255;
-    const size_t pip_mb = [] { const char* v = getenv("LASSO_MSM_PIP_SCRATCH_MB"); const long x = v ? atol(v) : 1200; return (size_t)(x < 16 ? 16 : x); }();
-    pip_group = (pip_mb << 20) / pip_row_bytes; if (pip_group < 64) pip_group = 64; if (pip_group > rows) pip_group = rows;
-    if (ensure_pip(c, pip_group * pip_row_bytes + 256) != 0) pip_group = 0;
-  }
   {
-    ProfScope ps(c, LASSO_K_MSM, (double)rows * n_cols * bps, msm_ref_adds(rows, n_cols, bps == 4 ? 4 * W : FR_MODULUS_BITS), rows > MSM_SMALL_ROWS,
-                 (double)rows * n_cols * (t8[0] ? W8 : full8 ? 32 : pip_group ? MSM_PIP_WINDOWS : W));
-    // many SHORT rows: one wave per row (k_msm_rows8w: 64 additions per lane and a 6-level tree inside the wave instead of 16 per thread and a 256-point tree).  Measured
-    // (profiles/r04_ab_rows8w.txt): -9 % on the headline's E (4096 one-byte columns), -8 % on BN254 configs[1], +2 % on configs[2]'s 16384-column rows, where a thread of the
-    // 256-lane kernel already runs 64 additions — hence the column bound.  LASSO_MSM_ROWS8W=0: A/B switch
-    static const bool rows8w = [] { const char* v = getenv("LASSO_MSM_ROWS8W"); return !(v && v[0] == '0'); }();
-    // rows per wave (round 6 experiment, NOT the default: LASSO_MSM_ROWS8W_WAVES=2048 caps a launch at two waves per SIMD, all resident at once — measured 0.966 ms against
-    // 0.896 ms at one row per wave on the headline's E, profiles/r06_madd_bench_curve25519.txt section C: two waves per SIMD hide less than three, the tail of the
-    // three-wave schedule costs less than that)
-    static const size_t w_max = [] { const char* v = getenv("LASSO_MSM_ROWS8W_WAVES"); const long x = v ? atol(v) : 0; return (size_t)(x < 0 ? 0 : x); }();
-    const size_t rpw = w_max ? (rows + w_max - 1) / w_max : 1, waves = (rows + rpw - 1) / rpw;
-    if (t8[0] && rows8w && K == 1 && rows >= 1024 && n_cols * W8 <= 8192) hipLaunchKernelGGL(k_msm_rows8w, dim3((unsigned)((waves + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64))), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4,
-                                                                      (uint32_t)n_cols, W8, t8[0], t8[1], b->n, d_partial, (uint32_t)rows, ps.counter(), (uint32_t)rpw);
-    else if (t8[0]) hipLaunchKernelGGL(k_msm_rows8, dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4, (uint32_t)n_cols, (uint32_t)cols_per_chunk, W8,
-                                  t8[0], t8[1], b->n, d_partial, ps.counter());
-    else if (pip_group) {
-      uint8_t* base = (uint8_t*)c->d_pip;
-      uint32_t* d_sorted = (uint32_t*)base; uint32_t* d_offs = d_sorted + pip_group * pip_items; uint16_t* d_perm = (uint16_t*)(d_offs + pip_group * (MSM_PIP_BUCKETS + 1));
-      uint8_t* d_vtop = (uint8_t*)(d_perm + pip_group * MSM_PIP_BUCKETS);
-      pt29* d_bk = (pt29*)((((uintptr_t)(d_vtop + pip_group * n_cols)) + 15) & ~(uintptr_t)15);
-      for (size_t r0 = 0; r0 < rows; r0 += pip_group) {
-        const unsigned g = (unsigned)(rows - r0 < pip_group ? rows - r0 : pip_group);
-        hipLaunchKernelGGL(k_msm_pip_sort, dim3(g), dim3(MSM_THREADS), 0, c->stream, d_scal + r0 * row_stride, row_stride, (uint32_t)n_cols, (uint32_t)b->n, d_sorted, pip_items, d_offs, d_perm, d_vtop, ps.counter());
-        hipLaunchKernelGGL(k_msm_pip_accumulate, dim3(g, MSM_PIP_PER_THREAD), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_sorted, pip_items, (const uint32_t*)d_offs, (const uint16_t*)d_perm, (const niels29*)b->d_table, d_bk);
-        hipLaunchKernelGGL(k_msm_pip_reduce, dim3(g), dim3(MSM_THREADS), 0, c->stream, (const pt29*)d_bk, (const uint8_t*)d_vtop, (uint32_t)n_cols, (const niels29*)b->d_table + (size_t)(MSM_WINDOWS - 1) * b->n, d_partial + r0);
-      }
+    ProfScope ps(c, LASSO_K_MSM, (double)rows * n_cols * bps, P.ref_adds, rows > MSM_SMALL_ROWS, P.adds);
+    switch (P.kernel) {
+      case MSM_K_ROWS8W:
+        hipLaunchKernelGGL(k_msm_rows8w, dim3((unsigned)((P.waves + MSM_THREADS / 64 - 1) / (MSM_THREADS / 64))), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4,
+                           (uint32_t)n_cols, P.W8, t8[0], t8[1], b->n, d_partial, (uint32_t)rows, ps.counter(), (uint32_t)P.rpw);
+        break;
+      case MSM_K_ROWS8:
+        hipLaunchKernelGGL(k_msm_rows8, dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4, (uint32_t)n_cols, (uint32_t)P.cols_per_chunk, P.W8,
+                           t8[0], t8[1], b->n, d_partial, ps.counter());
+        break;
+      case MSM_K_PIP: {
+        const size_t pip_group = P.pip_group, pip_items = P.pip_items;
+        uint8_t* base = (uint8_t*)c->d_pip;
+        uint32_t* d_sorted = (uint32_t*)base; uint32_t* d_offs = d_sorted + pip_group * pip_items; uint16_t* d_perm = (uint16_t*)(d_offs + pip_group * (MSM_PIP_BUCKETS + 1));
+        uint8_t* d_vtop = (uint8_t*)(d_perm + pip_group * MSM_PIP_BUCKETS);
+        pt29* d_bk = (pt29*)((((uintptr_t)(d_vtop + pip_group * n_cols)) + 15) & ~(uintptr_t)15);
+        for (size_t r0 = 0; r0 < rows; r0 += pip_group) {
+          const unsigned g = (unsigned)(rows - r0 < pip_group ? rows - r0 : pip_group);
+          hipLaunchKernelGGL(k_msm_pip_sort, dim3(g), dim3(MSM_THREADS), 0, c->stream, d_scal + r0 * row_stride, row_stride, (uint32_t)n_cols, (uint32_t)b->n, d_sorted, pip_items, d_offs, d_perm, d_vtop, ps.counter());
+          hipLaunchKernelGGL(k_msm_pip_accumulate, dim3(g, MSM_PIP_PER_THREAD), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_sorted, pip_items, (const uint32_t*)d_offs, (const uint16_t*)d_perm, (const niels29*)b->d_table, d_bk);
+          hipLaunchKernelGGL(k_msm_pip_reduce, dim3(g), dim3(MSM_THREADS), 0, c->stream, (const pt29*)d_bk, (const uint8_t*)d_vtop, (uint32_t)n_cols, (const niels29*)b->d_table + (size_t)(MSM_WINDOWS - 1) * b->n, d_partial + r0);
+        }
+      } break;
+      case MSM_K_FULL8:
+        hipLaunchKernelGGL((k_msm_rows_full<8>), dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4, (uint32_t)n_cols, (uint32_t)P.cols_per_chunk,
+                           (const niels29*)b->d_mult8, b->n, d_partial, ps.counter());
+        break;
+      default:
+        hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, d_scal, bps, W, row_stride, n_cols, P.cols_per_chunk, (const niels29*)b->d_table, b->n, d_partial, ps.counter());
     }
-    else if (full8) hipLaunchKernelGGL((k_msm_rows_full<8>), dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const uint32_t*)d_scal, row_stride / 4, (uint32_t)n_cols, (uint32_t)cols_per_chunk,
-                                       (const niels29*)b->d_mult8, b->n, d_partial, ps.counter());
-    else hipLaunchKernelGGL(k_msm_buckets, dim3((unsigned)K, (unsigned)rows), dim3(MSM_THREADS), 0, c->stream, d_scal, bps, W, row_stride, n_cols, cols_per_chunk, (const niels29*)b->d_table, b->n, d_partial, ps.counter());
     hipLaunchKernelGGL(k_points_sum, dim3((unsigned)rows), dim3(MSM_THREADS), 0, c->stream, (const pt29*)d_partial, (uint32_t)K, d_final, out_compressed ? (uint32_t*)d_final : (uint32_t*)nullptr,
                        c->d_counters + LASSO_MAX_PTRS + 1, small ? c->d_flag : (uint32_t*)nullptr, seq);
   }
   HIPCHK(c, hipGetLastError());
-  if (d_rows_out) { HIPCHK(c, hipMemcpyAsync(d_rows_out, d_final, rows * sizeof(pt29), hipMemcpyDeviceToDevice, c->stream)); return 0; }
-  if (out_compressed) {   // d_final holds the row sums as pt29 (144 B per row: the scratch is sized for it, see hyrax_commit_impl); 32 wire bytes per row go out
-    if (rows <= ((size_t)1 << 16)) {   // wire bytes straight into the host-mapped result buffer, handed over behind the sequence flag
+  switch (P.result) {
+    case MSM_R_DEVICE_ROWS: HIPCHK(c, hipMemcpyAsync(d_rows_out, d_final, rows * sizeof(pt29), hipMemcpyDeviceToDevice, c->stream)); return 0;
+    case MSM_R_COMPRESSED_MAPPED: {   // d_final holds the row sums as pt29 (144 B per row: the scratch is sized for it, see hyrax_commit_impl); 32 wire bytes per row go straight into the host-mapped result buffer, handed over behind the sequence flag
       int32_t rc = ensure_small(c, rows); if (rc) return rc;
       hipLaunchKernelGGL(k_points_compress, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, (const pt29*)d_final, rows, (uint32_t*)c->d_small);
       HIPCHK(c, hipGetLastError());
       return fetch_small(c, rows, (lasso_fr*)out_compressed);
     }
-    uint32_t* d_wire = (uint32_t*)(((uintptr_t)((pt29*)d_final + rows) + 15) & ~(uintptr_t)15);
-    hipLaunchKernelGGL(k_points_compress, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, (const pt29*)d_final, rows, d_wire);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out_compressed, d_wire, rows * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+    case MSM_R_COMPRESSED_MEMCPY: {
+      uint32_t* d_wire = (uint32_t*)(((uintptr_t)((pt29*)d_final + rows) + 15) & ~(uintptr_t)15);
+      hipLaunchKernelGGL(k_points_compress, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, (const pt29*)d_final, rows, d_wire);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(out_compressed, d_wire, rows * 32, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      return 0;
+    }
+    case MSM_R_FLAG: return wait_flag(c, seq, rows * (sizeof(ed_point) / sizeof(fr_t)), (lasso_fr*)out);
+    default: break;
   }
-  if (small) return wait_flag(c, seq, rows * (sizeof(ed_point) / sizeof(fr_t)), (lasso_fr*)out);
   HIPCHK(c, hipMemcpyAsync(out, d_final, rows * sizeof(ed_point), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -1805,7 +1720,7 @@ int32_t lasso_msm_dev(lasso_ctx* c, const lasso_bases* b, const lasso_fr* d_scal
   REQUIRE(c, b && d_scalars && out && n >= 1 && n <= b->n);
   int32_t rc = ensure_scratch(c, n * 32 + msm_pts_bytes(1, n)); if (rc) return rc;
   fr_t* d_can = (fr_t*)c->d_scratch;
-  if (b->d_mult && msm_direct_enabled() && msm_direct_fused()) {   // the latency-shaped kernel converts its own columns: one launch instead of two
+  if (b->d_mult && dsw::msm_direct() && dsw::msm_fused()) {   // the latency-shaped kernel converts its own columns: one launch instead of two
     const MsmColMap id = {0, 0, 0, 0};
     return run_msm_direct(c, (const uint8_t*)d_scalars, n * 32, 1, n, id, b, (uint8_t*)c->d_scratch, out, 1);
   }
@@ -1854,7 +1769,7 @@ int32_t lasso_msm_dev_scaled(lasso_ctx* c, const lasso_bases* b, const lasso_fr*
   const size_t row = n + 2;
   int32_t rc = ensure_scratch(c, row * 32 + msm_pts_bytes(1, row)); if (rc) return rc;
   fr_t* d_can = (fr_t*)c->d_scratch;
-  if (b->d_mult && msm_direct_enabled() && msm_direct_fused()) {   // scaling and conversion inside the MSM launch (the two tail columns are kernel arguments, never read from d_scalars)
+  if (b->d_mult && dsw::msm_direct() && dsw::msm_fused()) {   // scaling and conversion inside the MSM launch (the two tail columns are kernel arguments, never read from d_scalars)
     const MsmColMap id = {0, 0, 0, 0};
     return run_msm_direct(c, (const uint8_t*)d_scalars, row * 32, 1, row, id, b, (uint8_t*)c->d_scratch, out, 2, scale, tail);
   }
@@ -1886,13 +1801,8 @@ int32_t lasso_bullet_lr(lasso_ctx* c, const lasso_bases* b, size_t n, const lass
 static int32_t bullet_round_fused(lasso_ctx* c, const lasso_bases* b, size_t n, const lasso_fr* d_a_in, const lasso_fr* d_b_in, const lasso_fr* d_w_in, lasso_fr* d_a_out, lasso_fr* d_b_out,
                                   lasso_fr* d_w_out, size_t nk, const lasso_fr* u, const lasso_fr* u_inv, const lasso_fr* blinds, lasso_point* out, uint32_t world, uint32_t rank, bool ahead = false) {
   const bool fold = u != nullptr || ahead;   // ahead: a folding round enqueued before its challenge exists (the kernel waits for lasso_bullet_post)
-  // chunks per row: (workgroups of the launch - 2 extra) / 2 rows, items shared out evenly (a multiple of 64 keeps whole columns together where it can)
-  static const size_t wgs = [] { const char* v = getenv("LASSO_MSM_DIRECT_WGS"); const long x = v ? atol(v) : 0; return (size_t)(x >= 4 && x <= 4096 ? x : 256); }();
-  const size_t n_loc = n / world, cols = (nk / 2 >= world) ? n_loc / 2 : n_loc;   // the longest row's local columns
-  const bool w8 = b->d_mult8 != nullptr; const size_t windows = w8 ? MsmD<8>::WINDOWS : MsmD<4>::WINDOWS;
-  const size_t total = cols * windows, kmax = (wgs - 2) / 2;
-  size_t ipc_ = (total + kmax - 1) / kmax; ipc_ = (ipc_ + windows - 1) / windows * windows; if (ipc_ < 256) ipc_ = 256; if (ipc_ > windows * 128) ipc_ = windows * 128;
-  const uint32_t ipc = (uint32_t)ipc_; const size_t K = (total + ipc_ - 1) / ipc_;
+  const BulletPlan P = bullet_plan(n, nk, world, b->d_mult8 != nullptr, dsw::msm_direct_wgs());   // chunks per row and items per chunk (launch_plan.cuh)
+  const bool w8 = P.w8; const size_t windows = P.windows, n_loc = P.n_loc, K = P.K; const uint32_t ipc = P.ipc;
   int32_t rc = ensure_scratch(c, 2 * (K + 1) * sizeof(pt29) + 512); if (rc) return rc;
   const uint32_t seq = next_seq(c);
   if (ahead) hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, c->stream, (const uint32_t*)c->mail_d, c->d_gmail, seq, 1u);   // waits for lasso_bullet_post's two scalars; the round starts when it ends
@@ -1937,8 +1847,8 @@ int32_t lasso_bullet_round(lasso_ctx* c, const lasso_bases* b, size_t n, const l
   REQUIRE(c, b && d_a_in && d_b_in && d_w_in && blinds && out && n >= 2 && (n & (n - 1)) == 0 && nk >= 2 && nk <= n && (nk & (nk - 1)) == 0 && n + 2 <= b->n);
   const bool fold = u != nullptr;
   if (fold) REQUIRE(c, u_inv && d_a_out && d_b_out && d_w_out && 2 * nk <= n && d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in);
-  const bool direct = b->d_mult && msm_direct_enabled();
-  if (direct && msm_direct_fused()) return bullet_round_fused(c, b, n, d_a_in, d_b_in, d_w_in, d_a_out, d_b_out, d_w_out, nk, u, u_inv, blinds, out, 1, 0);
+  const bool direct = b->d_mult && dsw::msm_direct();
+  if (direct && dsw::msm_fused()) return bullet_round_fused(c, b, n, d_a_in, d_b_in, d_w_in, d_a_out, d_b_out, d_w_out, nk, u, u_inv, blinds, out, 1, 0);
   const size_t row = direct ? n / 2 + 2 : n + 2;   // compact rows for k_msm_direct: only the non-zero half
   const unsigned nx = grid_for(n / 2, 64);
   int32_t rc = ensure_scratch(c, 2 * row * 32 + (size_t)nx * 2 * sizeof(fr_t) + msm_pts_bytes(2, row)); if (rc) return rc;
@@ -1957,9 +1867,8 @@ int32_t lasso_bullet_round(lasso_ctx* c, const lasso_bases* b, size_t n, const l
 }
 // ---- a folding round LAUNCHED AHEAD of its challenge (include/lasso_hip.h): enqueue, later post u / u^-1, then collect like any deferred result
 static bool bullet_ahead_possible(lasso_ctx* c, const lasso_bases* b) {
-  static const bool off = [] { const char* v = getenv("LASSO_BULLET_AHEAD"); return v && v[0] == '0'; }();
-  const bool bracketed = ((c->prof_mask >> LASSO_K_MSM_DIRECT) & 1u) && !(c->prof_mask & 0x40000000u);   // a launch between profiling events would count the wait for the host as kernel time
-  return !off && !bracketed && b && b->d_mult && msm_direct_enabled() && msm_direct_fused();
+  const bool bracketed = prof_bracketed(c->prof_mask, LASSO_K_MSM_DIRECT);   // a launch between profiling events would count the wait for the host as kernel time
+  return dsw::bullet_ahead() && !bracketed && b && b->d_mult && dsw::msm_direct() && dsw::msm_fused();
 }
 int32_t lasso_bullet_ahead_ok(lasso_ctx* c, const lasso_bases* b) { return c && bullet_ahead_possible(c, b) ? 1 : 0; }
 int32_t lasso_bullet_round_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, const lasso_fr* d_a_in, const lasso_fr* d_b_in, const lasso_fr* d_w_in, lasso_fr* d_a_out, lasso_fr* d_b_out,
@@ -1975,8 +1884,7 @@ int32_t lasso_bullet_round_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, c
 // the stream before the host has the last round's L and R; lasso_bullet_post releases it and lasso_result_wait(ctx, out, 6) delivers the point (4 values) and the two heads.
 //   = lasso_bullet_fold(d_a, d_b, 2, d_w, nw, d_w_out, u, u_inv); lasso_read_heads({d_a, d_b}); lasso_msm_dev_scaled(bases, d_w_out, n, scale, tail)     with n = 2 nw
 int32_t lasso_bullet_tail_ahead_ok(lasso_ctx* c, const lasso_bases* b) {
-  static const bool off = [] { const char* v = getenv("LASSO_BULLET_TAIL_AHEAD"); return v && v[0] == '0'; }();
-  return c && !off && bullet_ahead_possible(c, b) && msm_tagged(c) ? 1 : 0;
+  return c && dsw::bullet_tail_ahead() && bullet_ahead_possible(c, b) && msm_tagged(c) ? 1 : 0;
 }
 int32_t lasso_bullet_tail_ahead(lasso_ctx* c, const lasso_bases* b, size_t n, lasso_fr* d_a, lasso_fr* d_b, const lasso_fr* d_w, size_t nw, lasso_fr* d_w_out, const lasso_fr* scale, const lasso_fr* tail) {
   REQUIRE(c, b && d_a && d_b && d_w && d_w_out && scale && tail && n >= 2 && (n & (n - 1)) == 0 && 2 * nw == n && n + 2 <= b->n && d_w != d_w_out && !c->proto.waiting_on_device() && !c->proto.tail_active && !c->proto.defer_next);

@@ -17,9 +17,7 @@
 #include "fe29.cuh"
 #include "poly_kernels.cuh"   // block_reduce_fr
 
-#define MSM_THREADS 256
 #define MSM_BATCH 8192   // (bin, index) pairs sorted per pass: 32 KB of the 36 KB LDS buffer the reduction tree reuses
-#define MSM_WINDOWS 64   // 4-bit windows over 256-bit scalars
 // Layout of the digit- / byte-multiple tables: entry (window w, multiple m1 = m - 1, generator j) of a table with NW windows of NM multiples over tn generators.
 //   window-major (rounds 2-5):  ((w NM + m1) tn + j)   — a wave's 64 lanes (consecutive items = consecutive windows of a column, or consecutive columns with random bytes) touch 64 pages
 //   column-major (MSM_TABLE_COLMAJOR): ((j NW + w) NM + m1) — everything a column can ever ask for is one contiguous block (28 KB per byte window), a wave's lanes stay inside 1-2 MB
@@ -401,9 +399,6 @@ __device__ __forceinline__ void msm_coop_tree(pt29* pts, fe29 (*st)[4], uint32_t
 //                         the row is sum_t T_t + 8 sum_t t S_t, the second sum through a suffix scan of the S_t in LDS (sum_t t S_t = sum_{j>=1} sum_{t>=j} S_t).
 // Same group element per row as k_msm_buckets (another projective representative; the order of additions inside a bucket depends on the scatter's atomics: wire bytes do
 // not change).  Additions per 8192-column row: 172 K + 4 K (the values above bit 252) + 8 K (bucket sums) instead of 491 K.
-#define MSM_PIP_WINDOWS 21            // bucket windows: bits 0 .. 251; what is left above them (bits 252 .. 255 plus the last carry: 0 .. 4 for a canonical scalar) is NOT a bucket digit:
-                                      // half the scalars of a row have 1 there (the carry), and a bucket of 4096 pairs in a row of 88-pair buckets is one lane working alone for 35 ms (measured)
-#define MSM_PIP_BUCKETS 2048
 #define MSM_PIP_PER_THREAD (MSM_PIP_BUCKETS / MSM_THREADS)
 __device__ __forceinline__ uint32_t msm_pip_bits(const uint32_t* s, uint32_t w) {   // bits [12 w, 12 w + 12) of a 256-bit little-endian integer held in eight words
   const uint32_t bit = 12u * w, word = bit >> 5, sh = bit & 31u;
@@ -660,7 +655,7 @@ __global__ void __launch_bounds__(MSM_THREADS) k_msm_rows8w(const uint32_t* __re
 // Window width of the digit-multiple table a latency-shaped launch reads: WB = 4 (mult: m * 16^w * G, m = 1..8, 64 windows — every generator set has it) or WB = 8
 // (mult8: m * 256^w * G, m = 1..128, 32 windows — 8x the bytes, half the mixed additions per scalar; generator sets up to LASSO_MSM_DIRECT8_MAX_N).
 template <int WB> struct MsmD {
-  static constexpr uint32_t WINDOWS = 256u / WB, LOGW = WB == 4 ? 6u : 5u, MULTS = 1u << (WB - 1), DMASK = (1u << WB) - 1u, PER_WORD = 32u / WB;
+  static constexpr uint32_t WINDOWS = msm_direct_windows(WB), LOGW = WB == 4 ? 6u : 5u, MULTS = 1u << (WB - 1), DMASK = (1u << WB) - 1u, PER_WORD = 32u / WB;
   static constexpr uint32_t BIAS = WB == 4 ? 0x88888888u : 0x80808080u;
 };
 // signed-digit recoding of one canonical scalar into LDS: e = s + 0x88..8 (0x8080..80): digit w = (field w of e) - 2^(WB-1), in [-2^(WB-1), 2^(WB-1) - 1]; s < 2^254, so the top field cannot overflow

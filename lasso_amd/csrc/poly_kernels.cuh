@@ -7,11 +7,11 @@
 #include "fr.cuh"
 #include "fr29.cuh"
 #include "handoff_device.cuh"   // results for the host, mail from the host: the wire encoding of the hand-off protocol
+#include "launch_plan.cuh"      // LASSO_BLOCK, CUBIC_TAIL_Q, MSM_THREADS, MSM_WINDOWS, MSM_PIP_*: the constants the launch decisions share with the kernels
 
 #ifndef LASSO_MAX_PTRS
 #define LASSO_MAX_PTRS 136   // 2 * (2 * 33 memories) + slack; pointer tables travel by value in the kernarg segment
 #endif
-#define LASSO_BLOCK 256
 #define LASSO_MAX_ALPHA 32
 
 struct PtrTable { const fr_t* p[LASSO_MAX_PTRS]; };
@@ -618,7 +618,6 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_cubic_eqw_small(TM A, TM B, con
 // out (2 * ncirc elements per turn): sums turns: out[2c], out[2c+1];  final turn: out[c] = A_c head, out[ncirc + c] = B_c head.
 // Q = capacity in indices per circuit = threads of the workgroup: 256 (74 KB of LDS) or, since round 3, 512 (147 KB of the CU's 160 KB: one streaming round fewer per layer —
 // a resident turn costs ~10 us where a launch-per-round costs ~25 us at these sizes, profiles/r03_kernel_trace_one_proof_2p24.csv)
-#define CUBIC_TAIL_Q 512   // the resident kernels take over at <= this many indices per circuit
 #ifdef TAIL_PHASE_CLOCK   // tools/tail_phase_bench.hip: workgroup 0 stamps the 100 MHz wall clock at the phase boundaries of each of its first 16 turns
 __device__ uint64_t tail_phase_clock[16 * 8];
 #define TAIL_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x == 0 && turn < 16) tail_phase_clock[turn * 8 + (k)] = wall_clock64(); } while (0)

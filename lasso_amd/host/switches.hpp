@@ -1,6 +1,6 @@
 // Every LASSO_* environment variable the HOST sources read (prover.hpp, prover_capi.cpp, field52.hpp), one line each: name, default, meaning.  A switch is read once per
 // process, on first use (tests change one per child process); on / off goes by the first character: "0" switches a default-on switch off, "1" a default-off one on.
-// They select WHERE and WHEN the same field arithmetic runs: no setting changes a byte of a proof.  The device library's own switches (lasso_amd/csrc/lasso_hip.hip) are not listed.
+// They select WHERE and WHEN the same field arithmetic runs: no setting changes a byte of a proof.  The device library's own switches are listed in the same way in lasso_amd/csrc/device_switches.cuh.
 #pragma once
 #include <cstdlib>
 

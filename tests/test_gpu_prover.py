@@ -192,7 +192,11 @@ print("DIGEST", hashlib.sha256(comm + proof).hexdigest())
                                  {"LASSO_BULLET_TAIL_AHEAD": "0"},           # round 6: the openings' last fold, heads and delta MSM as separate calls instead of one chain enqueued ahead
                                  {"LASSO_BULLET_TAIL_AHEAD": "0", "LASSO_MSM_TAGGED": "0"},
                                  {"LASSO_MSM_FULL8": "1"},                   # round 6: full-width commitments over the signed byte-multiple table instead of the bucket kernel (measured, not the default)
-                                 {"LASSO_MSM_ROWS8W_WAVES": "2048"}, {"LASSO_MSM_ROWS8W": "0"}])   # round 6: several rows per wave in the one-wave-per-row commitment (measured, not the default); the 256-lane form
+                                 {"LASSO_MSM_ROWS8W_WAVES": "2048"}, {"LASSO_MSM_ROWS8W": "0"},    # round 6: several rows per wave in the one-wave-per-row commitment (measured, not the default); the 256-lane form
+                                 {"LASSO_CUBIC_WIDE": "0"},                  # the two-sum fused round without its double-width accumulators
+                                 {"LASSO_LB_NT": "1"},                       # non-temporal loads of A and B in the evaluation-only round (measured, not the default)
+                                 {"LASSO_MSM_ROWS8": "0"},                   # the commitments of small scalars by the bucket kernel instead of the byte-multiple tables
+                                 {"LASSO_AHEAD_INKERNEL_WGS": "0"}, {"LASSO_AHEAD_INKERNEL_WGS": "64"}])   # a round launched ahead waits behind the gate kernel always / inside its own kernel up to 64 workgroups
 def test_gpu_ab_switches_do_not_change_the_bytes(host, env):
     """The A/B switches the measurements in DESIGN.md rest on (flag protocol instead of tagged results, in-launch second stage, launch per round instead of the resident tails, ...)
     select other kernels / protocols for the same arithmetic: commitment and proof must be the bytes of the default configuration.  Each setting runs in its own process
