@@ -25,7 +25,7 @@ CURVES = {"curve25519": ("", []), "bn254": ("_bn254", ["-DLASSO_BN254", "-Wl,-Bs
 
 def build_device(force=False, verbose=False, curve="curve25519"):
     """liblasso_hip.so: hand-written gfx950 kernels behind include/lasso_hip.h.  curve="bn254" builds the same kernels over ark-bn254's
-    Fr / G1 (csrc/bn254_*.cuh, mont29.cuh) into liblasso_hip_bn254.so — same C ABI, same symbol names, loaded side by side (RTLD_LOCAL)."""
+    Fr / G1 (the BN254 traits of csrc/bn254_fr.cuh and fr29.cuh, bn254_fq.cuh, bn254_fe29.cuh, over mont32.cuh / mont29.cuh) into liblasso_hip_bn254.so — same C ABI, same symbol names, loaded side by side (RTLD_LOCAL)."""
     suffix, flags = CURVES[curve]
     csrc = os.path.join(HERE, "csrc")
     target = os.path.join(HERE, f"liblasso_hip{suffix}.so")

@@ -1,7 +1,8 @@
-// A 254-bit prime field in nine signed 29-bit limbs with Montgomery radix 2^261, for a GENERAL modulus (all nine limbs of p non-zero).
-// fr29.cuh / fe29.cuh are the curve25519 instances, shaped around the sparse moduli 2^252 + c and 2^255 - 19; this header carries the same
-// carry-free column arithmetic (81 back-to-back v_mad_i64_i32 per product, see fr29.cuh) to the BN254 fields (ark-bn254's Fr and Fq, the
-// group BASELINE.json's configs[1] names), where the reduction is nine full rows (81 more multiply-adds) and the quotient estimates of the
+// A prime field below 2^255 in nine signed 29-bit limbs with Montgomery radix 2^261, as templates over a modulus trait M.  The instances: fr29.cuh
+// (Fr of curve25519, whose sparse modulus 2^252 + c specialises the four lazy reductions, and ark-bn254's Fr) and bn254_fe29.cuh (ark-bn254's Fq, the
+// group BASELINE.json's configs[1] names); fe29.cuh (2^255 - 19) is pseudo-Mersenne and not an instance.  The product is carry-free column
+// arithmetic (81 back-to-back v_mad_i64_i32, see fr29.cuh); for a GENERAL modulus (all nine limbs of p non-zero) the reduction is nine full
+// rows (81 more multiply-adds; zero limbs and powers of two of a sparse p fold away in the same loop) and the quotient estimates of the
 // lazy reductions come from a reciprocal instead of a shift.
 //
 // value(a) = sum a.v[k] * 2^(29k), limbs signed, lazily reduced:
@@ -9,7 +10,8 @@
 //   "loose":   |limb| <= 2^30
 // m29_mul(a, b) = a*b / 2^261 (mod p); requires |a.v| <= 2^30, |b.v| <= 2^29.  |a*b| < X * 2^261  =>  result in (-X, p + X), reduced.
 //   (column bound: nine products < 2^59 plus nine reduction terms < 2^58 plus a carry < 2^35: below 2^62.8.)
-// M supplies: p(k) (29-bit limbs of p), PINV (-p^-1 mod 2^29), QC = floor(2^284 / p), and the limbs of ONE_S = 2^261 and K522 = 2^522 (mod p).
+// M supplies: p(k) (29-bit limbs of p), PINV (-p^-1 mod 2^29), the limbs of ONE_S = 2^261 (mod p) and, unless it specialises the reductions that use them,
+// QC = floor(2^284 / p) and the limbs of K522 = 2^522 (mod p).
 #pragma once
 #include <stdint.h>
 
@@ -28,6 +30,9 @@ template <class M> struct m29 { int32_t v[9]; };
 template <class M> LHD m29<M> m29_zero() { m29<M> r;
 #pragma unroll
   for (int i = 0; i < 9; i++) r.v[i] = 0; return r; }
+template <class M> LHD m29<M> m29_limbs(int32_t a0, int32_t a1, int32_t a2, int32_t a3, int32_t a4, int32_t a5, int32_t a6, int32_t a7, int32_t a8) {
+  m29<M> r; r.v[0] = a0; r.v[1] = a1; r.v[2] = a2; r.v[3] = a3; r.v[4] = a4; r.v[5] = a5; r.v[6] = a6; r.v[7] = a7; r.v[8] = a8; return r;
+}
 template <class M> LHD m29<M> m29_add(const m29<M>& a, const m29<M>& b) { m29<M> r;
 #pragma unroll
   for (int i = 0; i < 9; i++) r.v[i] = a.v[i] + b.v[i]; return r; }

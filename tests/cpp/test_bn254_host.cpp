@@ -1,4 +1,4 @@
-// CPU check of the BN254 build of the product's arithmetic headers (lasso_amd/csrc/bn254_*.cuh + mont29.cuh, selected by -DLASSO_BN254)
+// CPU check of the BN254 build of the product's arithmetic headers (lasso_amd/csrc/bn254_fr.cuh, fr29.cuh, bn254_fq.cuh, bn254_fe29.cuh over mont32.cuh / mont29.cuh, selected by -DLASSO_BN254)
 // against the oracle's independent 64-bit arithmetic and Jacobian group law (oracle/ff.hpp, bn254.hpp under -DORC_BN254).
 // Test-only: links oracle code as the checker.
 #include "../../lasso_amd/csrc/fe29.cuh"

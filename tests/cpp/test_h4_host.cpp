@@ -1,5 +1,5 @@
 // lasso_amd/host/field_host.hpp: the host-only 64-bit additions (fr_add_host / fr_sub_host) and the plain 4 x u64 form of the field the host's finishing rounds compute in
-// (H4: h4_add / h4_sub / h4_mul) against the shared arithmetic the device executes (fr_add / fr_sub / fr_mul, lasso_amd/csrc/fr.cuh, bn254_fr.cuh), on random and edge values.
+// (H4: h4_add / h4_sub / h4_mul) against the shared arithmetic the device executes (fr_add / fr_sub / fr_mul, lasso_amd/csrc/fr.cuh over mont32.cuh), on random and edge values.
 #include <cstdio>
 #include <cstring>
 #include "../../lasso_amd/host/field_host.hpp"

@@ -15,7 +15,7 @@ def build_mock_prover_msm(curve="curve25519"):
     bn = curve == "bn254"
     so = os.path.join(out_dir, "liblasso_prover_mock_msm_bn254.so" if bn else "liblasso_prover_mock_msm.so")
     srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
+    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
     srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
     srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_hip_msm.h", "lasso_prover.h")]
     wrap = os.path.join(ROOT, "tests", "cpp", "mock_msm_points_wrap.cpp")

@@ -1,5 +1,5 @@
 """-m gpu: the BN254 build of the HIP path (liblasso_prover_bn254.so over liblasso_hip_bn254.so: the same kernels over ark-bn254's Fr / G1,
-csrc/bn254_*.cuh + mont29.cuh) against the oracle's BN254 instantiation — G = BN254 is the group BASELINE.json's configs[1] names.
+csrc/bn254_fr.cuh, fr29.cuh, bn254_fq.cuh, bn254_fe29.cuh over mont32.cuh / mont29.cuh) against the oracle's BN254 instantiation — G = BN254 is the group BASELINE.json's configs[1] names.
 Commitment and proof bytes identical to the oracle prover's; at configs[1]'s full size the reference's own acceptance property
 prove -> verify (src/e2e_test.rs:54-59) through the oracle verifier, tamper rejection and determinism."""
 import ctypes as C

@@ -27,7 +27,7 @@ def test_cpp_arith(name, flags):
 @pytest.mark.parametrize("name", ["test_bn254_host", "test_fr29_host"])
 @pytest.mark.parametrize("flags", [[], ["-DLASSO_HOST_LIMBS32"]], ids=["limbs64", "limbs32"])
 def test_cpp_arith_bn254(name, flags):
-    """The BN254 build of the same headers (-DLASSO_BN254: bn254_*.cuh over mont29.cuh) against the oracle's BN254 instantiation."""
+    """The BN254 build of the same headers (-DLASSO_BN254: the BN254 traits of bn254_fr.cuh / fr29.cuh, bn254_fq.cuh, bn254_fe29.cuh, over mont32.cuh / mont29.cuh) against the oracle's BN254 instantiation."""
     src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
     out_dir = os.path.join(ROOT, "tests", "_build")
     os.makedirs(out_dir, exist_ok=True)
@@ -52,6 +52,66 @@ def test_limb_bounds_hold_under_ubsan(name, flags):
     res = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     assert res.returncode == 0 and "runtime error" not in res.stderr, res.stdout[-1000:] + res.stderr[-3000:]
     assert "OK" in res.stdout
+
+
+MODULI = {
+    "Curve25519Fr": 2**252 + 27742317777372353535851937790883648493,
+    "Bn254Fr": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
+    "Bn254Fq": 21888242871839275222246405745257275088696311157297823662689037894645226208583,
+}
+# trait -> (field, the constants it must print): the 8 x u32 form (mont32.cuh) and the nine-29-bit-limb form (mont29.cuh)
+TRAITS = {
+    "curve25519": {"Curve25519FrM32": ("Curve25519Fr", {"p", "INV32", "INV64", "WRAPS", "ONE", "R2"}),
+                   "Curve25519FrM": ("Curve25519Fr", {"p", "PINV", "ONE_S", "K5", "K10", "R2S"})},   # its reductions take the quotient from a shift: no QC, no K522
+    "bn254": {"Bn254FrM32": ("Bn254Fr", {"p", "INV32", "INV64", "WRAPS", "ONE", "R2"}),
+              "Bn254FqM32": ("Bn254Fq", {"p", "INV32", "INV64", "WRAPS", "ONE", "R2"}),
+              "Bn254FrM": ("Bn254Fr", {"p", "PINV", "ONE_S", "QC", "K522", "K5", "K10", "R2S"}),
+              "Bn254FqM": ("Bn254Fq", {"p", "PINV", "ONE_S", "QC", "K522"})},
+}
+
+
+@pytest.mark.parametrize("curve", ["curve25519", "bn254"])
+def test_field_trait_constants(curve):
+    """Every constant of every modulus trait (tests/cpp/test_field_traits_host.cpp prints them as integers) against Python's big integers: both limb forms spell
+    the same p; INV32 / INV64 / PINV = -p^-1 mod 2^32 / 2^64 / 2^29; ONE, R2 = 2^256, 2^512 mod p; ONE_S, K522, K5, K10, R2S = 2^261, 2^522, 2^266, 2^271, 2^517 mod p;
+    QC = floor(2^284 / p); 2^256 < WRAPS p.  The program runs a second time under UBSan."""
+    flags = ["-DLASSO_BN254"] if curve == "bn254" else []
+    src = os.path.join(ROOT, "tests", "cpp", "test_field_traits_host.cpp")
+    out_dir = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    outputs = []
+    for tag, opt in (("", ["-O2"]), ("_ubsan", ["-O1", "-fsanitize=undefined", "-fno-sanitize-recover=undefined"])):
+        exe = os.path.join(out_dir, "test_field_traits_" + curve + tag)
+        subprocess.check_call(["g++", *opt, "-std=c++17", "-Wno-unknown-pragmas", *flags, "-o", exe, src])
+        res = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+        assert res.returncode == 0 and "runtime error" not in res.stderr and res.stdout.rstrip().endswith("OK"), res.stdout[-2000:] + res.stderr[-2000:]
+        outputs.append(res.stdout)
+    assert outputs[0] == outputs[1]
+    got = {}
+    for line in outputs[0].splitlines()[:-1]:
+        name, value = line.split(" = ")
+        trait, const = name.split(".")
+        assert const not in got.setdefault(trait, {}), line
+        got[trait][const] = int(value, 16)
+    assert {t: set(c) for t, c in got.items()} == {t: names for t, (_, names) in TRAITS[curve].items()}
+    power_of_two = {"ONE": 256, "R2": 512, "ONE_S": 261, "K522": 522, "K5": 266, "K10": 271, "R2S": 517}
+    neg_inverse_mod = {"INV32": 32, "INV64": 64, "PINV": 29}
+    for trait, (field, _) in TRAITS[curve].items():
+        p = MODULI[field]
+        for const, v in got[trait].items():
+            where = f"{trait}.{const} = {v:#x}"
+            if const == "p":
+                assert v == p, where
+            elif const in power_of_two:
+                assert v == pow(2, power_of_two[const], p), where
+            elif const in neg_inverse_mod:
+                assert v == -pow(p, -1, 2**neg_inverse_mod[const]) % 2**neg_inverse_mod[const], where
+            elif const == "QC":
+                assert v == 2**284 // p, where
+            elif const == "WRAPS":
+                assert 2**256 < v * p, where
+            else:
+                raise AssertionError("unchecked constant " + where)
 
 
 def extract_poly_math(dst):

@@ -293,7 +293,7 @@ def build_mock_prover_wire(curve="curve25519"):
     bn = curve == "bn254"
     so = os.path.join(out_dir, "liblasso_prover_mock_wire_bn254.so" if bn else "liblasso_prover_mock_wire.so")
     srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("fr.cuh", "fq.cuh", "fe29.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "bn254_fe29.cuh", "mont29.cuh")]
+    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "fe29.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "bn254_fe29.cuh", "mont29.cuh")]
     srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
     srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_prover.h", "lasso_custom_check.h")]
     wrap = os.path.join(ROOT, "tests", "cpp", "mock_wire_wrap.cpp")
