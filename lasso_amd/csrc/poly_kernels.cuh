@@ -71,8 +71,10 @@ __device__ __forceinline__ void acc_add(fr29& acc, const fr29& t, uint32_t& coun
 }
 // ------------------------------------------------------------------ challenges that arrive while the kernel is already running
 // One poll loop of the host-mapped mailbox (lasso_hip.hip post_mail: three self-validating 16-byte chunks [tag, w, w, w] [tag, w, w, w] [tag, w, w, check]; the host writes each with one
-// aligned 16-byte store and a PCIe read of an aligned 16 bytes is one transaction, so when all three carry the expected tag and the check word agrees the eight words are that message's).
-// Returns false on lasso_abort's poison tag or when the wall clock passes t_end (a host that never answers cannot hang the device).  ONE lane calls it.
+// aligned 16-byte store and a PCIe read of an aligned 16 bytes is one transaction, so when all three carry the expected tag and the check word agrees the eight words are that message's:
+// ONE read round trip per poll — eight dependent 4-byte reads of host memory cost 12 us).  A resident tail's tag is the sequence number of the publication the message enables: unique per
+// context, never reset.  Returns false on lasso_abort's poison tag or when the wall clock passes t_end (a host that never answers cannot hang the device).  ONE lane calls it.
+__device__ __forceinline__ uint64_t mail_deadline() { return wall_clock64() + 500000000ull; }   // every wait's t_end: 5 s at 100 MHz from where the kernel starts
 __device__ __forceinline__ bool mail_wait(const uint32_t* mailbox, uint32_t tag, uint64_t t_end, fr_t& chal) {   // no __restrict__ on the mailbox: the host writes it while the kernel polls
   const lasso_u32x4* m4 = reinterpret_cast<const lasso_u32x4*>(mailbox);
   lasso_u32x4 c0, c1, c2; uint32_t spins = 0;
@@ -98,7 +100,7 @@ __device__ __forceinline__ bool mail_wait(const uint32_t* mailbox, uint32_t tag,
 // to 512 lanes hammering one cache line; queued kernels follow each other without a measurable gap, so the gate costs nothing of the kind and occupies one wave, not the chip.
 __global__ void __launch_bounds__(64) k_gate(const uint32_t* mail, uint32_t* gmail, uint32_t seq, uint32_t pair) {   // no __restrict__: the host writes the mailbox while this polls
   if (threadIdx.x != 0) return;
-  const uint64_t t_end = wall_clock64() + 500000000ull;   // 5 s at 100 MHz
+  const uint64_t t_end = mail_deadline();
   fr_t c0, c1;
   bool ok = mail_wait(mail, seq, t_end, c0);
   if (ok && pair) ok = mail_wait(mail + 12, seq, t_end, c1);
@@ -113,7 +115,7 @@ __global__ void __launch_bounds__(64) k_gate(const uint32_t* mail, uint32_t* gma
 // republishes the scalar in gmail[0..8) behind the tag gmail[16]; the others wait on that tag.  gmail[17] = tag: no challenge (poison / 5 s), everybody leaves.  s_mail = 9 words.
 __device__ __forceinline__ bool ahead_challenge(const uint32_t* mail, uint32_t* gmail, uint32_t seq, fr_t& r, uint32_t* s_mail) {
   if (threadIdx.x == 0) {
-    const uint64_t t_end = wall_clock64() + 500000000ull;   // 5 s at 100 MHz
+    const uint64_t t_end = mail_deadline();
     uint32_t ok = 1, spins = 0;
     if (blockIdx.x == 0) {
       fr_t c;
@@ -164,7 +166,7 @@ __device__ __forceinline__ bool gated_challenge(const uint32_t* gmail, uint32_t 
                                   // host knows the one mailbox area is free for the next gate's message (cancel -> begin -> post could overwrite a message no gate had read yet)
 __global__ void __launch_bounds__(64) k_gate_point(const uint32_t* pmail, uint32_t* gpoint, uint32_t seq, uint32_t nfr, uint32_t* ack) {   // no __restrict__: the host writes pmail while this polls
   const uint32_t t = threadIdx.x;
-  const uint64_t t_end = wall_clock64() + 500000000ull;   // 5 s at 100 MHz
+  const uint64_t t_end = mail_deadline();
   bool ok = true; fr_t v = fr_zero();
   if (t < nfr) {
     ok = mail_wait(pmail + 12 * t, seq, t_end, v);
@@ -624,6 +626,35 @@ __device__ uint64_t tail_phase_clock[16 * 8];
 #else
 #define TAIL_STAMP(k) do { } while (0)
 #endif
+// The two sums of a resident tail's turn, by every thread of the workgroup (barriers inside): rows[(v * h + i) * 9 + k] = limb k of term i < h of sum v -> cols[v * 9 + k] (eight strips
+// of rows per (sum, limb) column, then the strips), and lanes 0 and 1 publish sum v times 2^shift as result 2 y + v of turn `turn`.
+__device__ __forceinline__ void tail_sums_publish(const int32_t* rows, int64_t* strips, int64_t* cols, uint32_t h, int shift, fr_t* out, uint32_t y, uint32_t* flag, uint32_t seq0, uint32_t turn) {
+  const uint32_t t = threadIdx.x;
+  if (h > 16) {
+    if (t < 8 * 18) {
+      const uint32_t col = t % 18, strip = t / 18, v = col / 9, k = col - v * 9;
+      const uint32_t per = (h + 7) / 8, i0 = strip * per, i1 = i0 + per < h ? i0 + per : h;
+      int64_t sum = 0;
+      for (uint32_t i = i0; i < i1; i++) sum += rows[(v * h + i) * 9 + k];
+      strips[strip * 18 + col] = sum;
+    }
+    __syncthreads();
+    if (t < 18) { int64_t sum = 0; for (int g = 0; g < 8; g++) sum += strips[g * 18 + t]; cols[t] = sum; }
+  } else if (t < 18) {   // a handful of rows: one pass
+    const uint32_t v = t / 9, k = t - v * 9;
+    int64_t sum = 0;
+    for (uint32_t i = 0; i < h; i++) sum += rows[(v * h + i) * 9 + k];
+    cols[t] = sum;
+  }
+  __syncthreads();
+  TAIL_STAMP(2);
+  if (t < 2) {
+    int64_t c[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) c[k] = cols[t * 9 + k];
+    result_store(out, (size_t)y * 2 + t, fr29_pack(fr29_reduce_columns(c, shift)), flag, seq0 + turn);
+  }
+}
 // EQI (first round of a layer only): the eq table is never materialised — the two factor tables are built in LDS (eq_inline_build, <= 32 entries each at q <= 512) and
 // every use of E[i] is one product.
 // m_stop (round 5): the kernel stops when the arrays are down to m_stop elements each and its LAST publication carries the arrays — out[(p * ncirc + c) * m_stop + i] = (p ? B : A)_c[i] —
@@ -650,7 +681,7 @@ __global__ void __launch_bounds__(Q) k_cubic_tail(TM A, TM B, const fr_t* __rest
   __shared__ fr_t chal;
   __shared__ uint32_t alive;
   const uint32_t t = threadIdx.x, y = blockIdx.x, ncirc = gridDim.x;
-  const uint64_t t_end = wall_clock64() + 500000000ull;   // 5 s at 100 MHz
+  const uint64_t t_end = mail_deadline();
   uint32_t m = 2 * q;
   {
     // every lane task (array p, index i) loads / binds its element and, for A, weights it with the eq table right away (no separate pass).  2 m <= 4 Q lane tasks: all of a
@@ -692,30 +723,7 @@ __global__ void __launch_bounds__(Q) k_cubic_tail(TM A, TM B, const fr_t* __rest
     }
     __syncthreads();
     TAIL_STAMP(1);
-    if (h > 16) {   // eight strips of rows per (sum, limb) column, then the strips
-      if (t < 8 * 18) {
-        const uint32_t col = t % 18, strip = t / 18, v = col / 9, k = col - v * 9;
-        const uint32_t per = (h + 7) / 8, i0 = strip * per, i1 = i0 + per < h ? i0 + per : h;
-        int64_t sum = 0;
-        for (uint32_t i = i0; i < i1; i++) sum += rows[(v * h + i) * 9 + k];
-        strips[strip * 18 + col] = sum;
-      }
-      __syncthreads();
-      if (t < 18) { int64_t sum = 0; for (int g = 0; g < 8; g++) sum += strips[g * 18 + t]; cols[t] = sum; }
-    } else if (t < 18) {   // a handful of rows: one pass
-      const uint32_t v = t / 9, k = t - v * 9;
-      int64_t sum = 0;
-      for (uint32_t i = 0; i < h; i++) sum += rows[(v * h + i) * 9 + k];
-      cols[t] = sum;
-    }
-    __syncthreads();
-    TAIL_STAMP(2);
-    if (t < 2) {
-      int64_t c[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) c[k] = cols[t * 9 + k];
-      result_store(out, (size_t)y * 2 + t, fr29_pack(fr29_reduce_columns(c, 5)), flag, seq0 + turn);
-    }
+    tail_sums_publish(rows, strips, cols, h, 5, out, y, flag, seq0, turn);   // (TAIL_STAMP(2) between the sums and the publication); u * u products: 2^5 short
     row_done(ncirc, counters, flag, seq0 + turn);
     TAIL_STAMP(3);
     // everything of the coming bind that does not depend on the challenge, while it travels: the pair (lo, hi - lo) of every lane task and the eq weight of the A tasks
@@ -731,26 +739,7 @@ __global__ void __launch_bounds__(Q) k_cubic_tail(TM A, TM B, const fr_t* __rest
       }
     }
     // the host's answer: the round's challenge
-    if (t == 0) {
-      // three self-validating 16-byte chunks [turn, w, w, w]: the host writes each with one aligned 16-byte store and a PCIe read of an aligned
-      // 16 bytes is one transaction, so when all three carry this turn's number the eight challenge words are this turn's — ONE read round trip
-      // per poll (eight dependent 4-byte reads of host memory cost 12 us)
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4* m4 = reinterpret_cast<const u32x4*>(mailbox);
-      uint32_t ok = 1; u32x4 c0, c1, c2; uint32_t spins = 0;
-      for (;;) {
-#ifndef LASSO_NO_POLL_FENCE
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // nothing cached from the previous poll
-#else
-        asm volatile("" ::: "memory");
-#endif
-        c0 = __builtin_nontemporal_load(m4); c1 = __builtin_nontemporal_load(m4 + 1); c2 = __builtin_nontemporal_load(m4 + 2);   // three 16-byte reads in flight together
-        if (mail_valid(c0, c1, c2, seq0 + turn + 1)) break;   // tagged with the sequence number of the publication it enables: unique per context, never reset
-        if (c0.x == LASSO_MAIL_POISON || ((++spins & 63u) == 0 && wall_clock64() > t_end)) { ok = 0; break; }   // lasso_abort's tag, or the host stopped answering
-      }
-      if (ok) { chal.v[0] = c0.y; chal.v[1] = c0.z; chal.v[2] = c0.w; chal.v[3] = c1.y; chal.v[4] = c1.z; chal.v[5] = c1.w; chal.v[6] = c2.y; chal.v[7] = c2.z; }
-      alive = ok;
-    }
+    if (t == 0) alive = mail_wait(mailbox, seq0 + turn + 1, t_end, chal) ? 1u : 0u;
     __syncthreads();
     if (!alive) return;
     TAIL_STAMP(4);
@@ -778,8 +767,6 @@ __global__ void __launch_bounds__(Q) k_cubic_tail(TM A, TM B, const fr_t* __rest
     }
   }
 }
-
-
 #undef TAIL_EQ_S
 // ------------------------------------------------------------------ K3 in eq-weighted form for the linear strategies (AND / OR / XOR / RangeCheck)
 // prove_arbitrary's comb_func is g(E_1..E_alpha) * eq with g = sum_k w_k E_k LINEAR (and.rs:45-53, range_check.rs:78-86) and eq = EqPolynomial(r).evals()
@@ -787,99 +774,79 @@ __global__ void __launch_bounds__(Q) k_cubic_tail(TM A, TM B, const fr_t* __rest
 // only two dot products against the table prefix:  S0_k = sum_{i<half} E_k[i] eq[i],  S1_k = sum_{i<half} E_k[i+half] eq[i];  the host forms
 // G(x) = sum_k w_k (S0_k + x (S1_k - S0_k)) and e(x) = s_j * eq1(r_j, x) / prod_{t<=j}(1 - r_t) * G(x) at x = 0, 1, 2.  No weight products, no eq
 // binding, and the bind of the previous challenge rides in the same launch.  out[3k + {0,1}] = S0_k, S1_k (slot 2 unused).  Grid = cubic_grid(nx, alpha).
-__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_lb(PtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t half, fr_t* __restrict__ partials, uint32_t* counters,
-                                                             fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) {
-  __shared__ RedScratch S;
-  const CubicGrid g = cubic_grid(nx, ny);
-  const fr_t* __restrict__ z = polys.p[g.by];
-  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;   // two dot products: double-width accumulation (fr29_mul_acc)
-  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < half; i += (size_t)nx * blockDim.x) {
-    const fr29 es = fr29_unpack_s(E[i]);
-    fr29_mul_acc(w0, fr29_unpack_u(z[i]), es);
-    fr29_mul_acc(w1, fr29_unpack_u(z[i + half]), es);
-    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }
-  }
-  fr29_acc_carry(w0); fr29_acc_carry(w1);
-  fr29 e[3] = {fr29_acc_reduce(w0), fr29_acc_reduce(w1), fr29_zero()};
-  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
-}
-// src != polys: the bind reads src (length 4q) and writes the bound halves to polys — the first bind of the primary sumcheck takes E itself as
-// src, so surge.rs:151's clone of the lookup polynomials never happens (the sumcheck must not modify E, which the later openings read)
-// AHEAD: launched before the host had the challenge, behind a gate kernel (k_gate) that leaves it in gmail
-template <bool AHEAD = false>
-__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_fused(PtrTable src, MutPtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t q, fr_t r, fr_t* __restrict__ partials, uint32_t* counters,
-                                                                fr_t* __restrict__ out, uint32_t* flag, uint32_t seq, const uint32_t* gmail = nullptr) {
-  __shared__ RedScratch S;
-  const CubicGrid g = cubic_grid(nx, ny);
-  fr_t* zd = polys.p[g.by];          // may alias z (in-place call): every thread reads its four elements before it writes its two
-  const fr_t* z = src.p[g.by];
-  if constexpr (AHEAD) {
-    __shared__ uint32_t s_mail[17];
-    if (!gated_challenge(gmail, seq, 8, s_mail)) return;
-#pragma unroll
-    for (int k = 0; k < 8; k++) r.v[k] = s_mail[k];
-  }
-  const fr29 rs = fr29_unpack_s(r);
-  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;
-  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < q; i += (size_t)nx * blockDim.x) {
-    const fr29 z0 = bind29(z[i], z[i + 2 * q], rs), z1 = bind29(z[i + q], z[i + 3 * q], rs);
-    zd[i] = fr29_pack(z0); zd[i + q] = fr29_pack(z1);
-    const fr29 es = fr29_unpack_s(E[i]);
-    fr29_mul_acc(w0, z0, es);
-    fr29_mul_acc(w1, z1, es);
-    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }
-  }
-  fr29_acc_carry(w0); fr29_acc_carry(w1);
-  fr29 e[3] = {fr29_acc_reduce(w0), fr29_acc_reduce(w1), fr29_zero()};
-  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
-}
-// The same two rounds from the lookup polynomials' INTEGER values (round 3).  E_k = T[dim] holds table entries — small integers the prover has as u32 anyway (the commitment
-// of E is made from them) — so the primary sumcheck's first round and first bind need not stream the 32-byte field form: 4 bytes per element instead of 32, and a product with a
-// two-limb operand is 18 multiply-adds instead of 81.  Same field elements: sum_i F(x_i) eq_i and F(lo) + r (F(hi) - F(lo)), F = Fr::from.
+// Both rounds exist in two forms, ONE body each over how an element is read and bound (the overloads below, chosen by the table's element type):
+//   PtrTable: the 32-byte field form;
+//   PtrTableU32 (round 3): the lookup polynomials' INTEGER values.  E_k = T[dim] holds table entries — small integers the prover has as u32 anyway (the commitment of E is made
+//   from them) — so the primary sumcheck's first round and first bind need not stream the field form: 4 bytes per element instead of 32, and a product with a two-limb operand is
+//   18 multiply-adds instead of 81.  Same field elements: sum_i F(x_i) eq_i and F(lo) + r (F(hi) - F(lo)), F = Fr::from.
+// (Macros, like CUBIC_ACCUMULATE: as functions the bodies move 15 - 21 instructions in each of the four kernels — the loop's blockDim.x is then folded no earlier than the epilogue's — and cost k_dot_eqw_fused_from_u32 three VGPRs.)
 struct PtrTableU32 { const uint32_t* p[LASSO_MAX_PTRS]; };
-__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_lb_u32(PtrTableU32 polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t half, fr_t* __restrict__ partials, uint32_t* counters,
-                                                                 fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) {
-  __shared__ RedScratch S;
-  const CubicGrid g = cubic_grid(nx, ny);
-  const uint32_t* __restrict__ z = polys.p[g.by];
-  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;
-  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < half; i += (size_t)nx * blockDim.x) {
-    const fr29 es = fr29_unpack_s(E[i]);
-    fr29_mul_acc(w0, fr29_from_u64_int(z[i]), es);          // integer * s-form: after the reduction the plain residue sum x_i eq_i
-    fr29_mul_acc(w1, fr29_from_u64_int(z[i + half]), es);
-    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }
-  }
-  fr29_acc_carry(w0); fr29_acc_carry(w1);
-  const fr29 r2s = fr29_r2s();   // 2^517: brings the thread's plain sum into memory (u-) form, once per thread
-  fr29 e[3] = {fr29_mul(fr29_acc_reduce(w0), r2s), fr29_mul(fr29_acc_reduce(w1), r2s), fr29_zero()};
-  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
-}
+__device__ __forceinline__ fr29 dot_elem(const fr_t& x) { return fr29_unpack_u(x); }
+__device__ __forceinline__ fr29 dot_elem(uint32_t x) { return fr29_from_u64_int(x); }   // integer * s-form: after the reduction the plain residue sum x_i eq_i
+__device__ __forceinline__ fr29 dot_sum(const fr29& s, const fr29&, const fr_t*) { return s; }
+__device__ __forceinline__ fr29 dot_sum(const fr29& s, const fr29& r2s, const uint32_t*) { return fr29_mul(s, r2s); }   // r2s = 2^517 brings the thread's plain sum into memory (u-) form, once per thread
 // F(lo) + r (F(hi) - F(lo)) for 32-bit integers lo, hi: two products with a two-limb operand; rx = r * 2^517 (so that integer * rx is the u-form of integer * r), canonical result
 __device__ __forceinline__ fr29 bind29_u32(uint32_t lo, uint32_t hi, const fr29& rx, const fr29& r2s) {
   const bool neg = hi < lo; const uint32_t ad = neg ? lo - hi : hi - lo;
   const fr29 t = fr29_mul(fr29_from_u64_int(ad), rx), l = fr29_mul(fr29_from_u64_int(lo), r2s);
   return fr29_canonical(neg ? fr29_sub(l, t) : fr29_add(l, t));
 }
-__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_fused_from_u32(PtrTableU32 src, MutPtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t q, fr_t r, fr_t* __restrict__ partials,
-                                                                         uint32_t* counters, fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) {
-  __shared__ RedScratch S;
-  const CubicGrid g = cubic_grid(nx, ny);
-  fr_t* __restrict__ zd = polys.p[g.by];
-  const uint32_t* __restrict__ z = src.p[g.by];
-  const fr29 r2s = fr29_r2s(), rx = fr29_mul(fr29_unpack_s(r), r2s);
-  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;
-  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < q; i += (size_t)nx * blockDim.x) {
-    const fr29 z0 = bind29_u32(z[i], z[i + 2 * q], rx, r2s), z1 = bind29_u32(z[i + q], z[i + 3 * q], rx, r2s);
-    zd[i] = fr29_pack(z0); zd[i + q] = fr29_pack(z1);
-    const fr29 es = fr29_unpack_s(E[i]);
-    fr29_mul_acc(w0, z0, es);
-    fr29_mul_acc(w1, z1, es);
-    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }
-  }
-  fr29_acc_carry(w0); fr29_acc_carry(w1);
-  fr29 e[3] = {fr29_acc_reduce(w0), fr29_acc_reduce(w1), fr29_zero()};
-  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
+__device__ __forceinline__ fr29 dot_bind(const fr_t& lo, const fr_t& hi, const fr29& rs, const fr29&) {
+  return bind29(lo, hi, rs);
 }
+__device__ __forceinline__ fr29 dot_bind(uint32_t lo, uint32_t hi, const fr29& rx, const fr29& r2s) { return bind29_u32(lo, hi, rx, r2s); }
+#define DOT_EQW_LB_BODY                                                                                                                      \
+  __shared__ RedScratch S;                                                                                                                   \
+  const CubicGrid g = cubic_grid(nx, ny);                                                                                                    \
+  const auto* z = polys.p[g.by];                                                                                                             \
+  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;   /* two dot products: double-width accumulation (fr29_mul_acc) */   \
+  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < half; i += (size_t)nx * blockDim.x) {                                         \
+    const fr29 es = fr29_unpack_s(E[i]);                                                                                                     \
+    fr29_mul_acc(w0, dot_elem(z[i]), es);                                                                                                    \
+    fr29_mul_acc(w1, dot_elem(z[i + half]), es);                                                                                             \
+    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }                                                                     \
+  }                                                                                                                                          \
+  fr29_acc_carry(w0); fr29_acc_carry(w1);                                                                                                    \
+  const fr29 r2s = fr29_r2s();                                                                                                               \
+  fr29 e[3] = {dot_sum(fr29_acc_reduce(w0), r2s, z), dot_sum(fr29_acc_reduce(w1), r2s, z), fr29_zero()};                                     \
+  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
+__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_lb(PtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t half, fr_t* __restrict__ partials, uint32_t* counters,
+                                                             fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) { DOT_EQW_LB_BODY }
+__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_lb_u32(PtrTableU32 polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t half, fr_t* __restrict__ partials, uint32_t* counters,
+                                                                 fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) { DOT_EQW_LB_BODY }
+#undef DOT_EQW_LB_BODY
+// src != polys: the bind reads src (length 4q) and writes the bound halves to polys — the first bind of the primary sumcheck takes E itself as
+// src, so surge.rs:151's clone of the lookup polynomials never happens (the sumcheck must not modify E, which the later openings read)
+// AHEAD: launched before the host had the challenge, behind a gate kernel (k_gate) that leaves it in GMAIL
+#define DOT_EQW_FUSED_BODY(AHEAD, GMAIL, RS)                                                                                                  \
+  __shared__ RedScratch S;                                                                                                                   \
+  const CubicGrid g = cubic_grid(nx, ny);                                                                                                    \
+  fr_t* zd = polys.p[g.by];          /* may alias z (in-place call): every thread reads its four elements before it writes its two */       \
+  const auto* z = src.p[g.by];                                                                                                               \
+  if constexpr (AHEAD) {                                                                                                                     \
+    __shared__ uint32_t s_mail[17];                                                                                                          \
+    if (!gated_challenge(GMAIL, seq, 8, s_mail)) return;                                                                                     \
+    _Pragma("unroll") for (int k = 0; k < 8; k++) r.v[k] = s_mail[k];                                                                        \
+  }                                                                                                                                          \
+  const fr29 r2s = fr29_r2s(), rs = RS;   /* the bind's scalar, from r (and r2s = 2^517) */                                                  \
+  fr29_acc w0 = fr29_acc_zero(), w1 = fr29_acc_zero(); uint32_t cnt = 0;                                                                     \
+  for (size_t i = g.bx * (size_t)blockDim.x + threadIdx.x; i < q; i += (size_t)nx * blockDim.x) {                                            \
+    const fr29 z0 = dot_bind(z[i], z[i + 2 * q], rs, r2s), z1 = dot_bind(z[i + q], z[i + 3 * q], rs, r2s);                                    \
+    zd[i] = fr29_pack(z0); zd[i + q] = fr29_pack(z1);                                                                                        \
+    const fr29 es = fr29_unpack_s(E[i]);                                                                                                     \
+    fr29_mul_acc(w0, z0, es);                                                                                                                \
+    fr29_mul_acc(w1, z1, es);                                                                                                                \
+    if (++cnt == 3) { fr29_acc_carry(w0); fr29_acc_carry(w1); cnt = 0; }                                                                     \
+  }                                                                                                                                          \
+  fr29_acc_carry(w0); fr29_acc_carry(w1);                                                                                                    \
+  fr29 e[3] = {fr29_acc_reduce(w0), fr29_acc_reduce(w1), fr29_zero()};                                                                       \
+  cubic_epilogue(e, g, partials, counters, out, flag, seq, S, 0);
+template <bool AHEAD = false>
+__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_fused(PtrTable src, MutPtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t q, fr_t r, fr_t* __restrict__ partials, uint32_t* counters,
+                                                                fr_t* __restrict__ out, uint32_t* flag, uint32_t seq, const uint32_t* gmail = nullptr) { DOT_EQW_FUSED_BODY(AHEAD, gmail, fr29_unpack_s(r)) }
+__global__ void __launch_bounds__(LASSO_BLOCK) k_dot_eqw_fused_from_u32(PtrTableU32 src, MutPtrTable polys, uint32_t nx, uint32_t ny, const fr_t* __restrict__ E, size_t q, fr_t r, fr_t* __restrict__ partials,
+                                                                         uint32_t* counters, fr_t* __restrict__ out, uint32_t* flag, uint32_t seq) { DOT_EQW_FUSED_BODY(false, (const uint32_t*)nullptr, fr29_mul(fr29_unpack_s(r), r2s)) }   // rx = r * 2^517
+#undef DOT_EQW_FUSED_BODY
 // The tail of the primary sumcheck for a linear strategy, resident like k_cubic_tail: from q <= CUBIC_TAIL_Q indices per polynomial on, the
 // remaining rounds' two dot products per polynomial (S0_k = sum_{i<h} z[i] E[i], S1_k = sum_{i<h} z[i+h] E[i]) and the binds run out of LDS,
 // challenges arrive through the host mailbox, and the last publication is the heads z_k[0] = E_k(r_z).  One workgroup per polynomial; src is
@@ -894,7 +861,7 @@ __global__ void __launch_bounds__(Q) k_linear_tail(PtrTable src, const fr_t* __r
   __shared__ fr_t chal;
   __shared__ uint32_t alive;
   const uint32_t t = threadIdx.x, y = blockIdx.x, npoly = gridDim.x;
-  const uint64_t t_end = wall_clock64() + 500000000ull;   // 5 s at 100 MHz
+  const uint64_t t_end = mail_deadline();
   uint32_t m = 2 * q;
   {
     const fr29 rs = fr29_unpack_s(r0);
@@ -910,43 +877,9 @@ __global__ void __launch_bounds__(Q) k_linear_tail(PtrTable src, const fr_t* __r
       for (int k = 0; k < 9; k++) rows[u * 9 + k] = term.v[k];
     }
     __syncthreads();
-    if (h > 16) {
-      if (t < 8 * 18) {
-        const uint32_t col = t % 18, strip = t / 18, v = col / 9, k = col - v * 9;
-        const uint32_t per = (h + 7) / 8, i0 = strip * per, i1 = i0 + per < h ? i0 + per : h;
-        int64_t sum = 0;
-        for (uint32_t i = i0; i < i1; i++) sum += rows[(v * h + i) * 9 + k];
-        strips[strip * 18 + col] = sum;
-      }
-      __syncthreads();
-      if (t < 18) { int64_t sum = 0; for (int g = 0; g < 8; g++) sum += strips[g * 18 + t]; cols[t] = sum; }
-    } else if (t < 18) {
-      const uint32_t v = t / 9, k = t - v * 9;
-      int64_t sum = 0;
-      for (uint32_t i = 0; i < h; i++) sum += rows[(v * h + i) * 9 + k];
-      cols[t] = sum;
-    }
-    __syncthreads();
-    if (t < 2) {
-      int64_t c[9];
-#pragma unroll
-      for (int k = 0; k < 9; k++) c[k] = cols[t * 9 + k];
-      result_store(out, (size_t)y * 2 + t, fr29_pack(fr29_reduce_columns(c, 0)), flag, seq0 + turn);   // u * s products: memory form already
-    }
+    tail_sums_publish(rows, strips, cols, h, 0, out, y, flag, seq0, turn);   // u * s products: memory form already
     row_done(npoly, counters, flag, seq0 + turn);
-    if (t == 0) {   // the round's challenge (three self-validating 16-byte chunks, see k_cubic_tail)
-      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-      const u32x4* m4 = reinterpret_cast<const u32x4*>(mailbox);
-      uint32_t ok = 1; u32x4 c0, c1, c2; uint32_t spins = 0;
-      for (;;) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        c0 = __builtin_nontemporal_load(m4); c1 = __builtin_nontemporal_load(m4 + 1); c2 = __builtin_nontemporal_load(m4 + 2);
-        if (mail_valid(c0, c1, c2, seq0 + turn + 1)) break;   // tagged with the sequence number of the publication it enables: unique per context, never reset
-        if (c0.x == LASSO_MAIL_POISON || ((++spins & 63u) == 0 && wall_clock64() > t_end)) { ok = 0; break; }   // lasso_abort's tag, or the host stopped answering
-      }
-      if (ok) { chal.v[0] = c0.y; chal.v[1] = c0.z; chal.v[2] = c0.w; chal.v[3] = c1.y; chal.v[4] = c1.z; chal.v[5] = c1.w; chal.v[6] = c2.y; chal.v[7] = c2.z; }
-      alive = ok;
-    }
+    if (t == 0) alive = mail_wait(mailbox, seq0 + turn + 1, t_end, chal) ? 1u : 0u;   // the host's answer: the round's challenge
     __syncthreads();
     if (!alive) return;
     const fr29 rs = fr29_unpack_s(chal);
@@ -963,7 +896,6 @@ __global__ void __launch_bounds__(Q) k_linear_tail(PtrTable src, const fr_t* __r
     }
   }
 }
-
 
 // ------------------------------------------------------------------ g = S::combine_lookups (subtables/*.rs)
 // AND/OR/XOR (and.rs:45-53) and RangeCheck (range_check.rs:78-86): g = sum_i 2^(i*inc) * vals[i] is LINEAR, so along the line
@@ -1024,14 +956,32 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_linear(StrategyDe
 // indices between two folds of the running sums: a term e * t is below p + |e| |t| / 2^261 <= 3.6 p (18 p * 24 p; BN254's p / 2^261 = 2^-7.4), so 32 of them stay
 // below 2^261 and limb 8 inside the loose bound 2^30 that the fold's product requires
 #define LT_FOLD_EVERY() 32u
-#define LT_REP(M) M(0) M(1) M(2) M(3) M(4) M(5)
+// The per-point steps the LT and the caller-defined round kernel share (a lane's PPG <= 6 points live in NAMED registers sum0.., t0.., v0..: PT_REP(M) is M(k) for every k).  PT_TOP: t_k = the line `cur` stepped by `dif` from point to point; PT_ACC: sum_k += e(x0 + k) * V_k,
+// V = the register family that holds the index's value (t in the LT walk, v in a term list); PT_FOLD: the running sums folded back; PT_OUT: mine[k] = the lane's finished sum k times the block's scale.
+#define PT_REP(M) M(0) M(1) M(2) M(3) M(4) M(5)
+#define PT_TOP(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = cur; cur = lt_line_step(cur, dif); } }
+#define PT_ACC(k, V) if constexpr (k < PPG) { if (x0 + k <= degree) { sum##k = lt_weighted_acc(sum##k, ecur, V##k); ecur = lt_line_step(ecur, edif); } }
+#define PT_FOLD(k) if constexpr (k < PPG) sum##k = fr29_mul(sum##k, fr29_one_s());
+#define PT_OUT(k) if constexpr (k < PPG) mine[k] = fr29_mul(sum##k, sc);
+// The three round kernels' epilogue — block sums, one point group at a time: lanes of group g contribute their PPG sums, everybody else zeros (no register array is indexed by a
+// run-time value).  MINE: the lane's sum number k0 + v, an expression in k0 and v.  (A macro like CUBIC_ACCUMULATE: as a function it cost the T = 1 kernels 760 - 1520 instructions.)
+#define PT_BLOCK_SUMS(MINE)                                                                                                              \
+  _Pragma("unroll") for (int g = 0; g < T; g++) {                                                                                         \
+    _Pragma("unroll") for (int k0 = 0; k0 < PPG; k0 += 3) {                                                                               \
+      fr29 grp[3];                                                                                                                       \
+      _Pragma("unroll") for (int v = 0; v < 3; v++) {                                                                                     \
+        grp[v] = fr29_zero();                                                                                                            \
+        if (k0 + v < PPG) { _Pragma("unroll") for (int l = 0; l < 9; l++) grp[v].v[l] = pg == (uint32_t)g ? (MINE).v[l] : 0; }            \
+      }                                                                                                                                  \
+      block_columns<3>(grp, R);                                                                                                          \
+      const uint32_t pt = (uint32_t)(g * PPG + k0) + threadIdx.x;                                                                        \
+      if (threadIdx.x < 3 && k0 + (int)threadIdx.x < PPG && pt <= degree) partials[(size_t)blockIdx.x * (degree + 1) + pt] = columns_to_fr(R, threadIdx.x, 0); \
+    }                                                                                                                                    \
+  }
 #define LT_DECL(k) fr29 sum##k = fr29_zero(), t##k = fr29_zero();
-#define LT_TOP(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = lt; lt = lt_line_step(lt, dlt); } }
 #define LT_STEP(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = lt_horner_step(lt, eqv, t##k); lt = lt_line_step(lt, dlt); eqv = lt_line_step(eqv, deq); } }
 #define LT_STEP_PROD(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = fr29_weak(fr29_mul(eqv, t##k)); eqv = lt_line_step(eqv, deq); } }
-#define LT_ACC(k) if constexpr (k < PPG) { if (x0 + k <= degree) { sum##k = lt_weighted_acc(sum##k, ecur, t##k); ecur = lt_line_step(ecur, edif); } }
-#define LT_FOLD(k) if constexpr (k < PPG) sum##k = fr29_mul(sum##k, fr29_one_s());
-#define LT_OUT(k) if constexpr (k < PPG) mine[k] = fr29_mul(sum##k, sc);
+#define LT_ACC(k) PT_ACC(k, t)
 // the per-point operations of the LT round (extracted verbatim by tests/test_host_arith_cpp.py and driven under UBSan): a line stepped to the next evaluation
 // point; a line started at point x0 (lo reduced, d a difference of reduced values, x0 <= 17); one Horner step t <- LT + (EQ * t) (u-form operands: the product is
 // 2^5 short, see above); the eq-weighted accumulation sum += e * t
@@ -1064,25 +1014,25 @@ template <int A, int D, int T, bool PROD = false>
 __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_lt(StrategyDev S, PtrTable polys, const fr_t* __restrict__ eq, fr_t scale, size_t half, uint32_t degree, fr_t* __restrict__ partials) {
   constexpr int PPG = (D + 1 + T - 1) / T;
   constexpr uint32_t SLOTS = LASSO_BLOCK / T;
-  static_assert(PPG <= 6, "LT_REP lists 6 points per lane");
+  static_assert(PPG <= 6, "PT_REP lists 6 points per lane");
   __shared__ RedScratch R;
   const uint32_t slot = threadIdx.x / T, pg = threadIdx.x - slot * T, x0 = pg * PPG;
-  LT_REP(LT_DECL)
+  PT_REP(LT_DECL)
   uint32_t cnt = 0;
   if (slot < SLOTS && x0 <= degree)
   for (size_t i = blockIdx.x * (size_t)SLOTS + slot; i < half; i += (size_t)gridDim.x * SLOTS) {
     {   // innermost term: t(x) = LT_{C-1}(x)   (PROD: the last memory's line)
       const fr_t* __restrict__ pl = polys.p[PROD ? S.c - 1 : 2 * (S.c - 1)];
-      const fr29 lo = fr29_unpack_u(pl[i]), dlt = fr29_sub(fr29_unpack_u(pl[i + half]), lo);
-      fr29 lt = lt_line_at(lo, dlt, x0);
-      LT_REP(LT_TOP)
+      const fr29 lo = fr29_unpack_u(pl[i]), dif = fr29_sub(fr29_unpack_u(pl[i + half]), lo);
+      fr29 cur = lt_line_at(lo, dif, x0);
+      PT_REP(PT_TOP)
     }
     if constexpr (PROD) {
       for (uint32_t m = S.c - 1; m-- > 0;) {   // t <- (E_m * t) / 32
         const fr_t* __restrict__ pe = polys.p[m];
         const fr29 eo = fr29_unpack_u(pe[i]), deq = fr29_sub(fr29_unpack_u(pe[i + half]), eo);
         fr29 eqv = lt_line_at(eo, deq, x0);
-        LT_REP(LT_STEP_PROD)
+        PT_REP(LT_STEP_PROD)
       }
     } else
     for (uint32_t m = S.c - 1; m-- > 0;) {   // t <- LT_m + (EQ_m * t) / 32   (LT_m pre-scaled)
@@ -1090,48 +1040,26 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_lt(StrategyDev S,
       const fr29 lo = fr29_unpack_u(pl[i]), dlt = fr29_sub(fr29_unpack_u(pl[i + half]), lo);
       const fr29 eo = fr29_unpack_u(pe[i]), deq = fr29_sub(fr29_unpack_u(pe[i + half]), eo);
       fr29 lt = lt_line_at(lo, dlt, x0), eqv = lt_line_at(eo, deq, x0);
-      LT_REP(LT_STEP)
+      PT_REP(LT_STEP)
     }
     {   // weight by the eq polynomial's line and accumulate over the indices
       const fr29 e0 = fr29_unpack_u(eq[i]), edif = fr29_sub(fr29_unpack_u(eq[i + half]), e0);
       fr29 ecur = lt_line_at(e0, edif, x0);
-      LT_REP(LT_ACC)
+      PT_REP(LT_ACC)
     }
-    if (++cnt >= LT_FOLD_EVERY()) { cnt = 0; LT_REP(LT_FOLD) }
+    if (++cnt >= LT_FOLD_EVERY()) { cnt = 0; PT_REP(PT_FOLD) }
   }
   const fr29 sc = fr29_unpack_s(scale);   // u-form sums of (value / 32^C) times the s-form of 32^C: u-form of the value
   fr29 mine[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) mine[k] = fr29_zero();
-  LT_REP(LT_OUT)
-  // block sums, one point group at a time: lanes of group g contribute their PPG sums, everybody else zeros (no register array is indexed by a run-time value)
-#pragma unroll
-  for (int g = 0; g < T; g++) {
-#pragma unroll
-    for (int k0 = 0; k0 < PPG; k0 += 3) {
-      fr29 grp[3];
-#pragma unroll
-      for (int v = 0; v < 3; v++) {
-        grp[v] = fr29_zero();
-        if (k0 + v < PPG) {
-#pragma unroll
-          for (int l = 0; l < 9; l++) grp[v].v[l] = pg == (uint32_t)g ? mine[k0 + v].v[l] : 0;
-        }
-      }
-      block_columns<3>(grp, R);
-      const uint32_t pt = (uint32_t)(g * PPG + k0) + threadIdx.x;
-      if (threadIdx.x < 3 && k0 + (int)threadIdx.x < PPG && pt <= degree) partials[(size_t)blockIdx.x * (degree + 1) + pt] = columns_to_fr(R, threadIdx.x, 0);
-    }
-  }
+  PT_REP(PT_OUT)
+  PT_BLOCK_SUMS(mine[k0 + v])
 }
-#undef LT_REP
 #undef LT_DECL
-#undef LT_TOP
 #undef LT_STEP
 #undef LT_STEP_PROD
 #undef LT_ACC
-#undef LT_FOLD
-#undef LT_OUT
 // The FIRST round of the LT sumcheck from the lookup polynomials' integer values.  Before any bind E_k = T[dim_k] holds subtable entries, and the LT / EQ subtables hold
 // bits (lt.rs:17-44): every line LT_m(x), EQ_m(x) = lo + x (hi - lo) is an integer in [-16, 17] for x <= 17, and the whole Horner walk t <- LT_m + EQ_m t is exact INTEGER
 // arithmetic — |t| <= 17 (17^16 - 1) / 16 < 2^67, a 128-bit multiply-add by a small number per memory and point instead of a 256-bit field product.  Only the eq weight is
@@ -1195,24 +1123,7 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_lt_u32(StrategyDe
     }
   }
   if (seen > 1u) *bad = 1u;   // host-mapped word, read by the host behind the result's flag (lasso_sumcheck_combine_round_lt_u32)
-#pragma unroll
-  for (int g = 0; g < T; g++) {
-#pragma unroll
-    for (int k0 = 0; k0 < PPG; k0 += 3) {
-      fr29 grp[3];
-#pragma unroll
-      for (int v = 0; v < 3; v++) {
-        grp[v] = fr29_zero();
-        if (k0 + v < PPG) {
-#pragma unroll
-          for (int l = 0; l < 9; l++) grp[v].v[l] = pg == (uint32_t)g ? sum[k0 + v < PPG ? k0 + v : 0].v[l] : 0;
-        }
-      }
-      block_columns<3>(grp, R);
-      const uint32_t pt = (uint32_t)(g * PPG + k0) + threadIdx.x;
-      if (threadIdx.x < 3 && k0 + (int)threadIdx.x < PPG && pt <= degree) partials[(size_t)blockIdx.x * (degree + 1) + pt] = columns_to_fr(R, threadIdx.x, 0);
-    }
-  }
+  PT_BLOCK_SUMS(sum[k0 + v < PPG ? k0 + v : 0])
 }
 // K3 for a CALLER-DEFINED strategy (include/lasso_hip.h lasso_strategy_custom): g(v) = sum_t coeff_t prod_j v[mem_{t,j}], any sparse polynomial in the memories, degree <= 16.
 // The PROD walk above, term by term: per point a lane keeps the running sum over indices (sum), the value of g at the current index (v) and the current term (t); each factor's
@@ -1251,17 +1162,13 @@ __device__ __forceinline__ void load_custom_terms(const CustomTermsDev* __restri
   for (uint32_t j = threadIdx.x; j < nf; j += blockDim.x) L.term_mem[j] = G->term_mem[j];
   __syncthreads();
 }
-#define CU_REP(M) M(0) M(1) M(2) M(3) M(4) M(5)
 #define CU_DECL(k) fr29 sum##k = fr29_zero(), t##k = fr29_zero(), v##k = fr29_zero();
 #define CU_ZERO(k) if constexpr (k < PPG) v##k = fr29_zero();
 #define CU_CONST(k) if constexpr (k < PPG) t##k = cf;
-#define CU_TOP(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = cur; cur = lt_line_step(cur, dif); } }
 #define CU_MUL(k) if constexpr (k < PPG) { if (x0 + k <= degree) { t##k = fr29_mul(cur, t##k); cur = lt_line_step(cur, dif); } }
 #define CU_ADD(k) if constexpr (k < PPG) { if constexpr (MULTI) v##k = fr29_weak(fr29_add(v##k, t##k)); else v##k = t##k; }
 #define CU_VFOLD(k) if constexpr (k < PPG) v##k = fr29_mul(v##k, fr29_one_s());
-#define CU_ACC(k) if constexpr (k < PPG) { if (x0 + k <= degree) { sum##k = lt_weighted_acc(sum##k, ecur, v##k); ecur = lt_line_step(ecur, edif); } }
-#define CU_FOLD(k) if constexpr (k < PPG) sum##k = fr29_mul(sum##k, fr29_one_s());
-#define CU_OUT(k) if constexpr (k < PPG) mine[k] = fr29_mul(sum##k, sc);
+#define CU_ACC(k) PT_ACC(k, v)
 // D = bound on the sumcheck degree, T = lanes that share one index (the LT kernel's layout: PPG = ceil((D + 1) / T) <= 6 points per lane in named registers).
 // Registers.  Three state elements per point (sum, v, t) are 162 VGPRs at PPG = 6: with the working set of a product the compiler moved 30 - 108 of them to AGPRs and the
 // kernel dropped to one wave per SIMD.  So a list of SEVERAL terms runs with PPG <= 4 (more lanes per index: DISPATCH_CUSTOM in lasso_hip.hip), and a list of ONE term
@@ -1271,80 +1178,64 @@ __global__ void __launch_bounds__(LASSO_BLOCK) k_combine_round_custom(PtrTable p
                                                                       size_t half, uint32_t degree, fr_t* __restrict__ partials) {
   constexpr int PPG = (D + 1 + T - 1) / T;
   constexpr uint32_t SLOTS = LASSO_BLOCK / T;
-  static_assert(PPG <= 6, "CU_REP lists 6 points per lane");
+  static_assert(PPG <= 6, "PT_REP lists 6 points per lane");
   __shared__ RedScratch R;
   __shared__ CustomTermsLds L;
   load_custom_terms<false>(G, nt, nf, L);
   const uint32_t slot = threadIdx.x / T, pg = threadIdx.x - slot * T, x0 = pg * PPG;
-  CU_REP(CU_DECL)
+  PT_REP(CU_DECL)
   uint32_t cnt = 0;
   if (slot < SLOTS && x0 <= degree)
   for (size_t i = blockIdx.x * (size_t)SLOTS + slot; i < half; i += (size_t)gridDim.x * SLOTS) {
-    if constexpr (MULTI) { CU_REP(CU_ZERO) }
+    if constexpr (MULTI) { PT_REP(CU_ZERO) }
     for (uint32_t t = 0; t < (MULTI ? nt : 1u); t++) {
       const uint32_t b = __builtin_amdgcn_readfirstlane(L.term_start[t]), e = __builtin_amdgcn_readfirstlane(L.term_start[t + 1]), fl = __builtin_amdgcn_readfirstlane(L.flags[t]);
-      if (b == e) { const fr29 cf = L.coeff[t]; CU_REP(CU_CONST) }   // a constant term
+      if (b == e) { const fr29 cf = L.coeff[t]; PT_REP(CU_CONST) }   // a constant term
       else {
         {   // first factor: the term's line, times the folded coefficient unless that is 1
           const fr_t* __restrict__ pm = polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[b])];
           fr29 lo = fr29_unpack_u(pm[i]), dif = fr29_sub(fr29_unpack_u(pm[i + half]), lo);
           if (!(fl & 1u)) { const fr29 cf = L.coeff[t]; lo = fr29_mul(lo, cf); dif = fr29_mul(dif, cf); }
           fr29 cur = lt_line_at(lo, dif, x0);
-          CU_REP(CU_TOP)
+          PT_REP(PT_TOP)
         }
         for (uint32_t j = b + 1; j < e; j++) {   // t <- (E_m * t) / 32
           const fr_t* __restrict__ pm = polys.p[__builtin_amdgcn_readfirstlane(L.term_mem[j])];
           const fr29 lo = fr29_unpack_u(pm[i]), dif = fr29_sub(fr29_unpack_u(pm[i + half]), lo);
           fr29 cur = lt_line_at(lo, dif, x0);
-          CU_REP(CU_MUL)
+          PT_REP(CU_MUL)
         }
       }
-      CU_REP(CU_ADD)
-      if constexpr (MULTI) { if (fl & 4u) { CU_REP(CU_VFOLD) } }
+      PT_REP(CU_ADD)
+      if constexpr (MULTI) { if (fl & 4u) { PT_REP(CU_VFOLD) } }
     }
     {   // weight by the eq polynomial's line and accumulate over the indices
       const fr29 e0 = fr29_unpack_u(eq[i]), edif = fr29_sub(fr29_unpack_u(eq[i + half]), e0);
       fr29 ecur = lt_line_at(e0, edif, x0);
-      CU_REP(CU_ACC)
+      PT_REP(CU_ACC)
     }
-    if (++cnt >= LT_FOLD_EVERY()) { cnt = 0; CU_REP(CU_FOLD) }
+    if (++cnt >= LT_FOLD_EVERY()) { cnt = 0; PT_REP(PT_FOLD) }
   }
   const fr29 sc = fr29_unpack_s(scale);   // u-form sums of (value / 32^Q) times the s-form of 32^Q: u-form of the value
   fr29 mine[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) mine[k] = fr29_zero();
-  CU_REP(CU_OUT)
-  // block sums, one point group at a time, as k_combine_round_lt
-#pragma unroll
-  for (int g = 0; g < T; g++) {
-#pragma unroll
-    for (int k0 = 0; k0 < PPG; k0 += 3) {
-      fr29 grp[3];
-#pragma unroll
-      for (int v = 0; v < 3; v++) {
-        grp[v] = fr29_zero();
-        if (k0 + v < PPG) {
-#pragma unroll
-          for (int l = 0; l < 9; l++) grp[v].v[l] = pg == (uint32_t)g ? mine[k0 + v].v[l] : 0;
-        }
-      }
-      block_columns<3>(grp, R);
-      const uint32_t pt = (uint32_t)(g * PPG + k0) + threadIdx.x;
-      if (threadIdx.x < 3 && k0 + (int)threadIdx.x < PPG && pt <= degree) partials[(size_t)blockIdx.x * (degree + 1) + pt] = columns_to_fr(R, threadIdx.x, 0);
-    }
-  }
+  PT_REP(PT_OUT)
+  PT_BLOCK_SUMS(mine[k0 + v])
 }
-#undef CU_REP
 #undef CU_DECL
 #undef CU_ZERO
 #undef CU_CONST
-#undef CU_TOP
 #undef CU_MUL
 #undef CU_ADD
 #undef CU_VFOLD
 #undef CU_ACC
-#undef CU_FOLD
-#undef CU_OUT
+#undef PT_REP
+#undef PT_TOP
+#undef PT_ACC
+#undef PT_FOLD
+#undef PT_OUT
+#undef PT_BLOCK_SUMS
 // K10 for a caller-defined strategy: claim = sum_k eq[k] g(E(k)) with the same term list.  A term starts as its first value in u-form and every further factor, the coefficient
 // multiply it in s-form; the eq weight is u-form and the block sum is corrected by 2^5 like the linear strategies'.  A finished term is below 4 p (a lone lazily reduced value) and otherwise below 2 p; g is
 // folded after every 4 terms: |g| < 18 p where eq multiplies it.

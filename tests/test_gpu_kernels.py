@@ -1006,6 +1006,33 @@ def test_abort_releases_a_waiting_tail_kernel(devs):
         d.free(p)
 
 
+def test_abort_releases_a_waiting_linear_tail_kernel(devs):
+    """The same for the linear strategies' resident tail (k_linear_tail waits in the same mail_wait): lasso_abort's poison tag releases it without the 5 s bail-out,
+    and the same context then runs a complete linear tail with the right answers."""
+    import time
+    d = devs[0]
+    rng = np.random.default_rng(78)
+    n, alpha = 64, 2
+    Ps = [rand_fr(rng, n) for _ in range(alpha)]; E = rand_fr(rng, n // 2)
+    turns = n.bit_length() - 1
+    chal = rand_fr(rng, turns, edge=False)
+    pp = [d.upload(x) for x in Ps]; pe = d.upload(E)
+    d._chk(d.lib.lasso_sumcheck_linear_tail_begin(d.ctx, d._ptrs(pp), alpha, C.c_void_p(pe), n, None))
+    out = np.empty((2 * alpha, 4), dtype=np.uint64)
+    d._chk(d.lib.lasso_result_wait(d.ctx, out.ctypes.data_as(C.c_void_p), 2 * alpha))      # first round's sums arrive; the kernel now waits for a challenge
+    t0 = time.perf_counter()
+    d._chk(d.lib.lasso_abort(d.ctx))
+    assert time.perf_counter() - t0 < 1.0, "abort must not wait for the kernel's 5 s bail-out"
+    want = devs[1].sumcheck_linear_tail([devs[1].upload(x) for x in Ps], devs[1].upload(E), n, None, chal)
+    got = d.sumcheck_linear_tail(pp, pe, n, None, chal)   # the tail only reads its source arrays
+    assert len(got) == len(want) == turns + 1
+    assert np.array_equal(out.reshape(alpha, 2, 4), want[0])   # the sums the aborted run did publish
+    for x, y in zip(got, want):
+        assert np.array_equal(x, y)
+    for p in pp + [pe]:
+        d.free(p)
+
+
 @pytest.mark.parametrize("n,ncirc,scaled", [(256, 2, False), (512, 3, True), (1 << 12, 2, False), (1 << 14, 2, True), (1 << 15, 5, False), (1 << 15, 16, True),
                                              (1 << 16, 2, True), (1 << 18, 3, False), (1 << 20, 1, True), (1 << 17, 9, False)])   # above 2^14 entries: factor tables in memory (EqGlobal)
 def test_sumcheck_cubic_round0_with_inline_eq_table(devs, n, ncirc, scaled):
