@@ -96,15 +96,39 @@ def test_gpu_bn254_config1_bit_exact_at_full_size(host, oracle_bn254):
     assert proof == o_proof
 
 
-def test_gpu_bn254_kernel_parity_suite():
-    """Every entry point of the BN254 library against the BN254 mock: tests/test_gpu_kernels.py re-run in a child process with LASSO_TEST_CURVE=bn254
-    (the switch is read at import time by tests/fieldref.py, so it cannot share this process)."""
+def _rerun_on_bn254(module, extra=(), timeout=900):
+    """a test module re-run in a child process with LASSO_TEST_CURVE=bn254 (the switch is read at import time by tests/fieldref.py, so it cannot share this process)"""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LASSO_TEST_CURVE="bn254")
-    res = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_kernels.py"), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider"],
-                         cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    res = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", module), "-m", "gpu", "-x", "-q", "-p", "no:cacheprovider", *extra],
+                         cwd=root, env=env, capture_output=True, text=True, timeout=timeout)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
     assert " passed" in res.stdout and "failed" not in res.stdout
+
+
+def test_gpu_bn254_kernel_parity_suite():
+    """Every entry point of the BN254 library against the BN254 mock: tests/test_gpu_kernels.py re-run in a child process with LASSO_TEST_CURVE=bn254."""
+    _rerun_on_bn254("test_gpu_kernels.py")
+
+
+def test_gpu_bn254_msm_over_caller_points():
+    """tests/test_gpu_msm_points.py on the BN254 build (minus its two long cases): the short-Weierstrass build is where "the group laws are complete" (msm_points_kernels.cuh) is
+    carried by the Renes-Costello-Batina formulas and the six-lane tree — test_degenerate_inputs (equal points, P and -P in one bucket, buckets that sum to the identity) is the
+    test of that sentence, and on the Edwards build the unified addition is complete anyway."""
+    _rerun_on_bn254("test_gpu_msm_points.py", ["-k", "not 2p17 and not 2p16"])
+
+
+def test_gpu_bn254_custom_strategy_kernel_level():
+    """Sections 5 and 9 of tests/test_gpu_custom_strategy.py (the tests over its `dev` fixture) on the BN254 build: every degree 1..17 of k_combine_round_custom, the caps exactly
+    reached and all inputs at LAZY_BOUND over the wider Fr, whose fr29 magnitude arguments are its own.  (The whole-proof tests of that module take the curve as a parameter.)"""
+    _rerun_on_bn254("test_gpu_custom_strategy.py", ["-k", "test_every_degree_one_term_and_several or test_sizes_and_memory_counts or test_repeated_memories_special_coefficients_and_constants "
+                                                    "or test_caps_exactly_reached or test_all_inputs_at_the_lazy_bound_and_two_factor_terms_with_coefficient_one "
+                                                    "or test_invalid_descriptor_at_the_device_entry_points"])
+
+
+def test_gpu_bn254_msm_variants():
+    """tests/test_gpu_msm_variants.py on the BN254 build: every switched MSM kernel against the BN254 mock."""
+    _rerun_on_bn254("test_gpu_msm_variants.py")

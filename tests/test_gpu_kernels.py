@@ -9,6 +9,7 @@ import pytest
 from fieldref import L as FR_P, limbs, to_mont
 from gpuutil import compress_points, gens, load_mock, rand_fr, small_fr
 from lasso_amd import _abi
+from msmvariants import FULL_WIDTH_WIDE_SHAPES, HYRAX_COMMIT_SHAPES, HYRAX_COMMIT_U32_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -447,12 +448,7 @@ def gens_300(devs):
     return gens(devs[1].lib, b"gens_sparse_poly", 300)
 
 
-@pytest.mark.parametrize("ls,rs,maxv", [(1, 1, 5), (4, 8, 256), (16, 256, 1 << 16), (8, 300, 1 << 24), (3, 100, 1 << 32), (2, 64, None),
-                                        # >= 32 rows of scalars <= 16 bits: the byte-table kernel (k_msm_rows8), one and two byte windows, ragged columns, a chunked row, and
-                                        # just past its limits (17 and 24 bits: the bucket kernel again)
-                                        (64, 256, 256), (40, 77, 2), (300, 300, 1 << 16), (33, 129, 1 << 12), (32, 5, 1 << 9), (64, 100, 1 << 17), (48, 64, 1 << 24),
-                                        # >= 1024 rows: one wave per row (k_msm_rows8w), one and two byte windows, fewer columns than lanes, ragged rows (not a multiple of 4), all-zero values
-                                        (1024, 64, 256), (1500, 100, 1 << 16), (2049, 33, 2), (1027, 300, 1 << 12), (1024, 8, 1)])
+@pytest.mark.parametrize("ls,rs,maxv", HYRAX_COMMIT_SHAPES)   # tests/msmvariants.py: each shape with the kernel that serves it (tests/test_msm_reach_cpu.py checks that)
 def test_hyrax_commit(devs, gens_300, ls, rs, maxv):
     rng = np.random.default_rng(ls * 31 + rs)
     if maxv is None:
@@ -476,7 +472,7 @@ def test_hyrax_commit(devs, gens_300, ls, rs, maxv):
     assert np.array_equal(wa, wb) and [bytes(x) for x in wa] == compress_points(mock_lib, b)
 
 
-@pytest.mark.parametrize("ls,rs,shape", [(256, 300, "random"), (300, 257, "edges"), (256, 64, "equal"), (512, 300, "sparse"), (333, 300, "groups")])
+@pytest.mark.parametrize("ls,rs,shape", FULL_WIDTH_WIDE_SHAPES)
 def test_hyrax_commit_full_width_wide_windows(devs, gens_300, ls, rs, shape, monkeypatch):
     """>= 256 rows of FULL-WIDTH scalars: the 12-bit signed-window bucket form (k_msm_pip_sort / _accumulate / _reduce; by default from 2048 columns on, here forced down to
     the fixture's 300 generators) against the oracle's row commitments and against the nibble-bucket kernel (LASSO_MSM_PIP=0) on the same device.  Shapes: random scalars;
@@ -661,7 +657,7 @@ def test_rccl_two_ranks_on_one_device(devs):
         d._chk(d.lib.lasso_rccl_shutdown(d.ctx)); d.close()
 
 
-@pytest.mark.parametrize("ls,rs,tbits", [(1, 1, 1), (4, 8, 8), (16, 256, 16), (8, 300, 24), (3, 100, 32), (128, 128, 8), (64, 300, 16), (32, 33, 1), (40, 64, 17)])
+@pytest.mark.parametrize("ls,rs,tbits", HYRAX_COMMIT_U32_SHAPES)
 def test_hyrax_commit_u32(devs, gens_300, ls, rs, tbits):
     """commitment from the integer values (gathered from an integer table, as for E = T[dim]) == commitment of the same polynomial as field elements"""
     rng = np.random.default_rng(ls * 17 + rs)

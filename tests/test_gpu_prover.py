@@ -151,18 +151,22 @@ def test_gpu_soak_alternating_shapes_on_one_prover(host):
             host.free(dense, gens)
 
 
+# the instances of the switch test: (kind, C, log_M, log2 of the lookups).  "spark": E holds field elements, so its commitment is 2^7 rows of full-width scalars — more than the
+# MSM_SMALL_ROWS the latency-shaped kernel takes, on a generator set that has the byte-multiple table: the one proof-level shape at which LASSO_MSM_FULL8 selects another kernel
+_SWITCH_INSTANCES = {"and": ("and", 2, 16, 14), "spark": ("spark", 2, 8, 14)}
 _SWITCH_SCRIPT = """
 import hashlib, sys
 import numpy as np
 from lasso_amd import HostProver, _abi
 hp = HostProver()
-kind, c, log_m, log_s = "and", 2, 16, 14
+kind, c, log_m, log_s = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 S = _abi.Strategy(_abi.KINDS[kind], c, log_m, 0)
 idx = hp.gen_indices(1 << log_s, 1 << log_m, c); r = hp.gen_random_point(log_s)
 gens = hp.gens(c, 1 << log_s, c, log_m); dense = hp.densify(idx, log_m)
 comm = hp.commit(dense, gens); proof = hp.prove(dense, gens, S, r)
 print("DIGEST", hashlib.sha256(comm + proof).hexdigest())
 """
+_SWITCH_WANT = {}      # instance -> digest of the default configuration's commitment and proof (this process)
 
 
 @pytest.mark.parametrize("env", [{"LASSO_TAGGED_RESULTS": "0"}, {"LASSO_DIRECT_NX": "0"}, {"LASSO_TAGGED_RESULTS": "0", "LASSO_CUBIC_TAIL": "0", "LASSO_LINEAR_TAIL": "0"},
@@ -196,24 +200,39 @@ print("DIGEST", hashlib.sha256(comm + proof).hexdigest())
                                  {"LASSO_CUBIC_WIDE": "0"},                  # the two-sum fused round without its double-width accumulators
                                  {"LASSO_LB_NT": "1"},                       # non-temporal loads of A and B in the evaluation-only round (measured, not the default)
                                  {"LASSO_MSM_ROWS8": "0"},                   # the commitments of small scalars by the bucket kernel instead of the byte-multiple tables
-                                 {"LASSO_AHEAD_INKERNEL_WGS": "0"}, {"LASSO_AHEAD_INKERNEL_WGS": "64"}])   # a round launched ahead waits behind the gate kernel always / inside its own kernel up to 64 workgroups
+                                 {"LASSO_AHEAD_INKERNEL_WGS": "0"}, {"LASSO_AHEAD_INKERNEL_WGS": "64"},    # a round launched ahead waits behind the gate kernel always / inside its own kernel up to 64 workgroups
+                                 {"LASSO_CUBIC_NX": "64"}, {"LASSO_CUBIC_NX": "2048"},             # the x-extent of every streaming round's grid: fewer and more workgroups than the default's ~512 over the grid
+                                 {"LASSO_MSM_DIRECT_WGS": "7"}, {"LASSO_MSM_DIRECT_WGS": "1024"},  # workgroups of the openings' latency-shaped launches: chunks per row and items per chunk of k_msm_direct / k_bullet_msm
+                                 {"LASSO_SIDE_STREAM": "0"},                 # no second context: E's commitment and the openings' preparation on the primary stream
+                                 # a tuple: (setting, instance of _SWITCH_INSTANCES) — the settings that need a full-width commitment of more than 16 rows to select another kernel
+                                 ({"LASSO_MSM_FULL8": "1"}, "spark"), ({"LASSO_MSM_ROWS8": "0"}, "spark"), ({"LASSO_MSM_DIRECT": "0"}, "spark")])
 def test_gpu_ab_switches_do_not_change_the_bytes(host, env):
     """The A/B switches the measurements in DESIGN.md rest on (flag protocol instead of tagged results, in-launch second stage, launch per round instead of the resident tails, ...)
     select other kernels / protocols for the same arithmetic: commitment and proof must be the bytes of the default configuration.  Each setting runs in its own process
-    (the switches are read once per process)."""
+    (the switches are read once per process).
+
+    What a proof of 2^14 lookups cannot reach, and tests/test_gpu_msm_variants.py reaches at kernel level instead (tests/test_msm_reach_cpu.py shows that each of its shapes does):
+    LASSO_MSM_ROWS8W_WAVES=2048 needs a commitment of more than 2048 rows of small scalars for a second row per wave, and LASSO_MSM_ROWS8W=0 one of at least 1024 rows for k_msm_rows8w
+    to have been chosen at all — the matrices committed here have at most a few hundred rows, so both settings leave every launch as it was; LASSO_MSM_FULL8=1 needs full-width scalars
+    on more than 16 rows (or wire bytes) — the AND instance commits small integers only, hence the Spark instance, whose E rows are field elements; wire bytes by hipMemcpy
+    (MSM_R_COMPRESSED_MEMCPY) need more than 2^16 rows; and LASSO_MSM_DIRECT_WGS at 1 and 4096, the ends of its range.
+    Still untested anywhere: LASSO_SLAB_OPEN and LASSO_SLAB_RCCL (slab mode: they need several contexts side by side) and LASSO_THROUGHPUT_AHEAD."""
     import hashlib, os, subprocess, sys
-    kind, c, log_m, log_s = "and", 2, 16, 14
-    S = _abi.Strategy(_abi.KINDS[kind], c, log_m, 0)
-    idx = host.gen_indices(1 << log_s, 1 << log_m, c); r = host.gen_random_point(log_s)
-    gens = host.gens(c, 1 << log_s, c, log_m); dense = host.densify(idx, log_m)
-    want = hashlib.sha256(host.commit(dense, gens) + host.prove(dense, gens, S, r)).hexdigest()
-    host.free(dense, gens)
+    env, inst = env if isinstance(env, tuple) else (env, "and")
+    kind, c, log_m, log_s = _SWITCH_INSTANCES[inst]
+    if inst not in _SWITCH_WANT:
+        S = _abi.Strategy(_abi.KINDS[kind], c, log_m, 0)
+        idx = host.gen_indices(1 << log_s, 1 << log_m, c); r = host.gen_random_point(log_s)
+        gens = host.gens(c, 1 << log_s, c, log_m); dense = host.densify(idx, log_m)
+        _SWITCH_WANT[inst] = hashlib.sha256(host.commit(dense, gens) + host.prove(dense, gens, S, r)).hexdigest()
+        host.free(dense, gens)
+    want = _SWITCH_WANT[inst]
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     e = dict(os.environ); e.update(env); e["PYTHONPATH"] = root + os.pathsep + e.get("PYTHONPATH", "")
-    out = subprocess.run([sys.executable, "-c", _SWITCH_SCRIPT], env=e, cwd=root, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([sys.executable, "-c", _SWITCH_SCRIPT, kind, str(c), str(log_m), str(log_s)], env=e, cwd=root, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     got = [l.split()[1] for l in out.stdout.splitlines() if l.startswith("DIGEST")]
-    assert got == [want], (env, got, want)
+    assert got == [want], (env, inst, got, want)
 
 
 # BASELINE.json's configurations at FULL size (configs[1], configs[2] and the configuration the metric is quoted on).  The oracle prover cannot
