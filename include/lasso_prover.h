@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "lasso_hip.h"
+#include "lasso_hip_operands.h"   /* lasso_operand_layout */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -90,6 +91,28 @@ void lasso_host_gens_free(lasso_host_gens* g);
 /* indices: n_lookups x c, row-major (Vec<[usize; C]>) */
 int32_t lasso_host_densify(lasso_host* h, const uint64_t* indices, size_t n_lookups, size_t c, size_t log_m, lasso_host_dense** out);
 void lasso_host_dense_free(lasso_host_dense* d);
+/* ---- densify from OPERAND columns (include/lasso_hip_operands.h: lasso_operand_layout and its rules) -------------------------------------------------------------
+ * What a caller holds are operands, two 64-bit columns x, y for AND / OR / XOR / LT or one for a range check; the Vec<[usize; C]> above is an artefact of the
+ * decomposition into C chunks, 8 C bytes per lookup against 16 (8 for one operand).  The layout says which chunk of which operand is which dimension's address, and
+ * is part of the statement: a proof over a wrong layout verifies, for another statement.
+ * lasso_host_operand_layout: the layout of a built-in strategy (AND / OR / XOR {2, log_m / 2, 0}; LT {2, log_m / 2, 1}; RangeCheck {1, log_m, 0}); -1 with a message for an
+ * odd log_m of a two-operand strategy and for LASSO_SPARK_UNCONFIRMED / LASSO_CUSTOM, which have none: the caller passes its own. */
+int32_t lasso_host_operand_layout(const lasso_strategy* strategy, lasso_operand_layout* out);
+/* The normative CPU statement of the layout: indices (n x c, row-major: what lasso_host_densify takes) of the n operand pairs; y = NULL exactly when the layout has one
+ * operand.  -1 with a message when the layout breaks a rule (operands 1 or 2, chunk_bits >= 1, operands * chunk_bits <= log_m <= 32) or an operand does not fit
+ * c * chunk_bits bits.  Needs no host object: a verifier-side caller restates the lookups with it. */
+int32_t lasso_host_operand_indices(const lasso_operand_layout* layout, const uint64_t* x, const uint64_t* y, size_t n, size_t c, size_t log_m, uint64_t* indices);
+/* lasso_host_densify(h, lasso_host_operand_indices(layout, x, y), ...) without the index array: the same representation (same buffers, capacity mode's compact form, slab
+ * mode's residue classes — commitment and proof bytes are identical), each dimension's addresses formed on the device inside its densify pass
+ * (lasso_densify_dim_operands).  where = 0: x, y are host arrays of n_lookups operands and are uploaded (16 or 8 bytes per lookup instead of 8 c; at c = 1 with two operands
+ * that is twice the index array); where = 1: they are device pointers of the host's context, used as they are (the caller's stream must have finished writing them).
+ * Against a device library without the entry, or with LASSO_DENSIFY_OPERANDS=0, where = 0 expands to indices on the host and takes lasso_host_densify's path, and
+ * where = 1 returns -1 with a message.  Return codes and error texts (layout refusals, an operand that does not fit) do not depend on the path. */
+int32_t lasso_host_densify_operands(lasso_host* h, const lasso_operand_layout* layout, const uint64_t* x, const uint64_t* y, size_t n_lookups, size_t c, size_t log_m,
+                                    int32_t where, lasso_host_dense** out);
+/* *operand_dims_on_device = dimensions this host has densified through lasso_densify_dim_operands so far (c per lasso_host_densify_operands call that took the device
+ * path); *available = 1 when the device library has the entry; either may be NULL; reset != 0 zeroes the counter. */
+int32_t lasso_host_densify_stats(lasso_host* h, uint64_t* operand_dims_on_device, int32_t* available, int32_t reset);
 /* out = [u64 L1][L1 x 32 B][u64 L2][L2 x 32 B]: l_variate_polys_commitment.C then log_m_variate_polys_commitment.C */
 int32_t lasso_host_commit(lasso_host_dense* d, lasso_host_gens* g, uint8_t* out, size_t cap, size_t* len);
 /* LIVENESS.  While a proof runs, kernels of this context wait ON THE DEVICE for the calling thread's next Fiat-Shamir challenge (resident tails, gate kernels

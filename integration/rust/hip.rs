@@ -292,6 +292,17 @@ impl Drop for HipProver {
   }
 }
 
+/// `lasso_operand_layout` (include/lasso_hip_operands.h): how an operand pair becomes the C table addresses of one lookup.  Part of the statement: a proof over a wrong
+/// layout verifies, for another statement.
+pub type OperandLayout = lasso_operand_layout;
+impl lasso_operand_layout {
+  /// the built-in layout of a strategy descriptor (lasso_host_operand_layout); `None` for a strategy without one (the caller writes its own)
+  pub fn of(strategy: &lasso_strategy) -> Option<Self> {
+    let mut out = lasso_operand_layout { operands: 0, chunk_bits: 0, msb_first: 0 };
+    if unsafe { lasso_host_operand_layout(strategy, &mut out) } == 0 { Some(out) } else { None }
+  }
+}
+
 /// `DensifiedRepresentation<F, C>` with dim / read / final resident in HBM (densified.rs:8-20: the `pub` fields are only read inside the crate).
 pub struct HipDensified<'a, F: PrimeField, const C: usize> {
   d: *mut lasso_host_dense,
@@ -307,6 +318,18 @@ impl<'a, F: PrimeField, const C: usize> HipDensified<'a, F, C> {
     let mut d = std::ptr::null_mut();
     chk(unsafe { lasso_host_densify(p.h, indices.as_ptr() as *const u64, indices.len(), C, log_m, &mut d) }, "lasso_host_densify");
     HipDensified { d, s: indices.len().next_power_of_two(), log_m, m: 1 << log_m, p, _p: PhantomData }
+  }
+
+  /// The same representation from OPERAND columns, the chunk indices formed on the device (include/lasso_prover.h lasso_host_densify_operands): `x`, `y` are what the
+  /// caller looks up — `y` is `None` for a one-operand layout (a range check) — and `layout` says which chunk of which operand is which dimension's address
+  /// (`OperandLayout::of(&S::descriptor())` for the built-in strategies: AND / OR / XOR {2, log_m / 2, 0}, LT {2, log_m / 2, 1}, RangeCheck {1, log_m, 0}).  Commitment and proof are
+  /// byte-identical to `from_lookup_indices` over `lasso_host_operand_indices(layout, x, y)`; 16 (or 8) bytes per lookup are uploaded instead of 8 C.
+  /// Panics if the layout breaks a rule of include/lasso_hip_operands.h or an operand does not fit C * chunk_bits bits.
+  pub fn from_operands(p: &'a HipProver, x: &[u64], y: Option<&[u64]>, layout: &OperandLayout, log_m: usize) -> Self {
+    if let Some(y) = y { assert_eq!(x.len(), y.len(), "operand columns of different lengths"); }
+    let mut d = std::ptr::null_mut();
+    chk(unsafe { lasso_host_densify_operands(p.h, layout, x.as_ptr(), y.map_or(std::ptr::null(), |y| y.as_ptr()), x.len(), C, log_m, 0, &mut d) }, "lasso_host_densify_operands");
+    HipDensified { d, s: x.len().next_power_of_two(), log_m, m: 1 << log_m, p, _p: PhantomData }
   }
 
   /// densified.rs:78-96.  The library returns `[u64 L1][L1 x 32 B][u64 L2][L2 x 32 B]` = the two `PolyCommitment { C: Vec<G> }` in

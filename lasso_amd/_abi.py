@@ -18,6 +18,14 @@ class StrategyCustom(C.Structure):
                 ("memory_subtable", vp), ("memory_dimension", vp), ("num_terms", u32), ("reserved", u32), ("coeff", vp), ("term_start", vp), ("term_mem", vp)]
 
 
+class OperandLayout(C.Structure):
+    """include/lasso_hip_operands.h lasso_operand_layout: how an operand pair becomes the C table addresses of one lookup"""
+    _fields_ = [("operands", u32), ("chunk_bits", u32), ("msb_first", u32)]
+
+    def __repr__(self):
+        return f"OperandLayout({self.operands}, {self.chunk_bits}, {self.msb_first})"
+
+
 KINDS = {"and": 0, "or": 1, "xor": 2, "lt": 3, "range": 4, "spark": 5, "custom": 6}   # "spark" = LASSO_SPARK_UNCONFIRMED (include/lasso_hip.h): not in the reference snapshot
 CUSTOM_MAX_TERMS, CUSTOM_MAX_FACTORS, CUSTOM_MAX_DEGREE = 256, 2048, 17
 K_BIND, K_CUBIC, K_COMBINE, K_EQ, K_GP, K_FINGERPRINT, K_DOT, K_MATVEC, K_MSM, K_MISC, K_MSM_DIRECT, K_COUNT = range(12)
@@ -167,6 +175,15 @@ def declare_msm_points(lib):
         fn.restype = i32
         fn.argtypes = [vp, vp, vp, sz, vp]
     return ["lasso_msm_points", "lasso_msm_points_dev"]
+
+
+def declare_operands(lib):
+    """include/lasso_hip_operands.h — densify from operand columns.  Declared apart from declare(), as declare_wire and declare_msm_points are: an implementation of
+    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
+    fn = lib.lasso_densify_dim_operands
+    fn.restype = i32
+    fn.argtypes = [vp, vp, vp, sz, C.POINTER(OperandLayout), sz, sz, sz, u32, u32, u32, vp, vp, vp, vp]
+    return ["lasso_densify_dim_operands"]
 
 
 HEADER_SYMBOLS = None

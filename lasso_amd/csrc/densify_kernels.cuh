@@ -8,6 +8,7 @@
 //
 // Kernels (all hand-written; u32 keys/values, 4096 elements per workgroup):
 //   k_densify_extract   indices -> keys (+ identity values, + dim polynomial, + range check)
+//   k_densify_extract_operands   the same from operand columns: the dimension's address is formed here (operand_layout.cuh), no index array exists
 //   k_radix_hist        per-tile digit histogram            hist[digit][tile]
 //   k_scan_*            exclusive scan of hist (three-step, any length)
 //   k_radix_scatter     stable scatter: in-tile rank by wave ballots (8 ballots give the lanes holding the same digit), waves in order
@@ -16,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "fr29.cuh"
+#include "operand_layout.cuh"
 
 #define RADIX_TILE 4096
 #define RADIX_THREADS 256
@@ -29,6 +31,26 @@ __global__ void __launch_bounds__(256) k_densify_extract(const uint64_t* __restr
     uint64_t a = k < n_lookups ? idx[k * C + col] : 0;         // access_sequence.resize(s, 0)  densified.rs:38
     if (a >= m) { atomicOr(bad, 1u); a = 0; }                    // debug_assert!(memory_address < m)  :46 — flagged (the call returns LASSO_ERR_INVALID) and
                                                                  // clamped, so the sort / run kernels that index 2*m words of scratch by key stay in bounds
+    keys[k] = (uint32_t)a; vals[k] = (uint32_t)k;
+    if (k % world == rank) { dim_u32[k / world] = (uint32_t)a; dim_fr[k / world] = fr29_store(fr29_mul(fr29_from_u64_int(a), r2s)); }
+  }
+}
+
+// k_densify_extract with the address formed from the lookup's operands (include/lasso_hip_operands.h): lane k reads x[k] and y[k] — two streams of 8 contiguous bytes per
+// lane, whatever C is — instead of one u64 at a stride of 8 C bytes.  y == nullptr: one operand.  An operand that does not fit C * chunk_bits bits raises the flag and the key
+// is clamped to 0, as the out-of-range index is above.  A valid address is below 2^(operands * chunk_bits) <= m by construction (the entry point has checked the layout against
+// log_m), so the sort / run kernels that index 2*m words of scratch by key stay in bounds.
+__global__ void __launch_bounds__(256) k_densify_extract_operands(const uint64_t* __restrict__ x, const uint64_t* __restrict__ y, size_t n_lookups, lasso_operand_layout layout, size_t C, size_t col, size_t s,
+                                                                   uint32_t world, uint32_t rank, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ dim_u32,
+                                                                   fr_t* __restrict__ dim_fr, uint32_t* __restrict__ bad) {
+  const fr29 r2s = fr29_r2s();
+  for (size_t k = blockIdx.x * (size_t)blockDim.x + threadIdx.x; k < s; k += (size_t)gridDim.x * blockDim.x) {
+    uint64_t a = 0;                                               // the padded tail k >= n_lookups has address 0
+    if (k < n_lookups) {
+      const uint64_t vx = x[k], vy = y ? y[k] : 0;
+      if (operand_fits(vx, C, layout.chunk_bits) && operand_fits(vy, C, layout.chunk_bits)) a = operand_index(layout, vx, vy, C, col);
+      else atomicOr(bad, 1u);
+    }
     keys[k] = (uint32_t)a; vals[k] = (uint32_t)k;
     if (k % world == rank) { dim_u32[k / world] = (uint32_t)a; dim_fr[k / world] = fr29_store(fr29_mul(fr29_from_u64_int(a), r2s)); }
   }

@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 #include <cstring>
+#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <ctime>
@@ -19,6 +20,7 @@
 #include "wire_kernels.cuh"
 #include "../../include/lasso_hip_msm.h"
 #include "msm_points_kernels.cuh"
+#include "../../include/lasso_hip_operands.h"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1418,10 +1420,10 @@ int32_t lasso_densify_dim(lasso_ctx* c, const uint64_t* d_indices, size_t n_look
                           lasso_fr* d_final) {
   return lasso_densify_dim_slab(c, d_indices, n_lookups, C, dim, s, log_m, 1, 0, d_dim_u32, d_dim, d_read, d_final);
 }
-int32_t lasso_densify_dim_slab(lasso_ctx* c, const uint64_t* d_indices, size_t n_lookups, size_t C, size_t dim, size_t s, uint32_t log_m, uint32_t world, uint32_t rank, uint32_t* d_dim_u32,
-                               lasso_fr* d_dim, lasso_fr* d_read, lasso_fr* d_final) {
-  REQUIRE(c, d_indices && d_dim_u32 && d_dim && d_read && d_final && C >= 1 && dim < C && s >= 1 && (s & (s - 1)) == 0 && n_lookups <= s && s < ((size_t)1 << 32) && log_m <= 32);
-  REQUIRE(c, world >= 1 && (world & (world - 1)) == 0 && rank < world && world <= s && world <= ((size_t)1 << log_m));
+// One dimension from the keys on: `extract(kA, vA)` launches the kernel that writes keys, identity values, dim_u32, dim and the flag word — the ONLY step in which the index
+// form (lasso_densify_dim_slab) and the operand form (lasso_densify_dim_operands) differ; the radix passes, the run boundaries and the timestamp kernels are shared.
+static int32_t densify_dim_run(lasso_ctx* c, size_t n_lookups, size_t s, uint32_t log_m, uint32_t world, uint32_t rank, lasso_fr* d_read, lasso_fr* d_final, double extract_bytes,
+                               const char* bad_msg, const std::function<void(uint32_t*, uint32_t*)>& extract) {
   const size_t m = (size_t)1 << log_m;
   const uint32_t ntiles = (uint32_t)((s + RADIX_TILE - 1) / RADIX_TILE);
   const size_t nh = (size_t)256 * ntiles, nb = (nh + 4095) / 4096;
@@ -1431,8 +1433,8 @@ int32_t lasso_densify_dim_slab(lasso_ctx* c, const uint64_t* d_indices, size_t n
   uint32_t* hist = vB + s; uint32_t* sums = hist + nh; uint32_t* run_start = sums + nb; uint32_t* run_end = run_start + m;
   HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8, c->stream));
   HIPCHK(c, hipMemsetAsync(run_start, 0, 2 * m * 4, c->stream));
-  ProfScope ps(c, LASSO_K_MISC, 8.0 * n_lookups + (32.0 * 2 + 4.0) * s + 32.0 * m);
-  hipLaunchKernelGGL(k_densify_extract, dim3(grid_for(s, 4096)), dim3(256), 0, c->stream, d_indices, n_lookups, C, dim, s, (uint64_t)m, world, rank, kA, vA, d_dim_u32, (fr_t*)d_dim, c->d_flags);
+  ProfScope ps(c, LASSO_K_MISC, extract_bytes + (32.0 * 2 + 4.0) * s + 32.0 * m);
+  extract(kA, vA);
   const uint32_t npass = log_m == 0 ? 1 : (log_m + 7) / 8;
   for (uint32_t p = 0; p < npass; p++) {
     hipLaunchKernelGGL(k_radix_hist, dim3(ntiles), dim3(RADIX_THREADS), 0, c->stream, (const uint32_t*)kA, s, 8 * p, hist, ntiles);
@@ -1449,8 +1451,29 @@ int32_t lasso_densify_dim_slab(lasso_ctx* c, const uint64_t* d_indices, size_t n
   uint32_t flags[2];
   HIPCHK(c, hipMemcpyAsync(flags, c->d_flags, 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (flags[0]) return fail(c, LASSO_ERR_INVALID, "lookup index out of range (memory_address >= M, densified.rs:46)");
+  if (flags[0]) return fail(c, LASSO_ERR_INVALID, bad_msg);
   return 0;
+}
+int32_t lasso_densify_dim_slab(lasso_ctx* c, const uint64_t* d_indices, size_t n_lookups, size_t C, size_t dim, size_t s, uint32_t log_m, uint32_t world, uint32_t rank, uint32_t* d_dim_u32,
+                               lasso_fr* d_dim, lasso_fr* d_read, lasso_fr* d_final) {
+  REQUIRE(c, d_indices && d_dim_u32 && d_dim && d_read && d_final && C >= 1 && dim < C && s >= 1 && (s & (s - 1)) == 0 && n_lookups <= s && s < ((size_t)1 << 32) && log_m <= 32);
+  REQUIRE(c, world >= 1 && (world & (world - 1)) == 0 && rank < world && world <= s && world <= ((size_t)1 << log_m));
+  return densify_dim_run(c, n_lookups, s, log_m, world, rank, d_read, d_final, 8.0 * n_lookups, "lookup index out of range (memory_address >= M, densified.rs:46)", [&](uint32_t* kA, uint32_t* vA) {
+    hipLaunchKernelGGL(k_densify_extract, dim3(grid_for(s, 4096)), dim3(256), 0, c->stream, d_indices, n_lookups, C, dim, s, (uint64_t)1 << log_m, world, rank, kA, vA, d_dim_u32, (fr_t*)d_dim, c->d_flags);
+  });
+}
+// include/lasso_hip_operands.h: the same with the dimension's addresses formed from the operand columns inside the first kernel (8 or 16 bytes read per lookup instead of a
+// strided u64 of an 8 C-byte row; no index array exists)
+int32_t lasso_densify_dim_operands(lasso_ctx* c, const uint64_t* d_x, const uint64_t* d_y, size_t n_lookups, const lasso_operand_layout* layout, size_t C, size_t dim, size_t s, uint32_t log_m,
+                                   uint32_t world, uint32_t rank, uint32_t* d_dim_u32, lasso_fr* d_dim, lasso_fr* d_read, lasso_fr* d_final) {
+  REQUIRE(c, d_x && d_dim_u32 && d_dim && d_read && d_final && C >= 1 && dim < C && s >= 1 && (s & (s - 1)) == 0 && n_lookups <= s && s < ((size_t)1 << 32) && log_m <= 32);
+  REQUIRE(c, world >= 1 && (world & (world - 1)) == 0 && rank < world && world <= s && world <= ((size_t)1 << log_m));
+  if (const int bad = operand_layout_check(layout, C, log_m)) return fail(c, LASSO_ERR_INVALID, std::string("lasso_densify_dim_operands: ") + operand_layout_error(bad));
+  if ((d_y != nullptr) != (layout->operands == 2u)) return fail(c, LASSO_ERR_INVALID, "lasso_densify_dim_operands: " OPL_MSG_Y);
+  const lasso_operand_layout L = *layout;
+  return densify_dim_run(c, n_lookups, s, log_m, world, rank, d_read, d_final, 8.0 * L.operands * n_lookups, "lasso_densify_dim_operands: " OPL_MSG_FIT, [&](uint32_t* kA, uint32_t* vA) {
+    hipLaunchKernelGGL(k_densify_extract_operands, dim3(grid_for(s, 4096)), dim3(256), 0, c->stream, d_x, d_y, n_lookups, L, C, dim, s, world, rank, kA, vA, d_dim_u32, (fr_t*)d_dim, c->d_flags);
+  });
 }
 
 // ------------------------------------------------------------------ curve entry points

@@ -399,6 +399,19 @@ class Device:
         self._chk(self.lib.lasso_bullet_lr(self.ctx, C.c_void_p(bases), n, C.c_void_p(d_a), nk, C.c_void_p(d_w), _vp(tail), _vp(out)))
         return out
 
+    def densify_dim_operands(self, d_x, d_y, n_lookups, layout, c, dim, s, log_m, d_dim_u32, d_dim, d_read, d_final, world=1, rank=0):
+        """densify_dim with the dimension's addresses formed on the device from operand columns (include/lasso_hip_operands.h lasso_densify_dim_operands): d_x, d_y = device
+        pointers of n_lookups uint64 each (d_y None for a one-operand layout), layout = _abi.OperandLayout; world / rank as lasso_densify_dim_slab.  A library without
+        the entry point is an error, not a fall-back."""
+        if not hasattr(self, "_operands"):
+            try:
+                _abi.declare_operands(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_densify_dim_operands (include/lasso_hip_operands.h)")
+            self._operands = True
+        self._chk(self.lib.lasso_densify_dim_operands(self.ctx, C.c_void_p(d_x), C.c_void_p(d_y) if d_y else None, n_lookups, C.byref(layout), c, dim, s, log_m, world, rank,
+                                                      C.c_void_p(d_dim_u32), C.c_void_p(d_dim), C.c_void_p(d_read), C.c_void_p(d_final)))
+
     def densify_dim(self, d_indices, n_lookups, c, dim, s, log_m, d_dim_u32, d_dim, d_read, d_final):
         self._chk(self.lib.lasso_densify_dim(self.ctx, C.c_void_p(d_indices), n_lookups, c, dim, s, log_m, C.c_void_p(d_dim_u32), C.c_void_p(d_dim), C.c_void_p(d_read), C.c_void_p(d_final)))
 

@@ -24,6 +24,7 @@
 #include "sumcheck_phase.hpp"
 #include "hashes.hpp"
 #include "../../include/lasso_prover.h"
+#include "../csrc/operand_layout.cuh"   // lasso_operand_layout as code: the same text the device kernel compiles
 #include "../../include/lasso_custom_check.h"
 
 #include <chrono>
@@ -188,7 +189,7 @@ class Dev {
     const size_t bytes = it->second; live_.erase(it); in_use_ -= bytes;
     pool_.emplace(bytes, p);
   }
-  // a one-off buffer (the uploaded index array of densify: 8 C s bytes that nothing of that size will ever want again) goes back to the driver, not into the pool
+  // a one-off buffer (the uploaded index array or operand columns of densify: 8 C s / 16 s bytes that nothing of that size will ever want again) goes back to the driver, not into the pool
   void release(void* p) const {
     if (!p) return; auto it = live_.find(p); if (it == live_.end()) return;
     const size_t bytes = it->second; in_use_ -= bytes; live_.erase(it);
@@ -239,7 +240,7 @@ struct DBufU64 {   // read-only upload of a host u64 array
   const Dev* dev = nullptr; uint64_t* p = nullptr; size_t n = 0;
   DBufU64(const Dev& d, const uint64_t* h, size_t n_) : dev(&d), p((uint64_t*)d.alloc_bytes((n_ ? n_ : 1) * 8)), n(n_) { if (n) d.chk(lasso_upload(d.ctx, p, h, n * 8), "lasso_upload"); }
   DBufU64(const DBufU64&) = delete; DBufU64& operator=(const DBufU64&) = delete;
-  ~DBufU64() { try { if (p && dev) dev->release(p); } catch (...) {} }   // only densify's index upload uses this type: not worth keeping
+  ~DBufU64() { try { if (p && dev) dev->release(p); } catch (...) {} }   // only densify's index / operand uploads use this type: not worth keeping
 };
 struct DBufU32 {
   const Dev* dev = nullptr; uint32_t* p = nullptr; size_t n = 0;
@@ -697,9 +698,11 @@ struct DensifiedRepresentation {
   void lift_block(size_t b, lasso_fr* d_tmp) const { dev->chk(lasso_fr_from_u32(dev->ctx, block_u32(b), s_loc, d_tmp), "lasso_fr_from_u32"); }
   const lasso_fr* final_(size_t i) const { return combined_log_m_variate_polys.p + i * m_loc; }
 
-  // indices: n_lookups x C, row-major (the reference's Vec<[usize; C]>)
-  static std::unique_ptr<DensifiedRepresentation> from_lookup_indices(const Dev& d, const uint64_t* indices, size_t n_lookups, size_t C, size_t log_m) {
-    Trace tr_all("DensifiedRepresentation.from_lookup_indices", d.ctx);
+  // densified.rs:22-75 for any source of addresses: `make_source()` uploads what the dimension calls read (the index array, or the operand columns: a one-off buffer either
+  // way, back with the driver when this function returns) and returns the call that densifies dimension i into the given buffers
+  template <class MakeSource>
+  static std::unique_ptr<DensifiedRepresentation> densify_with(const Dev& d, const char* span, size_t n_lookups, size_t C, size_t log_m, MakeSource&& make_source) {
+    Trace tr_all(span, d.ctx);
     auto D = std::make_unique<DensifiedRepresentation>();
     D->dev = &d; D->C = C; D->s = next_pow2(n_lookups); D->log_m = log_m; D->m = (size_t)1 << log_m;
     const size_t s = D->s, m = D->m, P = d.comm.world;
@@ -715,16 +718,15 @@ struct DensifiedRepresentation {
     // DensePolynomial::merge pads with zeros up to the next power of two (dense_mlpoly.rs:251-261)
     if (!D->compact && n_l > 2 * C * s) d.chk(lasso_zero(d.ctx, D->combined_l_variate_polys.p + 2 * C * D->s_loc, (n_l - 2 * C * s) / P * sizeof(lasso_fr)), "lasso_zero");
     if (n_m > C * m) d.chk(lasso_zero(d.ctx, D->combined_log_m_variate_polys.p + C * D->m_loc, (n_m - C * m) / P * sizeof(lasso_fr)), "lasso_zero");
-    // densified.rs:32-57 on the device: the index array is uploaded once as the reference holds it (Vec<[usize; C]>), each dimension is one
-    // lasso_densify_dim call (stable radix sort by address -> read/final timestamps), the polynomials are written straight into the merged buffers.
-    // Slab mode: every rank sorts the whole sequence (timestamps are a property of the whole sequence) and keeps its residue class.
-    DBufU64 d_idx(d, indices, n_lookups * C);
+    // densified.rs:32-57 on the device: each dimension is one densify call (stable radix sort by address -> read/final timestamps), the polynomials are written straight
+    // into the merged buffers.  Slab mode: every rank sorts the whole sequence (timestamps are a property of the whole sequence) and keeps its residue class.
+    auto densify_dim = make_source();
     DBuf tmp_dim, tmp_read; if (D->compact) { tmp_dim = DBuf(d, D->s_loc); tmp_read = DBuf(d, D->s_loc); }
     for (size_t i = 0; i < C; i++) {
       DBufU32 d_access(d, D->s_loc);
       lasso_fr* dim_out = D->compact ? tmp_dim.p : D->combined_l_variate_polys.p + i * D->s_loc;
       lasso_fr* read_out = D->compact ? tmp_read.p : D->combined_l_variate_polys.p + (C + i) * D->s_loc;
-      d.chk(lasso_densify_dim_slab(d.ctx, d_idx.p, n_lookups, C, i, s, (uint32_t)log_m, (uint32_t)P, (uint32_t)d.comm.rank, d_access.p, dim_out, read_out, D->combined_log_m_variate_polys.p + i * D->m_loc), "lasso_densify_dim");
+      densify_dim(i, s, d_access.p, dim_out, read_out, D->combined_log_m_variate_polys.p + i * D->m_loc);
       D->dim_u32.push_back(std::move(d_access));
       if (D->compact) {
         DBufU32 r32(d, D->s_loc); uint32_t mx = 0;
@@ -735,6 +737,31 @@ struct DensifiedRepresentation {
     if (D->compact) { tmp_dim.release(); tmp_read.release(); }
     if (d.capacity) (void)lasso_trim(d.ctx);   // the sort's buffers (16 bytes per lookup of scratch) are not needed again
     return D;
+  }
+  // indices: n_lookups x C, row-major (the reference's Vec<[usize; C]>), uploaded once as the reference holds it
+  static std::unique_ptr<DensifiedRepresentation> from_lookup_indices(const Dev& d, const uint64_t* indices, size_t n_lookups, size_t C, size_t log_m) {
+    return densify_with(d, "DensifiedRepresentation.from_lookup_indices", n_lookups, C, log_m, [&] {
+      auto d_idx = std::make_shared<DBufU64>(d, indices, n_lookups * C);
+      return [&d, d_idx, n_lookups, C, log_m](size_t i, size_t s, uint32_t* access, lasso_fr* dim_out, lasso_fr* read_out, lasso_fr* final_out) {
+        d.chk(lasso_densify_dim_slab(d.ctx, d_idx->p, n_lookups, C, i, s, (uint32_t)log_m, (uint32_t)d.comm.world, (uint32_t)d.comm.rank, access, dim_out, read_out, final_out), "lasso_densify_dim");
+      };
+    });
+  }
+  // The same representation from OPERAND columns (include/lasso_hip_operands.h): the addresses of dimension i are formed inside its densify call, the index array never
+  // exists.  x, y: n_lookups 64-bit operands each (y null for a one-operand layout), host pointers that are uploaded (8 or 16 bytes per lookup, whatever C is) or — on_device —
+  // device pointers used as they are.  `entry` = lasso_densify_dim_operands of the device library; the caller has checked the layout (operand_layout_check).
+  typedef int32_t (*OperandsEntry)(lasso_ctx*, const uint64_t*, const uint64_t*, size_t, const lasso_operand_layout*, size_t, size_t, size_t, uint32_t, uint32_t, uint32_t, uint32_t*, lasso_fr*, lasso_fr*, lasso_fr*);
+  static std::unique_ptr<DensifiedRepresentation> from_operands(const Dev& d, OperandsEntry entry, const lasso_operand_layout& layout, const uint64_t* x, const uint64_t* y, bool on_device, size_t n_lookups,
+                                                                size_t C, size_t log_m, uint64_t* dims_counter) {
+    return densify_with(d, "DensifiedRepresentation.from_operands", n_lookups, C, log_m, [&] {
+      std::shared_ptr<DBufU64> ux, uy;
+      if (!on_device) { ux = std::make_shared<DBufU64>(d, x, n_lookups); if (y) uy = std::make_shared<DBufU64>(d, y, n_lookups); }
+      const uint64_t* px = on_device ? x : ux->p; const uint64_t* py = !y ? nullptr : on_device ? y : uy->p;
+      return [&d, ux, uy, px, py, entry, layout, n_lookups, C, log_m, dims_counter](size_t i, size_t s, uint32_t* access, lasso_fr* dim_out, lasso_fr* read_out, lasso_fr* final_out) {
+        d.chk(entry(d.ctx, px, py, n_lookups, &layout, C, i, s, (uint32_t)log_m, (uint32_t)d.comm.world, (uint32_t)d.comm.rank, access, dim_out, read_out, final_out), "lasso_densify_dim_operands");
+        if (dims_counter) ++*dims_counter;
+      };
+    });
   }
   SparsePolynomialCommitment commit(const SparsePolyCommitmentGens& gens) const {  // densified.rs:78-96
     Trace tr_all("DensifiedRepresentation.commit", dev->ctx);

@@ -6,6 +6,7 @@
 #include "../../include/lasso_prover.h"
 #include "../../include/lasso_hip_wire.h"
 #include "../../include/lasso_hip_msm.h"
+#include "../../include/lasso_hip_operands.h"
 
 using namespace lasso;
 
@@ -21,6 +22,12 @@ extern "C" int32_t lasso_points_decompress(lasso_ctx*, const uint8_t*, size_t, l
 // No size threshold (LASSO_MSM_POINTS_MIN) yet: tools/verify_bench.py --ab msm_points is what one would be set from.
 extern "C" int32_t lasso_msm_points(lasso_ctx*, const lasso_affine*, const lasso_fr*, size_t, lasso_point*) __attribute__((weak));
 
+// Densify from operand columns (include/lasso_hip_operands.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
+// lasso_host_densify_operands then expands the operands to indices on the host (lasso_host_operand_indices) and takes lasso_host_densify's path.
+// LASSO_DENSIFY_OPERANDS=0 does the same where the entry point exists (A/B switch).
+extern "C" int32_t lasso_densify_dim_operands(lasso_ctx*, const uint64_t*, const uint64_t*, size_t, const lasso_operand_layout*, size_t, size_t, size_t, uint32_t, uint32_t, uint32_t, uint32_t*, lasso_fr*,
+                                              lasso_fr*, lasso_fr*) __attribute__((weak));
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -29,6 +36,7 @@ struct lasso_host {
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
   uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
   uint64_t msm_points_calls = 0;     // Verifier::msm_points calls of this host that took lasso_msm_points (lasso_host_msm_stats)
+  uint64_t operand_dims = 0;         // dimensions densified by lasso_densify_dim_operands for this host (lasso_host_densify_stats)
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
   WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
   explicit lasso_host(int device) : dev(device) {}
@@ -148,6 +156,58 @@ int32_t lasso_host_densify(lasso_host* h, const uint64_t* indices, size_t n, siz
   GUARD(std::unique_ptr<lasso_host_dense> d(new lasso_host_dense(h)); d->d = DensifiedRepresentation::from_lookup_indices(h->dev, indices, n, c, log_m); *out = d.release(); return 0;)
 }
 void lasso_host_dense_free(lasso_host_dense* d) { delete d; }
+// ---- densify from operand columns (include/lasso_hip_operands.h, lasso_amd/csrc/operand_layout.cuh)
+static void check_operand_args(const char* who, const lasso_operand_layout* L, const uint64_t* x, const uint64_t* y, size_t n, size_t c, size_t log_m) {
+  if (const int bad = operand_layout_check(L, c, log_m)) throw Error(std::string(who) + ": " + operand_layout_error(bad));
+  if ((y != nullptr) != (L->operands == 2u)) throw Error(std::string(who) + ": " OPL_MSG_Y);
+  if (!x && n) throw Error(std::string(who) + ": null operand column");
+}
+// an operand that does not fit, in the words the device path reports it with (Dev::chk of lasso_densify_dim_operands' LASSO_ERR_INVALID): one text whichever path ran
+static Error operand_unfit() { return Error("lasso_densify_dim_operands failed (" + std::to_string((int)LASSO_ERR_INVALID) + "): lasso_densify_dim_operands: " OPL_MSG_FIT); }
+static void expand_operands(const lasso_operand_layout& L, const uint64_t* x, const uint64_t* y, size_t n, size_t c, uint64_t* indices) {
+  for (size_t k = 0; k < n; k++) {
+    const uint64_t vx = x[k], vy = y ? y[k] : 0;
+    if (!operand_fits(vx, c, L.chunk_bits) || !operand_fits(vy, c, L.chunk_bits)) throw operand_unfit();
+    for (size_t i = 0; i < c; i++) indices[k * c + i] = operand_index(L, vx, vy, c, i);
+  }
+}
+int32_t lasso_host_operand_layout(const lasso_strategy* st, lasso_operand_layout* out) {
+  GUARD(
+    if (!st || !out) throw Error("lasso_host_operand_layout: null argument");
+    const bool two = st->kind == LASSO_AND || st->kind == LASSO_OR || st->kind == LASSO_XOR || st->kind == LASSO_LT;
+    if (!two && st->kind != LASSO_RANGE) throw Error("lasso_host_operand_layout: this strategy kind has no built-in operand layout (the caller passes its own)");
+    if (st->log_m < 1 || st->log_m > 32) throw Error("lasso_host_operand_layout: log_m must be 1 .. 32");
+    if (two && (st->log_m & 1u)) throw Error("lasso_host_operand_layout: a two-operand strategy splits log_m evenly between its operands: log_m must be even");
+    out->operands = two ? 2u : 1u; out->chunk_bits = two ? st->log_m / 2 : st->log_m; out->msb_first = st->kind == LASSO_LT ? 1u : 0u;   // lt.rs:60-69: LT[0] is the top chunk
+    return 0;)
+}
+int32_t lasso_host_operand_indices(const lasso_operand_layout* L, const uint64_t* x, const uint64_t* y, size_t n, size_t c, size_t log_m, uint64_t* indices) {
+  GUARD(
+    check_operand_args("lasso_host_operand_indices", L, x, y, n, c, log_m);
+    if (!indices && n) throw Error("lasso_host_operand_indices: null output");
+    expand_operands(*L, x, y, n, c, indices);
+    return 0;)
+}
+int32_t lasso_host_densify_operands(lasso_host* h, const lasso_operand_layout* L, const uint64_t* x, const uint64_t* y, size_t n, size_t c, size_t log_m, int32_t where, lasso_host_dense** out) {
+  GUARD(
+    if (!h || !out || (where != 0 && where != 1)) throw Error("lasso_host_densify_operands: null argument, or `where` is neither 0 (host pointers) nor 1 (device pointers)");
+    check_operand_args("lasso_host_densify_operands", L, x, y, n, c, log_m);
+    const bool device = lasso_densify_dim_operands && sw::densify_operands();
+    if (where == 1 && !device)
+      throw Error("lasso_host_densify_operands: device-resident operands need lasso_densify_dim_operands (include/lasso_hip_operands.h), which the device library this host was linked against does not have (or LASSO_DENSIFY_OPERANDS=0 keeps out)");
+    std::unique_ptr<lasso_host_dense> d(new lasso_host_dense(h));
+    if (device) d->d = DensifiedRepresentation::from_operands(h->dev, &lasso_densify_dim_operands, *L, x, y, where == 1, n, c, log_m, &h->operand_dims);
+    else { std::vector<uint64_t> idx(n * c); expand_operands(*L, x, y, n, c, idx.data()); d->d = DensifiedRepresentation::from_lookup_indices(h->dev, idx.data(), n, c, log_m); }
+    *out = d.release(); return 0;)
+}
+int32_t lasso_host_densify_stats(lasso_host* h, uint64_t* operand_dims_on_device, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_densify_stats: null host");
+    if (operand_dims_on_device) *operand_dims_on_device = h->operand_dims;
+    if (available) *available = lasso_densify_dim_operands ? 1 : 0;
+    if (reset) h->operand_dims = 0;
+    return 0;)
+}
 int32_t lasso_host_dense_info(lasso_host_dense* d, uint64_t* device_bytes, int32_t* compact) {
   if (!d || !d->d) return LASSO_ERR_INVALID;
   const DensifiedRepresentation& D = *d->d;

@@ -29,6 +29,7 @@ inline size_t host_tail(bool ifma) { static const size_t v = [&] { const char* e
 LASSO_SWITCH(bool, verify_device_points, unless0(getenv("LASSO_VERIFY_DEVICE_POINTS")))   // on; the verifier decodes compressed points on the device
 LASSO_SWITCH(size_t, wire_device_min, [] { const char* e = getenv("LASSO_WIRE_DEVICE_MIN"); const long long x = e ? atoll(e) : 376; return (size_t)(x < 1 ? 1 : x); }())   // 376 (the smallest batch measured with the device ahead), at least 1
 LASSO_SWITCH(bool, verify_msm_points, unless0(getenv("LASSO_VERIFY_MSM_POINTS")))         // on; the verifier's MSMs over commitment rows run table-free (lasso_msm_points) instead of lasso_bases_create + lasso_msm
+LASSO_SWITCH(bool, densify_operands, unless0(getenv("LASSO_DENSIFY_OPERANDS")))           // on; lasso_host_densify_operands forms the chunk indices on the device (off: expanded on the host, then the index path)
 // the two read per CALL, not per process (a test sets them between calls):
 inline bool slab_rccl() { return unless0(getenv("LASSO_SLAB_RCCL")); }             // on; slab mode's bulk exchange over RCCL (lasso_host_set_comm_shm)
 inline bool debug_cubic_host() { return if1(getenv("LASSO_DEBUG_CUBIC_HOST")); }   // off; lasso_host_debug_prove_cubic_batched runs the HOST rounds

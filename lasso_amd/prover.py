@@ -52,6 +52,11 @@ def declare_prover(lib):
     lib.lasso_host_gens_free.argtypes = [vp]
     lib.lasso_host_densify.argtypes = [vp, vp, sz, sz, sz, C.POINTER(vp)]
     lib.lasso_host_dense_free.argtypes = [vp]
+    lay = C.POINTER(_abi.OperandLayout)
+    lib.lasso_host_operand_layout.argtypes = [C.POINTER(_abi.Strategy), lay]
+    lib.lasso_host_operand_indices.argtypes = [lay, vp, vp, sz, sz, sz, vp]
+    lib.lasso_host_densify_operands.argtypes = [vp, lay, vp, vp, sz, sz, sz, i32, C.POINTER(vp)]
+    lib.lasso_host_densify_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
     lib.lasso_host_dense_info.argtypes = [vp, u64p, C.POINTER(C.c_int32)]
     lib.lasso_host_commit.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
     lib.lasso_host_prove.argtypes = [vp, vp, vp, C.POINTER(_abi.Strategy), vp, sz, C.c_char_p, C.c_char_p, vp, sz, C.POINTER(sz)]
@@ -83,6 +88,7 @@ class HostProver:
         if self.lib.lasso_host_create(device, C.byref(h)) != 0:
             raise LassoError("lasso_host_create: " + self.lib.lasso_host_last_error().decode())
         self.h = h
+        self.device = device
 
     def set_comm(self, group):
         """Slab mode (one proof sharded over the ranks of `group`, lasso_amd.parallel.Group): must precede gens()/densify()."""
@@ -140,6 +146,57 @@ class HostProver:
         d = C.c_void_p()
         self._chk(self.lib.lasso_host_densify(self.h, indices.ctypes.data_as(C.c_void_p), indices.shape[0], indices.shape[1], log_m, C.byref(d)))
         return d
+
+    def operand_layout(self, strategy):
+        """the operand layout of a built-in strategy (lasso_host_operand_layout): AND / OR / XOR (2, log_m / 2, 0), LT (2, log_m / 2, 1), RangeCheck (1, log_m, 0);
+        LassoError for a strategy without one (the caller then passes its own _abi.OperandLayout)"""
+        out = _abi.OperandLayout()
+        self._chk(self.lib.lasso_host_operand_layout(strategy_ptr(strategy), C.byref(out)))
+        return out
+
+    def operand_indices(self, x, y=None, *, layout, c, log_m):
+        """the (n, c) uint64 lookup indices of the operand columns x, y under `layout` (lasso_host_operand_indices): the normative CPU statement of the layout, what
+        densify() takes"""
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        y = None if y is None else np.ascontiguousarray(y, dtype=np.uint64).reshape(-1)
+        if y is not None and y.shape != x.shape:
+            raise LassoError("operand_indices: x and y must have the same length")
+        out = np.zeros((x.shape[0], c), dtype=np.uint64)
+        vpt = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.lasso_host_operand_indices(C.byref(layout), vpt(x), vpt(y), x.shape[0], c, log_m, vpt(out)))
+        return out
+
+    def densify_operands(self, x, y=None, *, layout, c, log_m):
+        """densify(operand_indices(x, y)) without the index array (lasso_host_densify_operands): each dimension's addresses are formed on the device inside its densify
+        pass.  x, y: numpy uint64 arrays (uploaded: 8 bytes per operand and lookup, whatever c is), or torch tensors ALREADY ON THE GPU — contiguous, one-dimensional int64
+        (reinterpreted as unsigned) on the device of this host's context — which are used where they are.  y = None for a one-operand layout."""
+        cols = [a for a in (x, y) if a is not None]
+        on_device = [hasattr(a, "data_ptr") and hasattr(a, "is_cuda") for a in cols]
+        if any(on_device) != all(on_device):
+            raise LassoError("densify_operands: x and y must both be numpy arrays or both be tensors on the GPU")
+        d = C.c_void_p()
+        if all(on_device):
+            import torch
+            for a in cols:
+                if not a.is_cuda or a.dtype != torch.int64 or a.dim() != 1 or not a.is_contiguous() or a.shape != cols[0].shape or a.device.index != self.device:
+                    raise LassoError(f"densify_operands: tensors must be one-dimensional contiguous int64 of one length on GPU {self.device}, the device of this host's context")
+            torch.cuda.current_stream(cols[0].device).synchronize()      # whatever wrote the columns has finished; the call below is synchronous, `cols` holds the references
+            ptrs = [C.c_void_p(a.data_ptr()) for a in cols] + [None] * (2 - len(cols))
+            self._chk(self.lib.lasso_host_densify_operands(self.h, C.byref(layout), ptrs[0], ptrs[1], cols[0].shape[0], c, log_m, 1, C.byref(d)))
+            return d
+        cols = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in cols]
+        if len(cols) == 2 and cols[1].shape != cols[0].shape:
+            raise LassoError("densify_operands: x and y must have the same length")
+        ptrs = [a.ctypes.data_as(C.c_void_p) for a in cols] + [None] * (2 - len(cols))
+        self._chk(self.lib.lasso_host_densify_operands(self.h, C.byref(layout), ptrs[0], ptrs[1], cols[0].shape[0], c, log_m, 0, C.byref(d)))
+        return d
+
+    def densify_stats(self, reset=False):
+        """{"operand_dims_on_device": dimensions this host densified through lasso_densify_dim_operands so far, "available": whether the device library has that entry}
+        (lasso_host_densify_stats)"""
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(self.lib.lasso_host_densify_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"operand_dims_on_device": k.value, "available": bool(a.value)}
 
     def dense_info(self, dense):
         """device bytes a densified representation holds, and whether dim / read are in capacity mode's compact form"""
