@@ -132,3 +132,8 @@ def test_gpu_bn254_custom_strategy_kernel_level():
 def test_gpu_bn254_msm_variants():
     """tests/test_gpu_msm_variants.py on the BN254 build: every switched MSM kernel against the BN254 mock."""
     _rerun_on_bn254("test_gpu_msm_variants.py")
+
+
+def test_gpu_bn254_round_variants():
+    """tests/test_gpu_round_variants.py on the BN254 build: every switched cubic-round kernel against the BN254 mock."""
+    _rerun_on_bn254("test_gpu_round_variants.py")

@@ -10,6 +10,7 @@ from fieldref import L as FR_P, limbs, to_mont
 from gpuutil import compress_points, gens, load_mock, rand_fr, small_fr
 from lasso_amd import _abi
 from msmvariants import FULL_WIDTH_WIDE_SHAPES, HYRAX_COMMIT_SHAPES, HYRAX_COMMIT_U32_SHAPES
+from roundvariants import CUBIC_EQW2_SHAPES, CUBIC_EQW_ROUND_FUSED_SHAPES, CUBIC_EQW_ROUND_SHAPES, CUBIC_ROUND0_EQ_SHAPES, CUBIC_ROUND_AHEAD_SHAPES, LAYER_AHEAD_SHAPES
 
 pytestmark = pytest.mark.gpu
 
@@ -848,7 +849,7 @@ def test_bullet_round_launched_ahead(devs, n, nk):
         assert np.array_equal(x, y) and np.array_equal(x, z)
 
 
-@pytest.mark.parametrize("n,ncirc", [(2, 1), (4, 2), (16, 33), (128, 5), (256, 2), (1 << 9, 2), (1 << 13, 8), (1 << 16, 3)])   # n <= 128: latency-shaped kernel
+@pytest.mark.parametrize("n,ncirc", CUBIC_EQW_ROUND_SHAPES)   # n <= 128: latency-shaped kernel (tests/roundvariants.py; tests/test_round_reach_cpu.py checks that)
 def test_sumcheck_cubic_eqw_round(devs, n, ncirc):
     """eq-weighted round sums: sum_i A(x)[i] B(x)[i] E[i] at x = 0, 2, 3, vs the oracle's loop"""
     rng = np.random.default_rng(n * 3 + ncirc)
@@ -864,7 +865,7 @@ def test_sumcheck_cubic_eqw_round(devs, n, ncirc):
     assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("n,ncirc", [(4, 1), (8, 2), (32, 33), (256, 5), (512, 2), (1 << 10, 2), (1 << 14, 8), (1 << 17, 3)])   # n <= 256: latency-shaped kernel
+@pytest.mark.parametrize("n,ncirc", CUBIC_EQW_ROUND_FUSED_SHAPES)   # n <= 256: latency-shaped kernel (tests/roundvariants.py)
 def test_sumcheck_cubic_eqw_round_fused(devs, n, ncirc):
     """bind A, B with r then the eq-weighted sums of the next round in one pass == bind_top followed by the plain eq-weighted round (sumcheck.rs:49-120)"""
     rng = np.random.default_rng(n * 5 + ncirc)
@@ -893,7 +894,7 @@ def test_sumcheck_cubic_eqw_round_fused(devs, n, ncirc):
     assert np.array_equal(bound(devs[0]), a[2][0])
 
 
-@pytest.mark.parametrize("n,ncirc", [(2, 1), (4, 1), (8, 2), (32, 33), (256, 5), (512, 2), (1 << 10, 2), (1 << 14, 8), (1 << 17, 3)])
+@pytest.mark.parametrize("n,ncirc", CUBIC_EQW2_SHAPES)   # tests/roundvariants.py
 def test_sumcheck_cubic_eqw2(devs, n, ncirc):
     """two-sum form of the eq-weighted round (begin + wait): (q(0), q_inf) per circuit, with and without the fused bind; q(0) must equal the
     three-sum form's value at 0 and q_inf must reproduce its values at 2 and 3 through q(x) = q(0) + (q(1) - q(0) - q_inf) x + q_inf x^2"""
@@ -1029,8 +1030,7 @@ def test_abort_releases_a_waiting_linear_tail_kernel(devs):
         d.free(p)
 
 
-@pytest.mark.parametrize("n,ncirc,scaled", [(256, 2, False), (512, 3, True), (1 << 12, 2, False), (1 << 14, 2, True), (1 << 15, 5, False), (1 << 15, 16, True),
-                                             (1 << 16, 2, True), (1 << 18, 3, False), (1 << 20, 1, True), (1 << 17, 9, False)])   # above 2^14 entries: factor tables in memory (EqGlobal)
+@pytest.mark.parametrize("n,ncirc,scaled", CUBIC_ROUND0_EQ_SHAPES)   # above 2^14 entries: factor tables in memory (tests/roundvariants.py)
 def test_sumcheck_cubic_round0_with_inline_eq_table(devs, n, ncirc, scaled):
     """lasso_sumcheck_cubic_eqw2_begin_eq: the first round of a layer with the layer's eq table built inside the launch == lasso_eq_evals_scaled followed by the plain
     first round — same two sums per circuit AND the same table bytes left behind for the later rounds (real library and the oracle's mock)"""
@@ -1556,7 +1556,7 @@ def test_cubic_tail_hands_its_arrays_over(devs, n, ncirc, bind, m_stop):
     assert [v[0] for v in vals] == heads
 
 
-@pytest.mark.parametrize("n,ncirc", [(512, 2), (1 << 12, 2), (1 << 12, 8), (1 << 16, 2), (1 << 18, 3), (1 << 20, 2), (1 << 13, 16)])
+@pytest.mark.parametrize("n,ncirc", CUBIC_ROUND_AHEAD_SHAPES)   # tests/roundvariants.py
 def test_cubic_round_launched_ahead(devs, n, ncirc):
     """lasso_sumcheck_cubic_eqw2_begin_ahead + lasso_challenge_post == lasso_sumcheck_cubic_eqw2_begin with the same challenge — sums and the bound arrays — when the round is
     enqueued while the previous round's result is still pending (the prover's schedule), device and mock; a round that never gets its challenge is released by lasso_abort at once;
@@ -1664,8 +1664,7 @@ def test_cubic_tail_launched_ahead(devs, n, ncirc, m_stop):
                 assert np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("n2,ncirc2,m_stop2,mode", [(1 << 12, 2, 1, "post"), (1 << 15, 3, 1, "post"), (1 << 17, 2, 1, "post"), (1 << 18, 9, 1, "post"), (512, 2, 4, "post"), (1024, 2, 1, "post"),
-                                                    (64, 9, 2, "post"), (1 << 13, 2, 1, "cancel"), (1 << 17, 2, 1, "cancel"), (512, 2, 8, "cancel")])
+@pytest.mark.parametrize("n2,ncirc2,m_stop2,mode", LAYER_AHEAD_SHAPES)   # tests/roundvariants.py
 def test_layer_enqueued_ahead_of_its_point(devs, n2, ncirc2, m_stop2, mode):
     """lasso_sumcheck_cubic_eqw2_begin_eq_ahead / lasso_sumcheck_cubic_tail_begin_eq_ahead + lasso_point_post: the NEXT layer's first launch enqueued while the current layer's
     resident tail is still answering, its eq point delivered afterwards == the plain entry points called after the layer (sums, the table left behind, every turn of a resident

@@ -205,7 +205,9 @@ _SWITCH_WANT = {}      # instance -> digest of the default configuration's commi
                                  {"LASSO_MSM_DIRECT_WGS": "7"}, {"LASSO_MSM_DIRECT_WGS": "1024"},  # workgroups of the openings' latency-shaped launches: chunks per row and items per chunk of k_msm_direct / k_bullet_msm
                                  {"LASSO_SIDE_STREAM": "0"},                 # no second context: E's commitment and the openings' preparation on the primary stream
                                  # a tuple: (setting, instance of _SWITCH_INSTANCES) — the settings that need a full-width commitment of more than 16 rows to select another kernel
-                                 ({"LASSO_MSM_FULL8": "1"}, "spark"), ({"LASSO_MSM_ROWS8": "0"}, "spark"), ({"LASSO_MSM_DIRECT": "0"}, "spark")])
+                                 ({"LASSO_MSM_FULL8": "1"}, "spark"), ({"LASSO_MSM_ROWS8": "0"}, "spark"), ({"LASSO_MSM_DIRECT": "0"}, "spark"),
+                                 # LASSO_LB_NT=1 where a proof reaches it: with every layer's eq table from its own kernels, round 0 is the plain table-reading round the non-temporal form serves
+                                 {"LASSO_LB_NT": "1", "LASSO_EQ_INLINE": "0"}])
 def test_gpu_ab_switches_do_not_change_the_bytes(host, env):
     """The A/B switches the measurements in DESIGN.md rest on (flag protocol instead of tagged results, in-launch second stage, launch per round instead of the resident tails, ...)
     select other kernels / protocols for the same arithmetic: commitment and proof must be the bytes of the default configuration.  Each setting runs in its own process
@@ -216,6 +218,13 @@ def test_gpu_ab_switches_do_not_change_the_bytes(host, env):
     to have been chosen at all — the matrices committed here have at most a few hundred rows, so both settings leave every launch as it was; LASSO_MSM_FULL8=1 needs full-width scalars
     on more than 16 rows (or wire bytes) — the AND instance commits small integers only, hence the Spark instance, whose E rows are field elements; wire bytes by hipMemcpy
     (MSM_R_COMPRESSED_MEMCPY) need more than 2^16 rows; and LASSO_MSM_DIRECT_WGS at 1 and 4096, the ends of its range.
+    The cubic rounds likewise: which launches a proof makes under a setting is the host prover's business, and nothing here shows that they include the kernel the setting is about.
+    With LASSO_EQ_INLINE on (the default) every streaming layer starts through lasso_sumcheck_cubic_eqw2_begin_eq or behind the point gate, so round 0 never is the plain
+    table-reading round without k_eq_outer in front: LASSO_LB_NT=1 alone selects k_cubic_eqw_lb<2, false, TP, EqNone, true> nowhere in a proof — hence the setting with
+    LASSO_EQ_INLINE=0 above.  The instantiations and boundaries cubic_plan (launch_plan.cuh) selects among — the narrow fused round launched ahead with either wait, the in-kernel
+    wait on hundreds of workgroups, the grids on both sides of LASSO_DIRECT_NX and at the cap LASSO_CUBIC_NX sets, the plain loop behind k_eq_outer, EqGlobal behind the gate, the
+    pointer tables of more than 8 circuits under each of them, the profiled round launched ahead — run at kernel level in tests/test_gpu_round_variants.py, one child process per
+    setting, at the shapes of tests/roundvariants.py; tests/test_round_reach_cpu.py shows on the CPU that each shape reaches its instantiation.
     Still untested anywhere: LASSO_SLAB_OPEN and LASSO_SLAB_RCCL (slab mode: they need several contexts side by side) and LASSO_THROUGHPUT_AHEAD."""
     import hashlib, os, subprocess, sys
     env, inst = env if isinstance(env, tuple) else (env, "and")
