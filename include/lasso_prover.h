@@ -190,6 +190,18 @@ int32_t lasso_host_msm_points(lasso_host* h, const lasso_affine* points, const l
 /* *points_calls = MSMs over commitment rows this host's verifier has run through lasso_msm_points so far; *available = 1 when the device library has the entry; either may
  * be NULL; reset != 0 zeroes the counter. */
 int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* available, int32_t reset);
+/* Label-derived generators, the arithmetic half: n candidates of ark-ec's `Projective::rand` (limbs = n x 4 words that ARE the Montgomery representation of the
+ * coordinate, greatest = n root choices, as the ChaCha stream of a label yields them) turned into points.  status[i] = a lasso_cand_status (include/lasso_hip_gens.h: ok,
+ * limbs not below the modulus, no point with this coordinate); out[i] = the affine point in the form lasso_host_gens_from_points takes (curve25519: times the cofactor,
+ * normalised), all zero unless status[i] is ok; out may be NULL.  where = 0: on the host, one candidate after the other; where = 1: on the device, all candidates in one
+ * launch (lasso_points_from_candidates) — -1 with a message when the device library this host was linked against does not have it.  Returns 0 even when some candidates
+ * yield no point: the per-candidate outcome is in status.
+ * lasso_host_gens_new takes the same device call for the candidates of a label's stream when it exists and the set needs at least LASSO_GENS_DEVICE_MIN points
+ * (LASSO_GENS_DEVICE_BATCH caps the candidates per call); LASSO_GENS_DEVICE=0 keeps the host route.  The generators do not depend on the route. */
+int32_t lasso_host_points_from_candidates(lasso_host* h, const uint64_t* limbs, const uint8_t* greatest, size_t n, int32_t where, lasso_affine* out, uint8_t* status);
+/* *device_candidates = candidates this host has handed to the device so far (lasso_host_gens_new and lasso_host_points_from_candidates(where = 1) together);
+ * *available = 1 when the device library has the entry; either may be NULL; reset != 0 zeroes the counter. */
+int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_t* available, int32_t reset);
 /* Validate a strategy descriptor without proving anything: 0, or LASSO_ERR_INVALID (-1) with the reason in lasso_host_last_error().  For kind = LASSO_CUSTOM
  * (include/lasso_hip.h lasso_strategy_custom, passed as (const lasso_strategy*)&custom) this is the check lasso_host_prove* / lasso_host_verify* make on entry: table pointers,
  * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (2^log_m products per memory): THE TABLES ARE PART OF THE STATEMENT,

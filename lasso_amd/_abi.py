@@ -186,4 +186,16 @@ def declare_operands(lib):
     return ["lasso_densify_dim_operands"]
 
 
+CAND_STATUS = ["ok", "non-canonical", "no-point"]   # include/lasso_hip_gens.h lasso_cand_status
+
+
+def declare_gens(lib):
+    """include/lasso_hip_gens.h — stream candidates to generator points.  Declared apart from declare(), as declare_wire and declare_msm_points are: an implementation of
+    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
+    fn = lib.lasso_points_from_candidates
+    fn.restype = i32
+    fn.argtypes = [vp, vp, vp, sz, vp, vp]
+    return ["lasso_points_from_candidates"]
+
+
 HEADER_SYMBOLS = None

@@ -10,6 +10,7 @@
 #include "fq.cuh"
 #include "mont29.cuh"
 #include "../../include/lasso_hip_wire.h"   // lasso_wire_status: what pt_decompress returns
+#include "../../include/lasso_hip_gens.h"   // lasso_cand_status: what pt_from_candidate returns
 
 struct Bn254FqM {
   static LHD int32_t p(int k) { const int32_t P[9] = {410844487, 17064118, 477274959, 47522512, 361093496, 47923392, 10936641, 240920116, 3171406}; return P[k]; }
@@ -220,10 +221,32 @@ LHD void pt_compress(const pt29& p, uint32_t* out) {
   for (int i = 7; i >= 0; i--) if (yw[i] != nyw[i]) { neg = yw[i] > nyw[i]; break; }
   if (neg) out[7] |= 0x80000000u;
 }
+// y from x, shared by pt_decompress and pt_from_candidate: x reduced (x 2^261).  y = (x^3 + 3)^((q + 1) / 4) (q = 3 mod 4), verified by squaring: false when x^3 + 3 is no
+// square.  Otherwise Y = the root `larger` asks for (the larger or the smaller of y and q - y as canonical integers; y = 0 is both), reduced, and sign = "Y > -Y".
+// Bounds: t is a weakened sum of a product output and a small multiple of one; the ladder squares and multiplies reduced values; -y of a reduced y is reduced.
+LHD bool pt_y_from_x(const fe29& x, bool larger, fe29& Y, bool& sign) {
+  const fe29 t = fe_weak(fe_add(fe_mul(fe_sqr(x), x), fe_small(fe_one(), 3)));
+  const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};   // (q + 1) / 4: 252 bits
+  fe29 y = t;
+#pragma unroll 1
+  for (int i = 250; i >= 0; i--) { y = fe_sqr(y); if ((e[i >> 5] >> (i & 31)) & 1u) y = fe_mul(y, t); }
+  uint32_t sw[8], tw[8]; fe_to_plain_words(fe_sqr(y), sw); fe_to_plain_words(t, tw);
+  uint32_t diff = 0; for (int i = 0; i < 8; i++) diff |= sw[i] ^ tw[i];
+  if (diff) return false;
+  const fe29 ny = fe_neg(y);
+  uint32_t yw[8], nyw[8]; fe_to_plain_words(y, yw); fe_to_plain_words(ny, nyw);
+  bool y_larger = false;   // ny < y as canonical integers
+  for (int i = 7; i >= 0; i--) if (yw[i] != nyw[i]) { y_larger = nyw[i] < yw[i]; break; }
+  const bool take_y = larger == y_larger;
+  for (int k = 0; k < 9; k++) Y.v[k] = take_y ? y.v[k] : ny.v[k];
+  sign = false;   // Y > -Y
+  for (int i = 7; i >= 0; i--) if (yw[i] != nyw[i]) { sign = take_y ? nyw[i] < yw[i] : yw[i] < nyw[i]; break; }
+  return true;
+}
 // ark-ec's deserialize_compressed with Validate::Yes for a short-Weierstrass point, the mirror of decompress_point in lasso_amd/host/verifier.hpp: in = 8 little-endian
 // words (canonical x, bit 255 = "y is the larger root", bit 254 = infinity).  Returns a lasso_wire_status; on LASSO_WIRE_OK aff = the affine point as lasso_affine holds it
 // (x then y, 8 words each, ark-ff's Montgomery limbs) and canon = serialize_compressed of the decoded point; LASSO_WIRE_OK_IDENTITY: aff zero, canon = the identity's encoding
-// (x = 0 under the flag, whatever x came in); all zero otherwise.  y = (x^3 + 3)^((q + 1) / 4) (q = 3 mod 4), verified by squaring.  G1 has cofactor 1: no subgroup check.
+// (x = 0 under the flag, whatever x came in); all zero otherwise.  y from x and the flag: pt_y_from_x above.  G1 has cofactor 1: no subgroup check.
 LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
   for (int i = 0; i < 16; i++) aff[i] = 0;
   for (int i = 0; i < 8; i++) canon[i] = 0;
@@ -235,24 +258,27 @@ LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
   if (infinity) { canon[7] = 0x40000000u; return LASSO_WIRE_OK_IDENTITY; }
   const int32_t K522[9] = {Bn254FqM::K522_0, Bn254FqM::K522_1, Bn254FqM::K522_2, Bn254FqM::K522_3, Bn254FqM::K522_4, Bn254FqM::K522_5, Bn254FqM::K522_6, Bn254FqM::K522_7, Bn254FqM::K522_8};
   const fe29 x = fe_mul(m29_unpack_words<Bn254FqM>(w), m29_const<Bn254FqM>(K522));   // the integer x times 2^522 / 2^261
-  const fe29 t = fe_weak(fe_add(fe_mul(fe_sqr(x), x), fe_small(fe_one(), 3)));
-  const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};   // (q + 1) / 4: 252 bits
-  fe29 y = t;
-#pragma unroll 1
-  for (int i = 250; i >= 0; i--) { y = fe_sqr(y); if ((e[i >> 5] >> (i & 31)) & 1u) y = fe_mul(y, t); }
-  uint32_t sw[8], tw[8]; fe_to_plain_words(fe_sqr(y), sw); fe_to_plain_words(t, tw);
-  uint32_t diff = 0; for (int i = 0; i < 8; i++) diff |= sw[i] ^ tw[i];
-  if (diff) return LASSO_WIRE_NOT_ON_CURVE;
-  const fe29 ny = fe_neg(y);
-  uint32_t yw[8], nyw[8]; fe_to_plain_words(y, yw); fe_to_plain_words(ny, nyw);
-  bool y_larger = false;   // ny < y as canonical integers
-  for (int i = 7; i >= 0; i--) if (yw[i] != nyw[i]) { y_larger = nyw[i] < yw[i]; break; }
-  const bool take_y = neg == y_larger;
-  fe29 Y; for (int k = 0; k < 9; k++) Y.v[k] = take_y ? y.v[k] : ny.v[k];
+  fe29 Y; bool sign;
+  if (!pt_y_from_x(x, neg, Y, sign)) return LASSO_WIRE_NOT_ON_CURVE;
   const fq_t xm = fe_to_fq(x), ym = fe_to_fq(Y);
-  bool sign = false;   // Y > -Y
-  for (int i = 7; i >= 0; i--) if (yw[i] != nyw[i]) { sign = take_y ? nyw[i] < yw[i] : yw[i] < nyw[i]; break; }
   for (int i = 0; i < 8; i++) { aff[i] = xm.v[i]; aff[8 + i] = ym.v[i]; canon[i] = w[i]; }
   if (sign) canon[7] |= 0x80000000u;
   return LASSO_WIRE_OK;
+}
+
+// ------------------------------------------------------------------ generators from stream candidates (include/lasso_hip_gens.h)
+// The arithmetic half of ark-ec's `Projective::rand` for a short Weierstrass curve (point_from_candidate in lasso_amd/host/prover.hpp is the host's statement of it):
+// limbs = eight words that ARE the Montgomery representation of x (x 2^256 mod q, as Fq::rand takes them from the stream), greatest = the bool drawn after them.
+// Returns a lasso_cand_status; on LASSO_CAND_OK aff = the affine point as lasso_affine holds it (x then y, canonical Montgomery limbs); all zero otherwise.  The cofactor
+// is 1: the x limbs leave as they came.
+// Bounds: fe_from_fq yields a product output (reduced); pt_y_from_x returns a reduced Y; fe_to_fq accepts reduced and loose values and returns canonical words.
+LHD uint32_t pt_from_candidate(const uint32_t* limbs, bool greatest, uint32_t* aff) {
+  for (int i = 0; i < 16; i++) aff[i] = 0;
+  if (fq_geq_p(limbs)) return LASSO_CAND_NONCANONICAL;
+  fq_t xm; for (int i = 0; i < 8; i++) xm.v[i] = limbs[i];
+  fe29 Y; bool sign;
+  if (!pt_y_from_x(fe_from_fq(xm), greatest, Y, sign)) return LASSO_CAND_NO_POINT;
+  const fq_t ym = fe_to_fq(Y);
+  for (int i = 0; i < 8; i++) { aff[i] = limbs[i]; aff[8 + i] = ym.v[i]; }
+  return LASSO_CAND_OK;
 }

@@ -10,6 +10,7 @@
 // fe_mul(a, b) requires a loose, b reduced: 9 products of <= 2^59.01 stay below 2^63.
 #pragma once
 #include "../../include/lasso_hip_wire.h"   // lasso_wire_status: what pt_decompress returns
+#include "../../include/lasso_hip_gens.h"   // lasso_cand_status: what pt_from_candidate returns
 #ifdef LASSO_BN254
 #include "bn254_fe29.cuh"   // the same interface over ark-bn254's Fq and G1
 #else
@@ -300,12 +301,34 @@ LHD fe29 fe_pow22523(const fe29& z) {
   return fe_mul(t, z);
 }
 LHD bool fe_is_zero(const fe29& a) { return fq_is_zero(fe_to_fq(a)); }   // a loose
-// ark-ec's deserialize_compressed with Validate::Yes for a twisted-Edwards point, the mirror of decompress_point in lasso_amd/host/verifier.hpp: in = 8 little-endian
-// words (canonical y, bit 255 = "x is the larger root").  Returns a lasso_wire_status; on LASSO_WIRE_OK aff = the affine point as lasso_affine holds it (x then y, 8 words
-// each, ark-ff's Montgomery limbs) and canon = serialize_compressed of the decoded point (differs from `in` only for x = 0 with the flag set); all zero otherwise.
+// x from y, shared by pt_decompress and pt_from_candidate (y reduced):
 //   x^2 = (1 - y^2) / (-1 - d y^2) = u / v with u = y^2 - 1, v = d y^2 + 1.  ONE power chain serves the inversion and the root (p = 5 mod 8):
 //   x = u v^3 (u v^7)^((p-5)/8) has v x^2 = +-u when u / v is a square; the minus case is mended by sqrt(-1).  Which of the two roots the chain lands on does not
 //   matter: the flag picks one by comparing the canonical integers x and p - x, exactly as `(neg == x_larger) ? x : nx` does.
+// False when u / v is no square (v = 0 included: x comes out 0 and v x^2 = 0 is neither u nor -u, since v = 0 forces y^2 = -1/d, where u = y^2 - 1 is not 0).  Otherwise
+// X = the root `larger` asks for (the larger or the smaller of x and p - x as canonical integers; x = 0 is both) and other = the root not taken, both canonical.
+// Bounds: u and v are weakened sums of reduced values; every fe_mul has a reduced second operand and a reduced first one.
+LHD bool pt_x_from_y(const fe29& y, bool larger, fq_t& X, fq_t& other) {
+  const fe29 y2 = fe_sqr(y);
+  const fe29 u = fe_weak(fe_sub(y2, fe_one())), v = fe_weak(fe_add(fe_mul(y2, fe_from_fq(fq_d())), fe_one()));
+  const fe29 v3 = fe_mul(fe_sqr(v), v), v7 = fe_mul(fe_sqr(v3), v);
+  fe29 x = fe_mul(fe_mul(u, v3), fe_pow22523(fe_mul(u, v7)));
+  const fe29 vxx = fe_mul(fe_sqr(x), v);
+  if (!fe_is_zero(fe_sub(vxx, u))) {
+    if (!fe_is_zero(fe_add(vxx, u))) return false;
+    x = fe_mul(x, fe_from_fq(fq_from_limbs(0x4a0ea0b0u, 0xc4ee1b27u, 0xad2fe478u, 0x2f431806u, 0x3dfbd7a7u, 0x2b4d0099u, 0x4fc1df0bu, 0x2b832480u)));   // sqrt(-1)
+  }
+  const fq_t xc = fq_canonical(fe_to_fq(x)), nxc = fq_canonical(fq_neg(xc));
+  bool x_larger = false;   // nx < x as canonical integers
+  for (int i = 7; i >= 0; i--) if (xc.v[i] != nxc.v[i]) { x_larger = nxc.v[i] < xc.v[i]; break; }
+  const bool take_x = larger == x_larger;
+  for (int i = 0; i < 8; i++) { X.v[i] = take_x ? xc.v[i] : nxc.v[i]; other.v[i] = take_x ? nxc.v[i] : xc.v[i]; }
+  return true;
+}
+// ark-ec's deserialize_compressed with Validate::Yes for a twisted-Edwards point, the mirror of decompress_point in lasso_amd/host/verifier.hpp: in = 8 little-endian
+// words (canonical y, bit 255 = "x is the larger root").  Returns a lasso_wire_status; on LASSO_WIRE_OK aff = the affine point as lasso_affine holds it (x then y, 8 words
+// each, ark-ff's Montgomery limbs) and canon = serialize_compressed of the decoded point (differs from `in` only for x = 0 with the flag set); all zero otherwise.
+//   x from y and the flag: pt_x_from_y above.
 //   Subgroup: [l]P == O by double-and-add over the fixed bits of l = 2^252 + 27742317777372353535851937790883648493 (252 doublings, 65 additions).
 LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
   for (int i = 0; i < 16; i++) aff[i] = 0;
@@ -316,20 +339,9 @@ LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
   { uint64_t c = 19; uint32_t top = 0;   // y >= p  <=>  y + 19 >= 2^255
     for (int i = 0; i < 8; i++) { c += yw.v[i]; top = (uint32_t)c; c >>= 32; }
     if (top >> 31) return LASSO_WIRE_NONCANONICAL; }
-  const fe29 y = fe_from_fq(yw), y2 = fe_sqr(y);
-  const fe29 u = fe_weak(fe_sub(y2, fe_one())), v = fe_weak(fe_add(fe_mul(y2, fe_from_fq(fq_d())), fe_one()));
-  const fe29 v3 = fe_mul(fe_sqr(v), v), v7 = fe_mul(fe_sqr(v3), v);
-  fe29 x = fe_mul(fe_mul(u, v3), fe_pow22523(fe_mul(u, v7)));
-  const fe29 vxx = fe_mul(fe_sqr(x), v);
-  if (!fe_is_zero(fe_sub(vxx, u))) {
-    if (!fe_is_zero(fe_add(vxx, u))) return LASSO_WIRE_NOT_ON_CURVE;
-    x = fe_mul(x, fe_from_fq(fq_from_limbs(0x4a0ea0b0u, 0xc4ee1b27u, 0xad2fe478u, 0x2f431806u, 0x3dfbd7a7u, 0x2b4d0099u, 0x4fc1df0bu, 0x2b832480u)));   // sqrt(-1)
-  }
-  const fq_t xc = fq_canonical(fe_to_fq(x)), nxc = fq_canonical(fq_neg(xc));
-  bool x_larger = false;   // nx < x as canonical integers
-  for (int i = 7; i >= 0; i--) if (xc.v[i] != nxc.v[i]) { x_larger = nxc.v[i] < xc.v[i]; break; }
-  const bool take_x = neg == x_larger;
-  fq_t X, other; for (int i = 0; i < 8; i++) { X.v[i] = take_x ? xc.v[i] : nxc.v[i]; other.v[i] = take_x ? nxc.v[i] : xc.v[i]; }
+  const fe29 y = fe_from_fq(yw);
+  fq_t X, other;
+  if (!pt_x_from_y(y, neg, X, other)) return LASSO_WIRE_NOT_ON_CURVE;
   // [l]P: the top bit (252) is P itself and bit 251 is clear, so the sum starts at 2P — every coordinate a product output, no constant limbs carried into the loop
   pt29 P; P.X = fe_from_fq(X); P.Y = y; P.T = fe_mul(P.X, y); P.Z = fe_one();
   const fe29 d2 = fe_d2();
@@ -344,6 +356,32 @@ LHD uint32_t pt_decompress(const uint32_t* in, uint32_t* aff, uint32_t* canon) {
   for (int i = 0; i < 8; i++) { aff[i] = xm.v[i]; aff[8 + i] = ym.v[i]; canon[i] = yw.v[i]; }
   if (sign) canon[7] |= 0x80000000u;
   return LASSO_WIRE_OK;
+}
+
+// ------------------------------------------------------------------ generators from stream candidates (include/lasso_hip_gens.h)
+// The arithmetic half of ark-ec's `Projective::rand` for a twisted Edwards curve (point_from_candidate in lasso_amd/host/prover.hpp is the host's statement of it):
+// limbs = eight words that ARE the Montgomery representation of y (y 2^256 = 38 y mod p, as Fq::rand takes them from the stream), greatest = the bool drawn after them.
+// Returns a lasso_cand_status; on LASSO_CAND_OK aff = the affine point as lasso_affine holds it (x then y, canonical Montgomery limbs, as fq_to_mont yields); all zero
+// otherwise.  x^2 = (1 - y^2) / (-1 - d y^2) by pt_x_from_y (one chain; a zero denominator and a non-square both come out as "no point"), the root picked by
+// `greatest`, three doublings for the cofactor, one inversion (fe_inv_chain) to normalise.  A small-order start (y = +-1, y = 0, ...) doubles to the identity and leaves
+// as ark's affine identity (0, 1): Z is never 0 on this complete curve, so nothing is special-cased.
+// Bounds: fe_from_fq yields limbs in [0, 2^29) (reduced); y, T and every coordinate after pt_dbl are fe_mul outputs (reduced); fe_mul_small takes a reduced value and
+// returns a reduced one; fe_to_fq accepts loose limbs and fq_canonical any lazy fq_t.
+LHD uint32_t pt_from_candidate(const uint32_t* limbs, bool greatest, uint32_t* aff) {
+  for (int i = 0; i < 16; i++) aff[i] = 0;
+  fq_t ym; for (int i = 0; i < 8; i++) ym.v[i] = limbs[i];
+  { uint64_t c = 19; uint32_t top = 0;   // limbs >= p  <=>  limbs + 19 >= 2^255: bit 255 of the sum, or a carry out of it
+    for (int i = 0; i < 8; i++) { c += ym.v[i]; top = (uint32_t)c; c >>= 32; }
+    if ((top >> 31) || c) return LASSO_CAND_NONCANONICAL; }
+  const fe29 y = fe_mul(fe_from_fq(ym), fe_from_fq(fq_inv38()));   // out of the Montgomery form: y = limbs / 38
+  fq_t X, other;
+  if (!pt_x_from_y(y, greatest, X, other)) return LASSO_CAND_NO_POINT;
+  pt29 P; P.X = fe_from_fq(X); P.Y = y; P.T = fe_mul(P.X, y); P.Z = fe_one();
+  P = pt_dbl(pt_dbl(pt_dbl(P)));
+  const fe29 zi = fe_inv_chain(P.Z);
+  const fq_t xm = fq_canonical(fe_to_fq(fe_mul_small(fe_mul(P.X, zi), 38))), yo = fq_canonical(fe_to_fq(fe_mul_small(fe_mul(P.Y, zi), 38)));   // into the Montgomery form: times 38
+  for (int i = 0; i < 8; i++) { aff[i] = xm.v[i]; aff[8 + i] = yo.v[i]; }
+  return LASSO_CAND_OK;
 }
 
 // helpers the kernels share with the BN254 build (bn254_fe29.cuh)

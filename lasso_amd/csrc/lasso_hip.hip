@@ -21,6 +21,8 @@
 #include "../../include/lasso_hip_msm.h"
 #include "msm_points_kernels.cuh"
 #include "../../include/lasso_hip_operands.h"
+#include "../../include/lasso_hip_gens.h"
+#include "gens_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1497,6 +1499,28 @@ int32_t lasso_points_decompress(lasso_ctx* c, const uint8_t* wire32, size_t n, l
   if (out) memcpy(out, host.data(), 64 * n);
   if (canon32) memcpy(canon32, host.data() + 64 * n, 32 * n);
   memcpy(status, host.data() + 96 * n, n);
+  return 0;
+}
+// include/lasso_hip_gens.h: n stream candidates in, per candidate a status and the affine point out.  Device layout in the context's scratch:
+// [limbs 32 n][affine 64 n][status n][greatest n] — the uint4 regions start on 16-byte boundaries; the download is the contiguous [affine][status].
+int32_t lasso_points_from_candidates(lasso_ctx* c, const uint64_t* limbs, const uint8_t* greatest, size_t n, lasso_affine* out, uint8_t* status) {
+  REQUIRE(c, status && ((limbs && greatest) || n == 0) && n < ((size_t)1 << 31));
+  if (!n) return 0;
+  int32_t rc = ensure_scratch(c, 98 * n);
+  if (rc) return rc == LASSO_ERR_UNSUPPORTED ? fail(c, rc, "lasso_points_from_candidates: the scratch buffer cannot grow while a resident kernel is active") : rc;
+  uint8_t* base = (uint8_t*)c->d_scratch;
+  HIPCHK(c, hipMemcpyAsync(base, limbs, 32 * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(base + 97 * n, greatest, n, hipMemcpyHostToDevice, c->stream));
+  {
+    ProfScope ps(c, LASSO_K_MISC, 98.0 * n);
+    hipLaunchKernelGGL(k_points_from_candidates, dim3((unsigned)((n + GENS_THREADS - 1) / GENS_THREADS)), dim3(GENS_THREADS), 0, c->stream, (const uint4*)base, (const uint8_t*)(base + 97 * n), n, (uint4*)(base + 32 * n), base + 96 * n);
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<uint8_t> host(65 * n);
+  HIPCHK(c, hipMemcpyAsync(host.data(), base + 32 * n, 65 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (out) memcpy(out, host.data(), 64 * n);
+  memcpy(status, host.data() + 64 * n, n);
   return 0;
 }
 int32_t lasso_bases_create(lasso_ctx* c, const lasso_affine* points, size_t n, lasso_bases** out) { return lasso_bases_create_opt(c, points, n, 1, out); }

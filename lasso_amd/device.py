@@ -305,6 +305,25 @@ class Device:
         self._chk(self.lib.lasso_points_decompress(self.ctx, _vp(w), n, _vp(aff), _vp(canon), _vp(status)))
         return aff, canon, status
 
+    def points_from_candidates(self, limbs, greatest):
+        """candidates of a label's generator stream turned into points on the device (include/lasso_hip_gens.h lasso_points_from_candidates): `limbs` = (n, 4) uint64, the
+        Montgomery representation of the coordinate as the stream yields it; `greatest` = (n,) root choices.  Returns (affine (n, 8) uint64 as bases_create takes it,
+        status (n,) uint8 — _abi.CAND_STATUS names the values); a candidate without a point leaves a zero row.  A library without the entry is an error, not a fall-back."""
+        if not hasattr(self, "_gens"):
+            try:
+                _abi.declare_gens(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_points_from_candidates (include/lasso_hip_gens.h)")
+            self._gens = True
+        limbs = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)
+        g = np.ascontiguousarray(np.asarray(greatest).astype(bool), dtype=np.uint8).reshape(-1)
+        n = limbs.shape[0]
+        if g.shape[0] != n:
+            raise LassoError("points_from_candidates: as many root choices as candidates are needed")
+        aff = np.zeros((n, 8), dtype=np.uint64); status = np.zeros(n, dtype=np.uint8)
+        self._chk(self.lib.lasso_points_from_candidates(self.ctx, _vp(limbs), _vp(g), n, _vp(aff), _vp(status)))
+        return aff, status
+
     def bases_destroy(self, b):
         self.lib.lasso_bases_destroy(self.ctx, C.c_void_p(b))
 

@@ -24,10 +24,12 @@
 #include "sumcheck_phase.hpp"
 #include "hashes.hpp"
 #include "../../include/lasso_prover.h"
+#include "../../include/lasso_hip_gens.h"   // lasso_cand_status and the device half of the label-derived generators
 #include "../csrc/operand_layout.cuh"   // lasso_operand_layout as code: the same text the device kernel compiles
 #include "../../include/lasso_custom_check.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -305,6 +307,8 @@ class RandomTape {  // utils/random.rs:9-39
 };
 
 // ------------------------------------------------------------------ generators (poly/commitments.rs:22-44, dot_product.rs:139-150, dense_mlpoly.rs:34-45)
+// One attempt of `Projective::rand` as the stream yields it: the coordinate's limbs (ARE the Montgomery representation, below the modulus) and the root choice.
+struct Candidate { uint64_t limbs[4]; bool greatest; };
 #ifdef LASSO_BN254
 inline bool fq_sqrt(const fq_t& a, fq_t& out) {  // q = 3 (mod 4): a^((q+1)/4)
   const uint32_t e[8] = {0xb61f3f52u, 0x4f082305u, 0x5a1c72a3u, 0x65e05aa4u, 0xa0605617u, 0x6e14116du, 0xb84c680au, 0x0c19139cu};
@@ -314,20 +318,27 @@ inline bool fq_sqrt(const fq_t& a, fq_t& out) {  // q = 3 (mod 4): a^((q+1)/4)
 }
 inline bool canonical_less(const fq_t& a, const fq_t& b) { fq_t x = fq_to_canonical(a), y = fq_to_canonical(b); for (int i = 7; i >= 0; i--) if (x.v[i] != y.v[i]) return x.v[i] < y.v[i]; return false; }
 // ark-ec `Projective::rand` for a short Weierstrass curve: x <- Fq::rand (limbs taken as the Montgomery representation, top 2 bits masked,
-// rejection), bool, y from x (smaller or larger root); cofactor 1
-inline Pt point_rand(ChaChaRng& rng) {
+// rejection), bool, y from x (smaller or larger root); cofactor 1.  In two parts, because every draw precedes any curve arithmetic:
+// draw_candidate is the stream part, point_from_candidate the arithmetic (what pt_from_candidate, csrc/bn254_fe29.cuh, does per lane on the device).
+inline Candidate draw_candidate(ChaChaRng& rng) {
   for (;;) {
-    uint64_t l[4]; for (int i = 0; i < 4; i++) l[i] = rng.next_u64();
-    l[3] &= (~(uint64_t)0) >> 2;
-    fq_t x; memcpy(x.v, l, 32);
+    Candidate c; for (int i = 0; i < 4; i++) c.limbs[i] = rng.next_u64();
+    c.limbs[3] &= (~(uint64_t)0) >> 2;
+    fq_t x; memcpy(x.v, c.limbs, 32);
     if (fq_geq_p(x.v)) continue;
-    bool greatest = ((int32_t)rng.next_u32()) < 0;
-    fq_t y;
-    if (!fq_sqrt(fq_add(fq_mul(fq_sqr(x), x), fq_from_u64(3)), y)) continue;
-    fq_t ny = fq_neg(y), ys, yl;
-    if (canonical_less(ny, y)) { ys = ny; yl = y; } else { ys = y; yl = ny; }
-    return Pt::from_affine_plain(x, greatest ? yl : ys);
+    c.greatest = ((int32_t)rng.next_u32()) < 0;
+    return c;
   }
+}
+inline uint32_t point_from_candidate(const uint64_t* limbs, bool greatest, Pt& out) {
+  fq_t x; memcpy(x.v, limbs, 32);
+  if (fq_geq_p(x.v)) return LASSO_CAND_NONCANONICAL;
+  fq_t y;
+  if (!fq_sqrt(fq_add(fq_mul(fq_sqr(x), x), fq_from_u64(3)), y)) return LASSO_CAND_NO_POINT;
+  fq_t ny = fq_neg(y), ys, yl;
+  if (canonical_less(ny, y)) { ys = ny; yl = y; } else { ys = y; yl = ny; }
+  out = Pt::from_affine_plain(x, greatest ? yl : ys);
+  return LASSO_CAND_OK;
 }
 inline void compress_generator(uint8_t out[32]) { compress_affine(fq_from_u64(1), fq_from_u64(2), out); }   // G1 generator (1, 2)
 #else
@@ -341,28 +352,37 @@ inline bool fq_sqrt(const fq_t& a, fq_t& out) {  // p = 5 (mod 8)
   return false;
 }
 inline bool canonical_less(const fq_t& a, const fq_t& b) { fq_t x = fq_canonical(a), y = fq_canonical(b); for (int i = 7; i >= 0; i--) if (x.v[i] != y.v[i]) return x.v[i] < y.v[i]; return false; }
-// ark-ec `Projective::rand` for a twisted Edwards curve: y <- Fq::rand, bool, x from y (smaller or larger root), times the cofactor
-inline Pt point_rand(ChaChaRng& rng) {
+// ark-ec `Projective::rand` for a twisted Edwards curve: y <- Fq::rand, bool, x from y (smaller or larger root), times the cofactor.  In two parts, because every
+// draw precedes any curve arithmetic: draw_candidate is the stream part, point_from_candidate the arithmetic (what pt_from_candidate, csrc/fe29.cuh, does per lane
+// on the device).
+inline bool fq_words_below_p(const uint32_t* w) {   // limbs (Montgomery representation) must be < p
+  const uint32_t P[8] = {0xffffffedu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x7fffffffu};
+  for (int i = 7; i >= 0; i--) if (w[i] != P[i]) return w[i] < P[i];
+  return false;
+}
+inline Candidate draw_candidate(ChaChaRng& rng) {
   for (;;) {
-    uint64_t l[4]; for (int i = 0; i < 4; i++) l[i] = rng.next_u64();
-    l[3] &= (~(uint64_t)0) >> 1;
-    fq_t ym; memcpy(ym.v, l, 32);
-    {  // rejection: limbs (Montgomery representation) must be < p
-      const uint32_t P[8] = {0xffffffedu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu, 0x7fffffffu};
-      bool lt = false; for (int i = 7; i >= 0; i--) if (ym.v[i] != P[i]) { lt = ym.v[i] < P[i]; break; }
-      if (!lt) continue;
-    }
-    bool greatest = ((int32_t)rng.next_u32()) < 0;
-    fq_t y = fq_from_mont(ym), y2 = fq_sqr(y);
-    fq_t den = fq_sub(fq_neg(fq_one()), fq_mul(fq_d(), y2));   // a - d*y^2, a = -1
-    if (fq_is_zero(den)) continue;
-    fq_t x2 = fq_mul(fq_sub(fq_one(), y2), fq_inv(den)), x;
-    if (!fq_sqrt(x2, x)) continue;
-    fq_t nx = fq_neg(x), xs, xl;
-    if (canonical_less(nx, x)) { xs = nx; xl = x; } else { xs = x; xl = nx; }
-    Pt p = Pt::from_affine_plain(greatest ? xl : xs, y);
-    return p.dbl().dbl().dbl();
+    Candidate c; for (int i = 0; i < 4; i++) c.limbs[i] = rng.next_u64();
+    c.limbs[3] &= (~(uint64_t)0) >> 1;
+    fq_t ym; memcpy(ym.v, c.limbs, 32);
+    if (!fq_words_below_p(ym.v)) continue;   // rejection
+    c.greatest = ((int32_t)rng.next_u32()) < 0;
+    return c;
   }
+}
+inline uint32_t point_from_candidate(const uint64_t* limbs, bool greatest, Pt& out) {
+  fq_t ym; memcpy(ym.v, limbs, 32);
+  if (!fq_words_below_p(ym.v)) return LASSO_CAND_NONCANONICAL;
+  fq_t y = fq_from_mont(ym), y2 = fq_sqr(y);
+  fq_t den = fq_sub(fq_neg(fq_one()), fq_mul(fq_d(), y2));   // a - d*y^2, a = -1
+  if (fq_is_zero(den)) return LASSO_CAND_NO_POINT;
+  fq_t x2 = fq_mul(fq_sub(fq_one(), y2), fq_inv(den)), x;
+  if (!fq_sqrt(x2, x)) return LASSO_CAND_NO_POINT;
+  fq_t nx = fq_neg(x), xs, xl;
+  if (canonical_less(nx, x)) { xs = nx; xl = x; } else { xs = x; xl = nx; }
+  Pt p = Pt::from_affine_plain(greatest ? xl : xs, y);
+  out = p.dbl().dbl().dbl();
+  return LASSO_CAND_OK;
 }
 inline void compress_generator(uint8_t out[32]) {
   fq_t gx = fq_from_limbs(0x8f25d51au, 0xc9562d60u, 0x9525a7b2u, 0x692cc760u, 0xfdd6dc5cu, 0xc0a4e231u, 0xcd6e53feu, 0x216936d3u);
@@ -370,15 +390,61 @@ inline void compress_generator(uint8_t out[32]) {
   compress_affine(gx, gy, out);
 }
 #endif  // LASSO_BN254
-// The generator stream for one label: MultiCommitGens::new(n, label) = first n points as G, point n as h.
+// the host path of a generator: attempts from the stream until one yields a point
+inline Pt point_rand(ChaChaRng& rng) {
+  for (;;) { const Candidate c = draw_candidate(rng); Pt p; if (point_from_candidate(c.limbs, c.greatest, p) == LASSO_CAND_OK) return p; }
+}
+// points -> affine Montgomery limbs for the ABI (CurveGroup::normalize_batch, commitments.rs:87), one batch inversion
+inline void normalize_points(const Pt* pts, size_t n, lasso_affine* aff) {
+  std::vector<fq_t> pre(n); fq_t acc = fq_one();
+  for (size_t i = 0; i < n; i++) { pre[i] = acc; acc = fq_mul(acc, pts[i].p.Z); }
+  fq_t inv = fq_inv(acc);
+  for (size_t i = n; i-- > 0;) {
+    fq_t zi = fq_mul(inv, pre[i]); inv = fq_mul(inv, pts[i].p.Z);
+    fq_t x = fq_to_mont(fq_mul(pts[i].p.X, zi)), y = fq_to_mont(fq_mul(pts[i].p.Y, zi));
+    memcpy(aff[i].x, x.v, 32); memcpy(aff[i].y, y.v, 32);
+  }
+}
+// The device's half of a label-derived set (include/lasso_hip_gens.h lasso_points_from_candidates) as the owning host hands it over; fn == null: the host route.
+struct GensDevice {
+  int32_t (*fn)(lasso_ctx*, const uint64_t*, const uint8_t*, size_t, lasso_affine*, uint8_t*) = nullptr;
+  size_t min_points = 1;        // sets smaller than this stay on the host (LASSO_GENS_DEVICE_MIN)
+  size_t batch = 0;             // most candidates per device call, 0 = no cap (LASSO_GENS_DEVICE_BATCH)
+  uint64_t* counter = nullptr;  // candidates handed to the device (lasso_host_gens_stats)
+};
+// The generator stream for one label: MultiCommitGens::new(n, label) = first n points as G, point n as h.  The points are kept normalised (affine), once for all the
+// sets that take prefixes of the stream.
 struct GenStream {
-  std::vector<Pt> pts;
-  GenStream(const char* label, size_t count) {
+  std::vector<lasso_affine> aff;
+  GenStream(const Dev& d, const char* label, size_t count, const GensDevice& gd = GensDevice()) : aff(count) {
     Shake256 sh; sh.update(label, strlen(label));
     uint8_t buf[32]; compress_generator(buf); sh.update(buf, 32);
     uint8_t seed[32]; sh.read(seed, 32);
     ChaChaRng rng(seed, 20);
-    for (size_t i = 0; i < count; i++) pts.push_back(point_rand(rng));
+    if (!gd.fn || count < gd.min_points) {
+      std::vector<Pt> pts; pts.reserve(count);
+      for (size_t i = 0; i < count; i++) pts.push_back(point_rand(rng));
+      normalize_points(pts.data(), count, aff.data());
+      return;
+    }
+    // Device route: the stream is drawn on the host (every draw precedes any arithmetic, so the candidate sequence does not depend on which attempts succeed), the
+    // arithmetic of a whole batch is one device call, and the successes are taken in stream order — the points are the host route's, however the stream is cut.
+    // An attempt succeeds with probability 1/2 (half of the field's elements are squares), so of B candidates B/2 +- sqrt(B)/2 (one standard deviation) succeed.  To
+    // find the `need` points still missing a batch holds  B = 2 need + 6 sqrt(2 need) + 64  candidates: the expected surplus 3 sqrt(2 need) + 32 is six standard
+    // deviations, a second call happens about once in 10^9 sets (the + 64 covers the small sets, where the normal estimate is poor: 64 attempts all failing is 2^-64).
+    // The surplus is cheap: 6 % more lanes at the headline's 8194 points, in a launch that does not fill the device.
+    std::vector<uint64_t> limbs; std::vector<uint8_t> greatest, status; std::vector<lasso_affine> out;
+    size_t have = 0;
+    while (have < count) {
+      const size_t need = count - have;
+      size_t B = 2 * need + 6 * (size_t)std::ceil(std::sqrt(2.0 * (double)need)) + 64;
+      if (gd.batch && B > gd.batch) B = gd.batch;
+      limbs.resize(4 * B); greatest.resize(B); status.resize(B); out.resize(B);
+      for (size_t i = 0; i < B; i++) { const Candidate c = draw_candidate(rng); memcpy(&limbs[4 * i], c.limbs, 32); greatest[i] = c.greatest ? 1 : 0; }
+      d.chk(gd.fn(d.ctx, limbs.data(), greatest.data(), B, out.data(), status.data()), "lasso_points_from_candidates");
+      if (gd.counter) *gd.counter += B;
+      for (size_t i = 0; i < B && have < count; i++) if (status[i] == LASSO_CAND_OK) aff[have++] = out[i];
+    }
   }
 };
 // PolyCommitmentGens for one polynomial size: gens_n = {G[0..n), h}, gens_1 = {G[n], h} with h = stream[n+1]  (DotProductProofGens::new(n) =
@@ -388,20 +454,11 @@ struct PolyCommitmentGens {
   lasso_bases* bases_slab = nullptr;   // slab mode: the generators G_{j*P + rank}, j < n/P (this rank's columns of every Hyrax row), then Q, h
   bool slab_open = false;              // slab mode: every rank can run its share of the opening's MSMs (agreed at construction)
   PolyCommitmentGens() {}
-  // From the generator stream of a label (PolyCommitmentGens::new, dense_mlpoly.rs:38-45): the first n + 2 points, normalised with one batch inversion
+  // From the generator stream of a label (PolyCommitmentGens::new, dense_mlpoly.rs:38-45): the first n + 2 points (the stream holds them normalised)
   PolyCommitmentGens(const Dev& d, const GenStream& gs, size_t num_vars) {
     const size_t nn = (size_t)1 << (num_vars - num_vars / 2);   // right = ell - ell/2 (eq_poly.rs:40-42)
-    LASSO_REQUIRE(gs.pts.size() >= nn + 2);
-    // affine Montgomery limbs for the ABI, one batch inversion
-    std::vector<fq_t> pre(nn + 2); fq_t acc = fq_one();
-    for (size_t i = 0; i < nn + 2; i++) { pre[i] = acc; acc = fq_mul(acc, gs.pts[i].p.Z); }
-    fq_t inv = fq_inv(acc); std::vector<lasso_affine> aff(nn + 2);
-    for (size_t i = nn + 2; i-- > 0;) {
-      fq_t zi = fq_mul(inv, pre[i]); inv = fq_mul(inv, gs.pts[i].p.Z);
-      fq_t x = fq_to_mont(fq_mul(gs.pts[i].p.X, zi)), y = fq_to_mont(fq_mul(gs.pts[i].p.Y, zi));
-      memcpy(aff[i].x, x.v, 32); memcpy(aff[i].y, y.v, 32);
-    }
-    init(d, std::move(aff), nn);
+    LASSO_REQUIRE(gs.aff.size() >= nn + 2);
+    init(d, std::vector<lasso_affine>(gs.aff.begin(), gs.aff.begin() + (nn + 2)), nn);
   }
   // From the CALLER's points — what SparsePolynomialEvaluationProof::prove is handed (surge.rs:119-125 `gens: &SparsePolyCommitmentGens<G>`): the n + 2 points
   // [gens.gens_n.G[0..n), gens.gens_1.G[0], gens.gens_n.h] of one PolyCommitmentGens (dense_mlpoly.rs:34-45, dot_product.rs:139-150, commitments.rs:15-19), affine, ark-ff's
@@ -445,10 +502,10 @@ struct SparsePolyCommitmentGens {  // surge.rs:25-59
     nv_l = ceil_log2(next_pow2(2 * c * s)); nv_m = ceil_log2(next_pow2(c)) + log_m; nv_d = ceil_log2(next_pow2(num_memories * s));
   }
   // SparsePolyCommitmentGens::new(label, c, s, num_memories, log_m) (surge.rs:32-58): a convenience for callers without generators of their own (C, Python, the bench)
-  SparsePolyCommitmentGens(const Dev& d, const char* label, size_t c, size_t s, size_t num_memories, size_t log_m) {
+  SparsePolyCommitmentGens(const Dev& d, const char* label, size_t c, size_t s, size_t num_memories, size_t log_m, const GensDevice& gd = GensDevice()) {
     size_t nv_l, nv_m, nv_d; num_vars(c, s, num_memories, log_m, nv_l, nv_m, nv_d);
     size_t mx = std::max(nv_l, std::max(nv_m, nv_d));
-    GenStream gs(label, ((size_t)1 << (mx - mx / 2)) + 2);   // the three sets share one label => one stream, three prefixes
+    GenStream gs(d, label, ((size_t)1 << (mx - mx / 2)) + 2, gd);   // the three sets share one label => one stream, three prefixes
     gens_combined_l_variate = PolyCommitmentGens(d, gs, nv_l);
     gens_combined_log_m_variate = PolyCommitmentGens(d, gs, nv_m);
     gens_derefs = PolyCommitmentGens(d, gs, nv_d);

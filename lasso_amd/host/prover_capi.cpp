@@ -7,6 +7,7 @@
 #include "../../include/lasso_hip_wire.h"
 #include "../../include/lasso_hip_msm.h"
 #include "../../include/lasso_hip_operands.h"
+#include "../../include/lasso_hip_gens.h"
 
 using namespace lasso;
 
@@ -28,6 +29,11 @@ extern "C" int32_t lasso_msm_points(lasso_ctx*, const lasso_affine*, const lasso
 extern "C" int32_t lasso_densify_dim_operands(lasso_ctx*, const uint64_t*, const uint64_t*, size_t, const lasso_operand_layout*, size_t, size_t, size_t, uint32_t, uint32_t, uint32_t, uint32_t*, lasso_fr*,
                                               lasso_fr*, lasso_fr*) __attribute__((weak));
 
+// The arithmetic of label-derived generators (include/lasso_hip_gens.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
+// lasso_host_gens_new then builds every point on the host, and lasso_host_points_from_candidates(where = 1) says so.  LASSO_GENS_DEVICE=0 keeps the host route where the
+// entry point exists; LASSO_GENS_DEVICE_MIN is the smallest set that goes to the device, LASSO_GENS_DEVICE_BATCH caps the candidates per call (switches.hpp).
+extern "C" int32_t lasso_points_from_candidates(lasso_ctx*, const uint64_t*, const uint8_t*, size_t, lasso_affine*, uint8_t*) __attribute__((weak));
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -37,6 +43,8 @@ struct lasso_host {
   uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
   uint64_t msm_points_calls = 0;     // Verifier::msm_points calls of this host that took lasso_msm_points (lasso_host_msm_stats)
   uint64_t operand_dims = 0;         // dimensions densified by lasso_densify_dim_operands for this host (lasso_host_densify_stats)
+  uint64_t gens_device_candidates = 0;   // candidates handed to lasso_points_from_candidates for this host (lasso_host_gens_stats)
+  GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = &gens_device_candidates; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
   WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
   explicit lasso_host(int device) : dev(device) {}
@@ -45,7 +53,7 @@ struct lasso_host {
 };
 struct lasso_host_gens {
   lasso_host* owner; std::unique_ptr<SparsePolyCommitmentGens> g;
-  lasso_host_gens(lasso_host* h, const char* label, size_t c, size_t s, size_t nm, size_t log_m) : owner(h) { g.reset(new SparsePolyCommitmentGens(h->dev, label, c, s, nm, log_m)); h->retain(); }
+  lasso_host_gens(lasso_host* h, const char* label, size_t c, size_t s, size_t nm, size_t log_m) : owner(h) { g.reset(new SparsePolyCommitmentGens(h->dev, label, c, s, nm, log_m, h->gens_device())); h->retain(); }
   lasso_host_gens(lasso_host* h, size_t c, size_t s, size_t nm, size_t log_m, const lasso_affine* p1, size_t n1, const lasso_affine* p2, size_t n2, const lasso_affine* p3, size_t n3) : owner(h) {
     g.reset(new SparsePolyCommitmentGens(h->dev, c, s, nm, log_m, p1, n1, p2, n2, p3, n3)); h->retain();
   }
@@ -377,6 +385,31 @@ int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* ava
     if (points_calls) *points_calls = h->msm_points_calls;
     if (available) *available = lasso_msm_points ? 1 : 0;
     if (reset) h->msm_points_calls = 0;
+    return 0;)
+}
+int32_t lasso_host_points_from_candidates(lasso_host* h, const uint64_t* limbs, const uint8_t* greatest, size_t n, int32_t where, lasso_affine* out, uint8_t* status) {
+  GUARD(
+    if (!h || !status || ((!limbs || !greatest) && n) || (where != 0 && where != 1)) throw Error("lasso_host_points_from_candidates: null argument, or `where` is neither 0 (host) nor 1 (device)");
+    if (where == 1) {
+      if (!lasso_points_from_candidates) throw Error("lasso_host_points_from_candidates: the device entry (lasso_points_from_candidates, include/lasso_hip_gens.h) is not available in the device library this host was linked against");
+      h->dev.chk(lasso_points_from_candidates(h->dev.ctx, limbs, greatest, n, out, status), "lasso_points_from_candidates");
+      h->gens_device_candidates += n;
+      return 0;
+    }
+    for (size_t i = 0; i < n; i++) {
+      Pt p; lasso_affine a; memset(&a, 0, sizeof a);
+      status[i] = (uint8_t)point_from_candidate(limbs + 4 * i, greatest[i] != 0, p);
+      if (status[i] == LASSO_CAND_OK) normalize_points(&p, 1, &a);
+      if (out) out[i] = a;
+    }
+    return 0;)
+}
+int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_gens_stats: null host");
+    if (device_candidates) *device_candidates = h->gens_device_candidates;
+    if (available) *available = lasso_points_from_candidates ? 1 : 0;
+    if (reset) h->gens_device_candidates = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

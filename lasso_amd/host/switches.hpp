@@ -30,6 +30,9 @@ LASSO_SWITCH(bool, verify_device_points, unless0(getenv("LASSO_VERIFY_DEVICE_POI
 LASSO_SWITCH(size_t, wire_device_min, [] { const char* e = getenv("LASSO_WIRE_DEVICE_MIN"); const long long x = e ? atoll(e) : 376; return (size_t)(x < 1 ? 1 : x); }())   // 376 (the smallest batch measured with the device ahead), at least 1
 LASSO_SWITCH(bool, verify_msm_points, unless0(getenv("LASSO_VERIFY_MSM_POINTS")))         // on; the verifier's MSMs over commitment rows run table-free (lasso_msm_points) instead of lasso_bases_create + lasso_msm
 LASSO_SWITCH(bool, densify_operands, unless0(getenv("LASSO_DENSIFY_OPERANDS")))           // on; lasso_host_densify_operands forms the chunk indices on the device (off: expanded on the host, then the index path)
+LASSO_SWITCH(bool, gens_device, unless0(getenv("LASSO_GENS_DEVICE")))                     // on; label-derived generators: the candidates' arithmetic in one lasso_points_from_candidates launch (off: one by one on the host)
+LASSO_SWITCH(size_t, gens_device_min, [] { const char* e = getenv("LASSO_GENS_DEVICE_MIN"); const long long x = e ? atoll(e) : 8194; return (size_t)(x < 1 ? 1 : x); }())   // 8194 (the smallest set measured with the device ahead on both curves), at least 1; smaller sets stay on the host
+LASSO_SWITCH(size_t, gens_device_batch, [] { const char* e = getenv("LASSO_GENS_DEVICE_BATCH"); const long long x = e ? atoll(e) : 0; return (size_t)(x < 1 ? 0 : x); }())   // 0 = no cap; most candidates per device call (bounds the call's scratch: 98 bytes per candidate)
 // the two read per CALL, not per process (a test sets them between calls):
 inline bool slab_rccl() { return unless0(getenv("LASSO_SLAB_RCCL")); }             // on; slab mode's bulk exchange over RCCL (lasso_host_set_comm_shm)
 inline bool debug_cubic_host() { return if1(getenv("LASSO_DEBUG_CUBIC_HOST")); }   // off; lasso_host_debug_prove_cubic_batched runs the HOST rounds

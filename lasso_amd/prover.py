@@ -74,6 +74,8 @@ def declare_prover(lib):
     lib.lasso_host_wire_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
     lib.lasso_host_msm_points.argtypes = [vp, vp, vp, sz, vp]
     lib.lasso_host_msm_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
+    lib.lasso_host_points_from_candidates.argtypes = [vp, vp, vp, sz, i32, vp, vp]
+    lib.lasso_host_gens_stats.argtypes = [vp, u64p, C.POINTER(i32), i32]
     lib.lasso_host_gen_indices.argtypes = [sz, sz, vp]
     lib.lasso_host_gen_random_point.argtypes = [sz, vp]
     return lib
@@ -281,6 +283,26 @@ class HostProver:
         k, a = C.c_uint64(), C.c_int32()
         self._chk(self.lib.lasso_host_msm_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
         return {"points_calls": k.value, "available": bool(a.value)}
+
+    def points_from_candidates(self, limbs, greatest, where=0):
+        """candidates of a label's generator stream -> (affine (n, 8) uint64, status (n,) uint8), on the host (where=0: one after the other) or on the device (where=1:
+        one launch; LassoError when the device library has no such entry) — lasso_host_points_from_candidates.  `limbs` = (n, 4) uint64, `greatest` = (n,) root choices."""
+        limbs = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)
+        g = np.ascontiguousarray(np.asarray(greatest).astype(bool), dtype=np.uint8).reshape(-1)
+        n = limbs.shape[0]
+        if g.shape[0] != n:
+            raise LassoError("points_from_candidates: as many root choices as candidates are needed")
+        aff = np.zeros((n, 8), dtype=np.uint64); status = np.zeros(n, dtype=np.uint8)
+        vpt = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.lasso_host_points_from_candidates(self.h, vpt(limbs), vpt(g), n, where, vpt(aff), vpt(status)))
+        return aff, status
+
+    def gens_stats(self, reset=False):
+        """{"device_candidates": generator candidates this host handed to the device so far, "available": whether the device library has
+        lasso_points_from_candidates} (lasso_host_gens_stats)"""
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(self.lib.lasso_host_gens_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"device_candidates": k.value, "available": bool(a.value)}
 
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
