@@ -622,6 +622,7 @@ int32_t lasso_bind_top(lasso_ctx* c, lasso_fr* const* d_polys, uint32_t npolys, 
   HIPCHK(c, hipGetLastError()); return 0;
 }
 static unsigned round_nx(size_t items, unsigned ny) { return round_nx(items, ny, dsw::cubic_nx()); }   // x-extent of the round grids (launch_plan.cuh)
+static unsigned reduce_nx(size_t items, unsigned cap) { return reduce_nx(items, cap, dsw::reduce_nx()); }   // ... of the reduction launches outside them
 // the reference's loop with an explicit third polynomial (any C): kept as the literal counterpart of sumcheck.rs:49-93
 int32_t lasso_sumcheck_cubic_round(lasso_ctx* c, const lasso_fr* const* d_A, const lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_C, size_t n, lasso_fr* out) {
   REQUIRE(c, d_A && d_B && d_C && out && ncirc >= 1 && ncirc <= LASSO_MAX_PTRS && n >= 2 && (n & (n - 1)) == 0);
@@ -1094,7 +1095,7 @@ static int32_t combine_round_custom(lasso_ctx* c, const lasso_strategy_custom* s
   REQUIRE(c, d_polys && d_eq && out && n >= 2 && (n & (n - 1)) == 0);
   REQUIRE(c, degree == custom_strategy_degree(s) + 1);   // sumcheck_poly_degree() = g_poly_degree() + 1: subtables/mod.rs:60-62
   PtrTable P; for (uint32_t i = 0; i < s->num_memories; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const size_t half = n / 2; const unsigned nx = grid_for(half, 1024); const uint32_t K = degree + 1;
+  const size_t half = n / 2; const unsigned nx = reduce_nx(half, 1024); const uint32_t K = degree + 1;
   rc = ensure_scratch(c, (size_t)nx * K * sizeof(fr_t)); if (rc) return rc;
   rc = ensure_small(c, K); if (rc) return rc;
   {
@@ -1111,7 +1112,7 @@ static int32_t combine_claim_custom(lasso_ctx* c, const lasso_strategy_custom* s
   uint32_t Q = 1; int32_t rc = pack_custom_terms(c, s, Q); if (rc) return rc;
   REQUIRE(c, d_polys && d_eq && out && n >= 1);
   PtrTable P; for (uint32_t i = 0; i < s->num_memories; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const unsigned nx = grid_for(n, 1024);
+  const unsigned nx = reduce_nx(n, 1024);
   rc = ensure_scratch(c, (size_t)nx * sizeof(fr_t)); if (rc) return rc;
   {
     ProfScope ps(c, LASSO_K_COMBINE, 32.0 * n * (s->num_memories + 1.0));
@@ -1133,7 +1134,7 @@ static int32_t combine_round_impl(lasso_ctx* c, const lasso_strategy* s, const l
   const bool spark = s->kind == LASSO_SPARK_UNCONFIRMED;
   REQUIRE(c, degree == ((s->kind == LASSO_LT || spark) ? s->c + 1 : 2));   // sumcheck_poly_degree(): subtables/mod.rs:60-62
   PtrTable P; for (uint32_t i = 0; i < S.alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const size_t half = n / 2; const unsigned nx = grid_for(half, 1024); const uint32_t K = degree + 1;
+  const size_t half = n / 2; const unsigned nx = reduce_nx(half, 1024); const uint32_t K = degree + 1;
   const bool lt = s->kind == LASSO_LT;
   const size_t copy_elems = lt && !lt_scaled && S.c > 1 ? (size_t)(S.c - 1) * n : 0;
   rc = ensure_scratch(c, ((size_t)nx * K + copy_elems) * sizeof(fr_t)); if (rc) return rc;
@@ -1173,7 +1174,7 @@ int32_t lasso_sumcheck_combine_round_lt_u32(lasso_ctx* c, const lasso_strategy* 
   StrategyDev S; WeightTable W; int32_t rc = make_strategy(c, s, S, W); if (rc) return rc;
   REQUIRE(c, s->kind == LASSO_LT && d_u32 && d_eq && out && n >= 2 && (n & (n - 1)) == 0 && degree == s->c + 1 && s->c <= 16 && !c->proto.defer_next);   // C <= 16: |t| < 2^67 fits the three-limb form (header)
   PtrTableU32 P; for (uint32_t i = 0; i < S.alpha; i++) { REQUIRE(c, d_u32[i]); P.p[i] = d_u32[i]; }
-  const size_t half = n / 2; const unsigned nx = grid_for(half, 1024); const uint32_t K = degree + 1;
+  const size_t half = n / 2; const unsigned nx = reduce_nx(half, 1024); const uint32_t K = degree + 1;
   rc = ensure_scratch(c, (size_t)nx * K * sizeof(fr_t)); if (rc) return rc;
   rc = ensure_small(c, K); if (rc) return rc;
   {
@@ -1205,7 +1206,7 @@ int32_t lasso_combine_claim(lasso_ctx* c, const lasso_strategy* s, const lasso_f
   StrategyDev S; WeightTable W; int32_t rc = make_strategy(c, s, S, W); if (rc) return rc;
   REQUIRE(c, d_polys && d_eq && out && n >= 1);
   PtrTable P; for (uint32_t i = 0; i < S.alpha; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const unsigned nx = grid_for(n, 1024);
+  const unsigned nx = reduce_nx(n, 1024);
   rc = ensure_scratch(c, (size_t)nx * sizeof(fr_t)); if (rc) return rc;
   {
     ProfScope ps(c, LASSO_K_COMBINE, 32.0 * n * (S.alpha + 1.0));
@@ -1219,7 +1220,7 @@ int32_t lasso_combine_claim(lasso_ctx* c, const lasso_strategy* s, const lasso_f
 int32_t lasso_multi_dot(lasso_ctx* c, const lasso_fr* const* d_polys, uint32_t k, const lasso_fr* d_w, size_t n, lasso_fr* out) {
   REQUIRE(c, d_polys && d_w && out && k >= 1 && k <= LASSO_MAX_PTRS && n >= 1);
   PtrTable P; for (uint32_t i = 0; i < k; i++) { REQUIRE(c, d_polys[i]); P.p[i] = (const fr_t*)d_polys[i]; }
-  const unsigned nx = grid_for(n, 512);
+  const unsigned nx = reduce_nx(n, 512);
   int32_t rc = ensure_scratch(c, (size_t)nx * k * sizeof(fr_t)); if (rc) return rc;
   rc = ensure_small(c, k); if (rc) return rc;
   {
@@ -1351,10 +1352,7 @@ int32_t lasso_fingerprint_mem_slab(lasso_ctx* c, const lasso_fr* d_table, const 
 }
 int32_t lasso_matvec_left(lasso_ctx* c, const lasso_fr* d_Z, const lasso_fr* L, size_t l_size, size_t r_size, lasso_fr* out) {
   REQUIRE(c, d_Z && L && out && l_size >= 1 && r_size >= 1);
-  // enough row chunks to fill the chip: ~1024 workgroups
-  size_t col_blocks = (r_size + LASSO_BLOCK - 1) / LASSO_BLOCK;
-  size_t nchunks = (1024 + col_blocks - 1) / col_blocks; if (nchunks > l_size) nchunks = l_size; if (nchunks < 1) nchunks = 1;
-  size_t rows_per_chunk = (l_size + nchunks - 1) / nchunks; nchunks = (l_size + rows_per_chunk - 1) / rows_per_chunk;
+  const MatvecPlan mp = matvec_plan(l_size, r_size); const size_t col_blocks = mp.col_blocks, nchunks = mp.nchunks, rows_per_chunk = mp.rows_per_chunk;
   int32_t rc = ensure_scratch(c, (l_size + nchunks * r_size) * sizeof(fr_t)); if (rc) return rc;
   rc = ensure_big(c, r_size); if (rc) return rc;
   fr_t* dL = (fr_t*)c->d_scratch; fr_t* partials = dL + l_size;
@@ -1374,9 +1372,7 @@ int32_t lasso_matvec_left(lasso_ctx* c, const lasso_fr* d_Z, const lasso_fr* L, 
 // device-resident forms used by the opening: L already on the device, L*Z left on the device (no host round trip)
 int32_t lasso_matvec_left_dev(lasso_ctx* c, const lasso_fr* d_Z, const lasso_fr* d_L, size_t l_size, size_t r_size, lasso_fr* d_out) {
   REQUIRE(c, d_Z && d_L && d_out && l_size >= 1 && r_size >= 1);
-  size_t col_blocks = (r_size + LASSO_BLOCK - 1) / LASSO_BLOCK;
-  size_t nchunks = (1024 + col_blocks - 1) / col_blocks; if (nchunks > l_size) nchunks = l_size; if (nchunks < 1) nchunks = 1;
-  size_t rows_per_chunk = (l_size + nchunks - 1) / nchunks; nchunks = (l_size + rows_per_chunk - 1) / rows_per_chunk;
+  const MatvecPlan mp = matvec_plan(l_size, r_size); const size_t col_blocks = mp.col_blocks, nchunks = mp.nchunks, rows_per_chunk = mp.rows_per_chunk;
   int32_t rc = ensure_scratch(c, nchunks * r_size * sizeof(fr_t)); if (rc) return rc;
   fr_t* partials = (fr_t*)c->d_scratch;
   ProfScope ps(c, LASSO_K_MATVEC, 32.0 * l_size * r_size);
@@ -1825,7 +1821,7 @@ int32_t lasso_msm_dev_scaled(lasso_ctx* c, const lasso_bases* b, const lasso_fr*
 }
 int32_t lasso_inner_products_lr(lasso_ctx* c, const lasso_fr* d_a, const lasso_fr* d_b, size_t nk, lasso_fr* out) {
   REQUIRE(c, d_a && d_b && out && nk >= 2 && (nk & (nk - 1)) == 0);
-  const size_t half = nk / 2; const unsigned nx = grid_for(half, 256);
+  const size_t half = nk / 2; const unsigned nx = reduce_nx(half, 256);
   int32_t rc = ensure_scratch(c, (size_t)nx * 2 * sizeof(fr_t)); if (rc) return rc;
   {
     ProfScope ps(c, LASSO_K_DOT, 64.0 * nk);

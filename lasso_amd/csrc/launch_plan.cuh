@@ -36,6 +36,17 @@ static inline unsigned round_nx(size_t items, unsigned ny, long cubic_nx) {
   unsigned cap = 512 / (ny ? ny : 1); if (cap < 64) cap = 64;
   return grid_for(items, cubic_nx > 0 ? (unsigned)cubic_nx : cap);
 }
+// x-extent of a one-dimensional reduction launch outside the round grids (combine rounds and claims, multi_dot, inner_products_lr): the launch's own cap, or reduce_nx_sw > 0
+// (LASSO_REDUCE_NX) in its place.  Every one of these kernels strides by its grid, and its partials and second stage are sized from the same value.
+static inline unsigned reduce_nx(size_t items, unsigned cap, long reduce_nx_sw) { return grid_for(items, reduce_nx_sw > 0 ? (unsigned)reduce_nx_sw : cap); }
+// L * Z by row chunks (k_matvec_left, k_matvec_reduce): enough chunks of whole rows to fill the chip, ~1024 workgroups over the column blocks
+struct MatvecPlan { size_t col_blocks, nchunks, rows_per_chunk; };
+static inline MatvecPlan matvec_plan(size_t l_size, size_t r_size) {
+  MatvecPlan p; p.col_blocks = (r_size + LASSO_BLOCK - 1) / LASSO_BLOCK;
+  p.nchunks = (1024 + p.col_blocks - 1) / p.col_blocks; if (p.nchunks > l_size) p.nchunks = l_size; if (p.nchunks < 1) p.nchunks = 1;
+  p.rows_per_chunk = (l_size + p.nchunks - 1) / p.nchunks; p.nchunks = (l_size + p.rows_per_chunk - 1) / p.rows_per_chunk;
+  return p;
+}
 // workgroup = capacity of the two resident tails (k_cubic_tail, k_linear_tail): 256 threads / 74 KB of LDS up to 256 indices per circuit, 512 threads / 147 KB above
 static inline unsigned tail_threads(size_t q) { return q <= 256 ? 256u : 512u; }
 

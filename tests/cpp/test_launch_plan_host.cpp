@@ -210,6 +210,18 @@ static int test_cubic() {
   // the x-extent of the linear rounds (cubic_nx_cap / grid_for) and the resident tails' workgroup
   for (size_t items = 1; items <= ((size_t)1 << 22); items = items * 2 + (items & 1 ? 0 : 1)) for (unsigned ny : {0u, 1u, 2u, 8u, 9u, 32u, 136u}) for (long cnx : {-1L, 0L, 64L, 1000L})
     CHECK(round_nx(items, ny, cnx) == old_grid_for(items, old_cubic_nx_cap(ny, cnx)));
+  // the reduction launches outside the round grids: grid_for(items, 1024 / 512 / 256) as each launch site had it, LASSO_REDUCE_NX in the cap's place where it is above 0
+  for (size_t items = 1; items <= ((size_t)1 << 26); items = items * 2 + (items & 1 ? 0 : 1)) for (unsigned cap : {256u, 512u, 1024u}) for (long rnx : {-1L, 0L, 1L, 3L, 2000L})
+    CHECK(reduce_nx(items, cap, rnx) == old_grid_for(items, rnx > 0 ? (unsigned)rnx : cap));
+  // the row chunks of lasso_matvec_left / lasso_matvec_left_dev, as both had them
+  for (size_t l_size : {(size_t)1, (size_t)2, (size_t)3, (size_t)320, (size_t)512, (size_t)1000, (size_t)4096, (size_t)5000}) for (size_t r_size : {(size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)1024, (size_t)4096, (size_t)300000}) {
+    size_t col_blocks = (r_size + 256 - 1) / 256;
+    size_t nchunks = (1024 + col_blocks - 1) / col_blocks; if (nchunks > l_size) nchunks = l_size; if (nchunks < 1) nchunks = 1;
+    size_t rows_per_chunk = (l_size + nchunks - 1) / nchunks; nchunks = (l_size + rows_per_chunk - 1) / rows_per_chunk;
+    const MatvecPlan mp = matvec_plan(l_size, r_size);
+    CHECK(mp.col_blocks == col_blocks && mp.nchunks == nchunks && mp.rows_per_chunk == rows_per_chunk);
+    CHECK(mp.nchunks * mp.rows_per_chunk >= l_size && (mp.nchunks - 1) * mp.rows_per_chunk < l_size);
+  }
   for (size_t q : {(size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)512}) CHECK(tail_threads(q) == (q <= 256 ? 256u : 512u));
   CHECK(grid_for(0) == 1 && grid_for(257) == 2 && grid_for((size_t)1 << 40) == 2048 && grid_for(1 << 20, 4096) == 4096);
   return 0;

@@ -137,3 +137,8 @@ def test_gpu_bn254_msm_variants():
 def test_gpu_bn254_round_variants():
     """tests/test_gpu_round_variants.py on the BN254 build: every switched cubic-round kernel against the BN254 mock."""
     _rerun_on_bn254("test_gpu_round_variants.py")
+
+
+def test_gpu_bn254_pass_variants():
+    """tests/test_gpu_pass_variants.py on the BN254 build: every running sum of the sumcheck kernels through its fold, against the BN254 mock."""
+    _rerun_on_bn254("test_gpu_pass_variants.py")

@@ -16,7 +16,7 @@ r_tests_bn254() {  # tests_bn254 [k] [tag]: the entry-point cases on the BN254 l
   local k="${1:-}" tag="${2:-tests_bn254}"; mkdir -p gpurun_out/$tag
   LASSO_TEST_CURVE=bn254 timeout 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_bn254.py -m gpu -q -x ${k:+-k "$k"} > gpurun_out/$tag/pytest.log 2>&1; grep -E "passed|failed|error" gpurun_out/$tag/pytest.log | tail -2
   # ... and the modules that take the curve from LASSO_TEST_CURVE themselves (the MSM over caller points, the custom-strategy kernels, every switched MSM kernel), output as it comes
-  LASSO_TEST_CURVE=bn254 timeout 900 python -m pytest tests/test_gpu_msm_points.py tests/test_gpu_custom_strategy.py tests/test_gpu_msm_variants.py tests/test_gpu_round_variants.py -m gpu -q -x ${k:+-k "$k"} 2>&1
+  LASSO_TEST_CURVE=bn254 timeout 900 python -m pytest tests/test_gpu_msm_points.py tests/test_gpu_custom_strategy.py tests/test_gpu_msm_variants.py tests/test_gpu_round_variants.py tests/test_gpu_pass_variants.py -m gpu -q -x ${k:+-k "$k"} 2>&1
 }
 r_bench() {        # bench <tag> [bench.py args...]: one bench.py run, JSON line kept, headline printed
   local tag="$1"; shift; mkdir -p gpurun_out/$tag
