@@ -25,6 +25,12 @@
  *  - `d_` parameters are DEVICE pointers obtained from lasso_alloc (or any hipMalloc'd memory on the
  *    context's device, e.g. a torch tensor's data_ptr); all other pointers are HOST memory owned by the
  *    caller for the duration of the call only.
+ *  - WRITE EXTENTS.  A call writes caller device memory only where its comment says so, and exactly that many elements: a non-const `d_` parameter that is an output
+ *    receives the stated count and not one element more (a buffer of exactly that size suffices, at any address aligned for its element type: 16 bytes for lasso_fr /
+ *    lasso_affine / lasso_point arrays, 4 for uint32_t, 8 for uint64_t); a round that binds (lasso_bind_top, every *_fused form, lasso_sumcheck_cubic_eqw2_begin with r,
+ *    and the *_ahead forms of those) writes the LOWER n/2 elements of each bound array, n the length before the bind, and leaves the upper half as it was; the resident
+ *    tails (lasso_sumcheck_*_tail_begin*, lasso_sumcheck_cubic_tail_next) and every call whose result goes to host memory write nothing.  tests/writecontract.py states
+ *    this per function and tests/test_gpu_write_contract.py holds the library to it.
  *  - Every function returns 0 on success and a negative lasso_status otherwise; lasso_last_error()
  *    gives the message.  Nothing unwinds across the ABI.  The reference prover panics on contract
  *    violations (assert!); a host binding turns non-zero into panic!.
@@ -238,7 +244,10 @@ int32_t lasso_tail_handover_next(lasso_ctx* ctx, uint32_t m_stop);
  * WITHOUT a result on lasso_abort's poison tag or after 5 s without a post (then lasso_result_wait fails: nothing hangs).  Between begin_ahead and the post ONLY lasso_result_wait
  * is legal on the context: entry points that would synchronise the stream (lasso_free / upload / download / sync / trim, buffer growth) return LASSO_ERR_INVALID instead of blocking
  * behind the waiting kernel.  Streaming two-sum rounds only (n / 4 > 64); LASSO_ERR_UNSUPPORTED otherwise.  lasso_rounds_ahead_ok: 1 unless LASSO_ROUNDS_AHEAD=0.
- * lasso_sumcheck_cubic_tail_begin_ahead: the resident tail enqueued ahead of the challenge it binds first (n = 4q); the first lasso_sumcheck_cubic_tail_next posts it. */
+ * lasso_sumcheck_cubic_tail_begin_ahead: the resident tail enqueued ahead of the challenge it binds first (n = 4q); the first lasso_sumcheck_cubic_tail_next posts it.
+ * What an *_ahead form writes is what its plain form writes (lasso_sumcheck_cubic_eqw2_begin_ahead and lasso_sumcheck_linear_eqw_round_fused_ahead: the lower n/2 of each bound
+ * array; lasso_sumcheck_cubic_tail_begin_ahead: nothing; lasso_sumcheck_cubic_eqw2_begin_eq_ahead below: n/2 entries of d_E_out; lasso_sumcheck_cubic_tail_begin_eq_ahead:
+ * nothing; lasso_bullet_round_ahead: nk, nk and n/nk elements of the three *_out arrays), by the time its result has been collected. */
 int32_t lasso_rounds_ahead_ok(lasso_ctx* ctx);
 int32_t lasso_sumcheck_cubic_eqw2_begin_ahead(lasso_ctx* ctx, lasso_fr* const* d_A, lasso_fr* const* d_B, uint32_t ncirc, const lasso_fr* d_E, size_t n);
 int32_t lasso_challenge_post(lasso_ctx* ctx, const lasso_fr* r);
@@ -281,7 +290,9 @@ int32_t lasso_sumcheck_combine_round(lasso_ctx* ctx, const lasso_strategy* s, co
  * unscaled ones.  After the last bind the caller multiplies the head of polynomial 2m by 32^(C-1-m) to obtain LT_m(r); the EQ polynomials (odd indices) are never touched.
  * (lasso_sumcheck_combine_round on an LT strategy scales private copies itself: the literal call.) */
 /* d_src == NULL: in place.  Otherwise d_polys[i] <- (scaled) d_src[i] for ALL 2C polynomials (the ones the scaling leaves alone are copied): the sumcheck's clone of the lookup
- * polynomials (surge.rs:151) and the scaling in one pass over the data. */
+ * polynomials (surge.rs:151) and the scaling in one pass over the data.
+ * Written: in place, n elements of d_polys[2m] for m < C - 1 and nothing else (LT_{C-1} and every EQ_m are not touched, not even rewritten with the same bytes); out of place,
+ * n elements of every d_polys[i], i < 2C, and nothing of d_src. */
 int32_t lasso_lt_prescale(lasso_ctx* ctx, const lasso_strategy* s, const lasso_fr* const* d_src, lasso_fr* const* d_polys, size_t n);
 int32_t lasso_sumcheck_combine_round_lt_scaled(lasso_ctx* ctx, const lasso_strategy* s, const lasso_fr* const* d_polys, const lasso_fr* d_eq, size_t n, uint32_t degree, lasso_fr* out);
 /* The FIRST round of that sumcheck (before any bind) from the lookup polynomials' INTEGER values, E_k[i] = F::from(d_u32[k][i]) with EVERY ENTRY 0 OR 1 — the LT and EQ subtables
@@ -333,7 +344,7 @@ int32_t lasso_fingerprint_ops_gp(lasso_ctx* ctx, const lasso_fr* d_table, const 
                                  lasso_fr* d_tree_read, lasso_fr* d_tree_write);
 /* Capacity mode (one proof larger than the reference's "every layer a Vec<F>" layout allows, grand_product.rs:38-58): the same two trees WITHOUT their leaf layers —
  * d_upper_read / d_upper_write receive the layers of s/2, s/4, .., 2 elements back to back (s - 2 elements; what lasso_fingerprint_ops_gp leaves at d_tree + s); the
- * fingerprints exist only inside the launch.  Half the resident bytes of the read / write trees. */
+ * fingerprints exist only inside the launch.  Half the resident bytes of the read / write trees.  Exactly s - 2 elements of each are written: a buffer of s - 2 suffices. */
 int32_t lasso_fingerprint_ops_gp_upper(lasso_ctx* ctx, const lasso_fr* d_table, const uint32_t* d_dim, const lasso_fr* d_read, size_t s, const lasso_fr* gamma, const lasso_fr* tau,
                                        lasso_fr* d_upper_read, lasso_fr* d_upper_write);
 /* the same, the read timestamps given as 32-bit integers (identical bytes out) */
@@ -483,6 +494,7 @@ int32_t lasso_bullet_post(lasso_ctx* ctx, const lasso_fr* u, const lasso_fr* u_i
  *   lasso_bullet_post(ctx, u, u_inv)               release the chain
  *   lasso_result_wait(ctx, out, 6)                 out[0..4) = delta as a lasso_point, out[4] = d_a[0], out[5] = d_b[0]
  * d_a, d_b: the two-element state after the last round (folded in place); d_w: n / 2 weights, d_w_out: n; scale = d; tail = {0, r_delta} (the Q and h terms).
+ * Written: d_a[0] and d_b[0] (the second element of each is only read), the 2 * nw = n elements of d_w_out; nothing of d_w.
  * Same group element and field elements as lasso_bullet_fold + lasso_read_heads + lasso_msm_dev_scaled.  lasso_bullet_tail_ahead_ok: lasso_bullet_ahead_ok, tagged results on,
  * LASSO_BULLET_TAIL_AHEAD != 0.  LASSO_ERR_UNSUPPORTED when a buffer would have to grow (first proof of a context: the plain calls size them). */
 int32_t lasso_bullet_tail_ahead_ok(lasso_ctx* ctx, const lasso_bases* bases);

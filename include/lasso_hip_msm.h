@@ -17,7 +17,7 @@ extern "C" {
  * Scratch comes from the context (counted by lasso_mem_stats): 257 bytes per point (161 for the _dev form, which uploads nothing) plus 4.8 KB per 1024 points.
  * LASSO_ERR_UNSUPPORTED, with a message, when that buffer would have to grow while a resident kernel is active.  Synchronous. */
 int32_t lasso_msm_points(lasso_ctx* ctx, const lasso_affine* points, const lasso_fr* scalars, size_t n, lasso_point* out);
-/* the same with points and scalars resident on the device */
+/* the same with points and scalars resident on the device: both arrays are only read (the digits and sorted pairs live in the context's scratch), `out` is host memory */
 int32_t lasso_msm_points_dev(lasso_ctx* ctx, const lasso_affine* d_points, const lasso_fr* d_scalars, size_t n, lasso_point* out);
 
 #ifdef __cplusplus

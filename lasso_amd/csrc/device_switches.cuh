@@ -40,6 +40,8 @@ LASSO_DSWITCH(size_t, msm_rows8w_waves, [] { const char* e = getenv("LASSO_MSM_R
 LASSO_DSWITCH(bool, msm_full8, if1(getenv("LASSO_MSM_FULL8")))                 // off; full-width commitments over the signed byte-multiple table (k_msm_rows_full<8>) instead of the bucket kernel
 LASSO_DSWITCH(bool, bullet_ahead, unless0(getenv("LASSO_BULLET_AHEAD")))       // on; the openings' folding rounds may be enqueued ahead of their challenge
 LASSO_DSWITCH(bool, bullet_tail_ahead, unless0(getenv("LASSO_BULLET_TAIL_AHEAD")))   // on; the opening's last fold, heads and delta MSM as one chain enqueued ahead of the last challenge
+// ---- the context's own buffers
+LASSO_DSWITCH(bool, scratch_guard, if1(getenv("LASSO_SCRATCH_GUARD")))         // off; tests: a guard pattern directly behind the REQUESTED size of every scratch / sort / big-result request, verified by lasso_sync and lasso_trim (launch_plan.cuh SCRATCH_GUARD_BYTES)
 // ---- the three read per CALL, not per process (a commitment of that size is milliseconds; one test process runs both forms):
 inline bool msm_pip() { return unless0(getenv("LASSO_MSM_PIP")); }   // on; many long rows of full-width scalars by the 12-bit-window kernels (k_msm_pip_*) instead of the bucket kernel
 inline size_t msm_pip_min_cols() { const char* e = getenv("LASSO_MSM_PIP_MIN_COLS"); const long x = e ? atol(e) : 512; return (size_t)(x < 1 ? 1 : x); }   // 512, at least 1; columns from which they serve

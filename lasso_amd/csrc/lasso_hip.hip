@@ -47,6 +47,9 @@ struct lasso_ctx {
   std::string err;
   void* d_scratch = nullptr; size_t scratch_cap = 0;      // reduction partials / converted scalars
   void* d_pip = nullptr; size_t pip_cap = 0;              // k_msm_pip_*: a group of rows' sorted pairs, bucket offsets, size ranks and bucket sums (run_msm)
+  // LASSO_SCRATCH_GUARD=1 (tests): the most recent request of d_scratch / d_pip / d_big has the guard pattern behind its requested size (guard_place); guard_err: the first damage seen, reported by lasso_sync / lasso_trim
+  struct Guarded { uint8_t* base = nullptr; size_t req = 0; } guarded[3];
+  std::string guard_err;
   // Small results (round polynomials, claims) return through HOST-MAPPED pinned memory: the producing kernel stores straight into
   // h_small (d_small is the device alias of the same pages), then a sequence number is stored to h_flag and the host spins on it.
   // No hipMemcpy, no stream synchronisation: 6.7 us per round trip instead of 13.6 us (tools/latency_bench.hip on MI355X).
@@ -130,19 +133,48 @@ static int32_t grow_guard(lasso_ctx* c) {
   if (c->proto.waiting_on_device()) return fail(c, LASSO_ERR_INVALID, "a launch is waiting on the device for its challenge: only lasso_result_wait and the post of that challenge are legal until then");   // growing would synchronise the stream for the kernel's whole 5 s bail-out and lose the round
   return 0;
 }
+// ---- LASSO_SCRATCH_GUARD=1 (tests; launch_plan.cuh): the three device buffers below carry SCRATCH_GUARD_BYTES more than their capacity, and every request, growing or not, puts the
+// pattern directly behind the size it ASKED for, in stream order: a kernel that writes past a hand-summed request damages it although the write stays far inside the buffer's floor.
+// Nothing keeps data in these buffers across calls, and a launch enqueued ahead shares the stream with the round in front of it, so the memset never lands in live data.
+// The mapped result buffers (ensure_small) are left out: they may hold a pending result of another size.
+enum { GUARD_SCRATCH = 0, GUARD_PIP = 1, GUARD_BIG = 2 };
+// the stream is drained: read the guard of the buffer's most recent request back, once
+static void guard_check(lasso_ctx* c, int which) {
+  static const char* const names[3] = {"scratch", "sort (k_msm_pip_*)", "big-result"};
+  lasso_ctx::Guarded g = c->guarded[which]; c->guarded[which].base = nullptr;
+  if (!g.base) return;
+  std::vector<uint8_t> h(SCRATCH_GUARD_BYTES);
+  if (hipMemcpy(h.data(), g.base + g.req, SCRATCH_GUARD_BYTES, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return; }
+  const size_t bad = guard_first_damage(h.data());
+  if (bad < SCRATCH_GUARD_BYTES && c->guard_err.empty())
+    c->guard_err = std::string("LASSO_SCRATCH_GUARD: the ") + names[which] + " buffer was written behind its request of " + std::to_string(g.req) + " bytes: first damaged byte at offset " + std::to_string(g.req + bad);
+}
+static int32_t guard_place(lasso_ctx* c, int which, void* base, size_t bytes) {
+  if (!dsw::scratch_guard()) return 0;
+  if (c->guarded[which].base) { if (hipStreamQuery(c->stream) == hipSuccess) guard_check(c, which); else (void)hipGetLastError(); }   // an idle stream: the request before this one can be judged now
+  HIPCHK(c, hipMemsetAsync((uint8_t*)base + bytes, SCRATCH_GUARD_BYTE, SCRATCH_GUARD_BYTES, c->stream));
+  c->guarded[which].base = (uint8_t*)base; c->guarded[which].req = bytes; return 0;
+}
+// lasso_sync / lasso_trim, stream drained: the first damage since the last report
+static int32_t guard_report(lasso_ctx* c) {
+  if (!dsw::scratch_guard()) return 0;
+  for (int w = 0; w < 3; w++) guard_check(c, w);
+  if (c->guard_err.empty()) return 0;
+  std::string m; m.swap(c->guard_err); return fail(c, LASSO_ERR_INVALID, m);
+}
 static int32_t ensure_scratch(lasso_ctx* c, size_t bytes) {
-  if (bytes <= c->scratch_cap) return 0;
+  if (bytes <= c->scratch_cap) return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes);
   if (int32_t g = grow_guard(c)) return g;
-  if (c->d_scratch) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0; }
+  if (c->d_scratch) { HIPCHK(c, hipStreamSynchronize(c->stream)); guard_check(c, GUARD_SCRATCH); HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0; }
   size_t cap = bytes < ((size_t)1 << 22) ? ((size_t)1 << 22) : bytes;
-  HIPCHK(c, dmalloc(c, &c->d_scratch, cap)); c->scratch_cap = cap; return 0;
+  HIPCHK(c, dmalloc(c, &c->d_scratch, guard_alloc_bytes(cap, dsw::scratch_guard()))); c->scratch_cap = cap; return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes);
 }
 static int32_t ensure_pip(lasso_ctx* c, size_t bytes) {
-  if (bytes <= c->pip_cap) return 0;
+  if (bytes <= c->pip_cap) return guard_place(c, GUARD_PIP, c->d_pip, bytes);
   if (!c->proto.may_grow()) return LASSO_ERR_UNSUPPORTED;   // the caller takes the bucket kernel instead
-  if (c->d_pip) { HIPCHK(c, hipStreamSynchronize(c->stream)); HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
-  if (dmalloc(c, &c->d_pip, bytes) != hipSuccess) { (void)hipGetLastError(); c->d_pip = nullptr; return LASSO_ERR_UNSUPPORTED; }   // no room: not an error, the bucket kernel serves the commitment
-  c->pip_cap = bytes; return 0;
+  if (c->d_pip) { HIPCHK(c, hipStreamSynchronize(c->stream)); guard_check(c, GUARD_PIP); HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
+  if (dmalloc(c, &c->d_pip, guard_alloc_bytes(bytes, dsw::scratch_guard())) != hipSuccess) { (void)hipGetLastError(); c->d_pip = nullptr; return LASSO_ERR_UNSUPPORTED; }   // no room: not an error, the bucket kernel serves the commitment
+  c->pip_cap = bytes; return guard_place(c, GUARD_PIP, c->d_pip, bytes);
 }
 static int32_t ensure_small(lasso_ctx* c, size_t count) {
   if (count <= c->small_cap) return 0;
@@ -161,16 +193,17 @@ static int32_t ensure_small(lasso_ctx* c, size_t count) {
   c->small_cap = cap; return 0;
 }
 static int32_t ensure_big(lasso_ctx* c, size_t count) {
-  if (count <= c->big_cap) return 0;
+  if (count <= c->big_cap) return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t));
   if (int32_t g = grow_guard(c)) return g;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  guard_check(c, GUARD_BIG);
   if (c->d_big) (void)dfree(c, c->d_big);
   if (c->h_big) (void)hipHostFree(c->h_big);
   c->d_big = nullptr; c->h_big = nullptr; c->big_cap = 0;
   size_t cap = count < 8192 ? 8192 : count;
-  HIPCHK(c, dmalloc(c, (void**)&c->d_big, cap * sizeof(fr_t)));
+  HIPCHK(c, dmalloc(c, (void**)&c->d_big, guard_alloc_bytes(cap * sizeof(fr_t), dsw::scratch_guard())));
   HIPCHK(c, hipHostMalloc((void**)&c->h_big, cap * sizeof(fr_t), hipHostMallocDefault));
-  c->big_cap = cap; return 0;
+  c->big_cap = cap; return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t));
 }
 // profiling: bracket a launch with an event pair on the context's stream
 struct ProfScope {
@@ -522,6 +555,7 @@ int32_t lasso_mem_stats(lasso_ctx* c, uint64_t* live_bytes, uint64_t* peak_bytes
 int32_t lasso_trim(lasso_ctx* c) {
   REQUIRE(c, c && c->proto.idle());
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (int32_t g = guard_report(c)) return g;
   if (c->d_pip) { HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
   if (c->scratch_cap <= ((size_t)1 << 22)) return 0;
   HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0;
@@ -531,7 +565,7 @@ int32_t lasso_upload(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c
 int32_t lasso_download(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s && !c->proto.waiting_on_device()); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
 int32_t lasso_copy(lasso_ctx* c, void* d, const void* s, size_t n) { REQUIRE(c, d && s); ProfScope ps(c, LASSO_K_MISC, 2.0 * n); HIPCHK(c, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, c->stream)); return 0; }
 int32_t lasso_zero(lasso_ctx* c, void* d, size_t n) { REQUIRE(c, d); HIPCHK(c, hipMemsetAsync(d, 0, n, c->stream)); return 0; }
-int32_t lasso_sync(lasso_ctx* c) { REQUIRE(c, c && !c->proto.waiting_on_device()); HIPCHK(c, hipStreamSynchronize(c->stream)); return 0; }
+int32_t lasso_sync(lasso_ctx* c) { REQUIRE(c, c && !c->proto.waiting_on_device()); HIPCHK(c, hipStreamSynchronize(c->stream)); return guard_report(c); }
 
 int32_t lasso_prof_get_large(lasso_ctx* c, int32_t k, uint64_t* launches, double* ms, double* bytes) {
   REQUIRE(c, k >= 0 && k < LASSO_K_COUNT); prof_flush(c);

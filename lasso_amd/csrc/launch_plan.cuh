@@ -226,3 +226,13 @@ static inline MsmPlan msm_plan(const MsmShape& s, const MsmHave& have, const Msm
   p.adds = (double)s.rows * s.n_cols * (tab8 ? p.W8 : full8 ? 32 : p.pip_group ? MSM_PIP_WINDOWS : s.W);
   return p;
 }
+
+// ------------------------------------------------------------------ the guard behind the context's own buffers (LASSO_SCRATCH_GUARD, tests)
+// Every request of the scratch, the sort buffer of the 12-bit-window kernels and the big-result buffer names its size as a hand-written sum of sub-buffers, and the buffers'
+// floors (4 MiB of scratch) hide a sum that is too small at every shape a test runs.  With the switch on a buffer of capacity `cap` is allocated with SCRATCH_GUARD_BYTES more,
+// and each request of `bytes` <= cap has the pattern at [bytes, bytes + SCRATCH_GUARD_BYTES): directly behind what was ASKED for, wherever the capacity ends.
+#define SCRATCH_GUARD_BYTES ((size_t)64 << 10)
+#define SCRATCH_GUARD_BYTE 0xA5
+static inline size_t guard_alloc_bytes(size_t cap, bool guard) { return guard ? cap + SCRATCH_GUARD_BYTES : cap; }
+// the first byte of a guard read back that no longer holds the pattern, or SCRATCH_GUARD_BYTES: intact
+static inline size_t guard_first_damage(const uint8_t* g) { size_t i = 0; while (i < SCRATCH_GUARD_BYTES && g[i] == SCRATCH_GUARD_BYTE) i++; return i; }

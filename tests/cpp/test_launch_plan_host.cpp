@@ -232,6 +232,15 @@ int main() {
   if (test_cubic()) return 1;
   // the switch table's helpers
   CHECK(lasso::dsw::unless0(nullptr) && lasso::dsw::unless0("1") && !lasso::dsw::unless0("0") && !lasso::dsw::if1(nullptr) && lasso::dsw::if1("1") && !lasso::dsw::if1("0"));
+  // LASSO_SCRATCH_GUARD: default off; the guard's room is added to a capacity only with the switch on; the first damaged byte of a guard read back
+  CHECK(!lasso::dsw::scratch_guard());   // the test runs without the variable
+  CHECK(guard_alloc_bytes((size_t)1 << 22, false) == ((size_t)1 << 22) && guard_alloc_bytes((size_t)1 << 22, true) == ((size_t)1 << 22) + SCRATCH_GUARD_BYTES && SCRATCH_GUARD_BYTES >= ((size_t)64 << 10));
+  {
+    static uint8_t g[SCRATCH_GUARD_BYTES];
+    memset(g, SCRATCH_GUARD_BYTE, sizeof(g)); CHECK(guard_first_damage(g) == SCRATCH_GUARD_BYTES);
+    for (size_t at : {(size_t)0, (size_t)1, (size_t)4095, SCRATCH_GUARD_BYTES - 1}) { g[at] ^= 1; CHECK(guard_first_damage(g) == at); g[at] ^= 1; }
+    g[7] = 0; g[9] = 0; CHECK(guard_first_damage(g) == 7);
+  }
   printf("OK %ld checks\n", checks);
   return 0;
 }

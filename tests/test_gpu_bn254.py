@@ -142,3 +142,8 @@ def test_gpu_bn254_round_variants():
 def test_gpu_bn254_pass_variants():
     """tests/test_gpu_pass_variants.py on the BN254 build: every running sum of the sumcheck kernels through its fold, against the BN254 mock."""
     _rerun_on_bn254("test_gpu_pass_variants.py")
+
+
+def test_gpu_bn254_write_contract():
+    """tests/test_gpu_write_contract.py on the BN254 build: every child of it (the arena cases of tests/arena_cases.py by group and switch setting) inherits LASSO_TEST_CURVE."""
+    _rerun_on_bn254("test_gpu_write_contract.py", timeout=1800)
