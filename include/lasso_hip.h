@@ -74,7 +74,8 @@ typedef struct {
  * lasso_host_verify*, lasso_sumcheck_combine_round, lasso_combine_claim.  All pointers are HOST memory owned by the caller for the duration of the call.
  *   materialize_subtables    -> num_subtables tables of 2^log_m entries, ALL as 32-bit integers (tables_u32; what every table of the reference holds) or ALL as field
  *                               elements in memory form (tables_fr); exactly one of the two pointers is non-NULL.  The two device entry points do not read the tables.
- *   evaluate_subtable_mle    -> nothing to write: the verifier evaluates the MLE of the table itself (a dot product with EqPolynomial(point).evals(), 2^log_m products).
+ *   evaluate_subtable_mle    -> nothing to write: the verifier evaluates the MLE of the table itself, the dot product with EqPolynomial(point).evals() — one device call for all
+ *                               subtables where the device library has lasso_tables_mle (lasso_hip_mle.h; lasso_host_tables_mle, lasso_prover_mle.h, offers it to callers), else 2^log_m products on the host.
  *                               THE TABLES ARE PART OF THE STATEMENT: fixed by the strategy both sides agreed on, not chosen by the prover.
  *   memory_to_subtable_index / memory_to_dimension_index -> memory_subtable[i] < num_subtables, memory_dimension[i] < c; NULL = the trait's defaults i % num_subtables and
  *                               i / num_subtables (mod.rs:64-74), which require num_memories <= c * num_subtables.

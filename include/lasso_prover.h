@@ -204,7 +204,8 @@ int32_t lasso_host_points_from_candidates(lasso_host* h, const uint64_t* limbs, 
 int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_t* available, int32_t reset);
 /* Validate a strategy descriptor without proving anything: 0, or LASSO_ERR_INVALID (-1) with the reason in lasso_host_last_error().  For kind = LASSO_CUSTOM
  * (include/lasso_hip.h lasso_strategy_custom, passed as (const lasso_strategy*)&custom) this is the check lasso_host_prove* / lasso_host_verify* make on entry: table pointers,
- * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (2^log_m products per memory): THE TABLES ARE PART OF THE STATEMENT,
+ * memory maps, term list, degree and caps.  The verifier evaluates the tables' multilinear extensions itself (once per distinct subtable: one lasso_tables_mle call on the device,
+ * or 2^log_m products per subtable on the host; lasso_prover_mle.h): THE TABLES ARE PART OF THE STATEMENT,
  * fixed by the strategy prover and verifier agreed on — a verifier must never take them from the prover. */
 int32_t lasso_host_strategy_check(const lasso_strategy* strategy);
 /* Test support (not part of the reference's surface): prove_cubic_batched (sumcheck.rs:27-135, C = EqPolynomial(rand).evals()) on caller-supplied

@@ -198,4 +198,14 @@ def declare_gens(lib):
     return ["lasso_points_from_candidates"]
 
 
+def declare_mle(lib):
+    """include/lasso_hip_mle.h — the multilinear extensions of caller-defined tables at a point.  Declared apart from declare(), as declare_wire and declare_msm_points
+    are: an implementation of lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
+    for name in ("lasso_tables_mle", "lasso_tables_mle_dev"):
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), u32, u32, vp, vp]
+    return ["lasso_tables_mle", "lasso_tables_mle_dev"]
+
+
 HEADER_SYMBOLS = None

@@ -42,7 +42,8 @@ LASSO_DSWITCH(bool, bullet_ahead, unless0(getenv("LASSO_BULLET_AHEAD")))       /
 LASSO_DSWITCH(bool, bullet_tail_ahead, unless0(getenv("LASSO_BULLET_TAIL_AHEAD")))   // on; the opening's last fold, heads and delta MSM as one chain enqueued ahead of the last challenge
 // ---- the context's own buffers
 LASSO_DSWITCH(bool, scratch_guard, if1(getenv("LASSO_SCRATCH_GUARD")))         // off; tests: a guard pattern directly behind the REQUESTED size of every scratch / sort / big-result request, verified by lasso_sync and lasso_trim (launch_plan.cuh SCRATCH_GUARD_BYTES)
-// ---- the three read per CALL, not per process (a commitment of that size is milliseconds; one test process runs both forms):
+// ---- the four read per CALL, not per process (a commitment of that size is milliseconds; one test process runs both forms):
+inline long long mle_strip() { const char* e = getenv("LASSO_MLE_STRIP"); const long long x = e ? atoll(e) : 0; return x < 0 ? 0 : x; }   // 0 (unset): 64 MiB of strips over all tables; N: lasso_tables_mle uploads N entries of every table per strip (tests: strip boundaries within small tables)
 inline bool msm_pip() { return unless0(getenv("LASSO_MSM_PIP")); }   // on; many long rows of full-width scalars by the 12-bit-window kernels (k_msm_pip_*) instead of the bucket kernel
 inline size_t msm_pip_min_cols() { const char* e = getenv("LASSO_MSM_PIP_MIN_COLS"); const long x = e ? atol(e) : 512; return (size_t)(x < 1 ? 1 : x); }   // 512, at least 1; columns from which they serve
 inline size_t msm_pip_scratch_mb() { const char* e = getenv("LASSO_MSM_PIP_SCRATCH_MB"); const long x = e ? atol(e) : 1200; return (size_t)(x < 16 ? 16 : x); }   // 1200, at least 16; MiB of scratch a group of rows may take

@@ -23,6 +23,8 @@
 #include "../../include/lasso_hip_operands.h"
 #include "../../include/lasso_hip_gens.h"
 #include "gens_kernels.cuh"
+#include "../../include/lasso_hip_mle.h"
+#include "mle_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1836,6 +1838,68 @@ static int32_t msm_points_impl(lasso_ctx* c, const char* who, const lasso_affine
 }
 int32_t lasso_msm_points(lasso_ctx* c, const lasso_affine* points, const lasso_fr* scalars, size_t n, lasso_point* out) { return msm_points_impl(c, "lasso_msm_points", points, scalars, n, true, out); }
 int32_t lasso_msm_points_dev(lasso_ctx* c, const lasso_affine* d_points, const lasso_fr* d_scalars, size_t n, lasso_point* out) { return msm_points_impl(c, "lasso_msm_points_dev", d_points, d_scalars, n, false, out); }
+// include/lasso_hip_mle.h: the MLEs of caller-defined tables at one point (mle_kernels.cuh).  Device layout in the context's scratch, every region on a 256-byte boundary:
+// [hi factor table 32 * 2^hi_bits][lo factor table 32 * 2^lo_bits][block sums 32 * nx * num_tables] (host form only) [num_tables strips of strip_len entries].
+// The host form walks the tables strip by strip — upload, one launch over the strip's entries, the strip's sums added on the host — so its scratch does not grow with log_m.
+static int32_t tables_mle_impl(lasso_ctx* c, const char* who, const uint32_t* const* tu32, const lasso_fr* const* tfr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out, bool on_host) {
+  REQUIRE(c, point && out && (tu32 != nullptr) != (tfr != nullptr) && num_tables >= 1 && num_tables <= MLE_MAX_TABLES && log_m >= 1 && log_m <= 30);
+  for (uint32_t k = 0; k < num_tables; k++) REQUIRE(c, tu32 ? tu32[k] != nullptr : tfr[k] != nullptr);
+  const bool fr = tfr != nullptr; const size_t elem = fr ? sizeof(lasso_fr) : sizeof(uint32_t);
+  const uint64_t m = (uint64_t)1 << log_m;
+  const uint64_t strip = on_host ? mle_strip_len(num_tables, elem, dsw::mle_strip()) : m, strip_len = strip < m ? strip : m;
+  const MlePlan whole = mle_plan(log_m, 0, m);   // the split of the point; every strip's own plan gives its grid
+  const unsigned max_nx = mle_max_nx(log_m, strip_len);
+  const size_t o_hi = 0, o_lo = o_hi + up256(sizeof(fr_t) << whole.hi_bits), o_part = o_lo + up256(sizeof(fr_t) << whole.lo_bits);
+  const size_t part_bytes = up256((size_t)max_nx * num_tables * sizeof(fr_t)), o_strip = o_part + part_bytes, strip_bytes = up256((size_t)strip_len * elem);
+  int32_t rc = ensure_scratch(c, o_strip + (on_host ? strip_bytes * num_tables : 0));
+  if (!rc) rc = ensure_small(c, num_tables);
+  if (rc) return rc == LASSO_ERR_UNSUPPORTED ? fail(c, rc, std::string(who) + ": the scratch buffer cannot grow while a resident kernel is active") : rc;
+  uint8_t* base = (uint8_t*)c->d_scratch;
+  fr_t* hi = (fr_t*)(base + o_hi); fr_t* lo = (fr_t*)(base + o_lo);
+  {
+    RTable16 Rh, Rl; for (uint32_t j = 0; j < 16; j++) { Rh.r[j] = j < whole.hi_bits ? to_fr(point + j) : fr_zero(); Rl.r[j] = j < whole.lo_bits ? to_fr(point + whole.hi_bits + j) : fr_zero(); }
+    const unsigned hb = grid_for((size_t)1 << whole.hi_bits), lb = grid_for((size_t)1 << whole.lo_bits);
+    ProfScope ps(c, LASSO_K_EQ, 32.0 * (((size_t)1 << whole.hi_bits) + ((size_t)1 << whole.lo_bits)));
+    hipLaunchKernelGGL(k_eq_small2, dim3(hb + lb), dim3(LASSO_BLOCK), 0, c->stream, Rh, whole.hi_bits, fr ? fr_one() : fr_r2(), hi, hb, Rl, whole.lo_bits, lo);   // u32 entries are integers: the scale 2^256 puts the sums in memory form
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<fr_t> acc(num_tables, fr_zero()); std::vector<lasso_fr> part(num_tables);
+  for (uint64_t e0 = 0; e0 < m; e0 += strip_len) {
+    const uint64_t e1 = e0 + strip_len < m ? e0 + strip_len : m;
+    const MlePlan P = mle_plan(log_m, e0, e1);
+    if (P.nx > max_nx) return fail(c, LASSO_ERR_INVALID, std::string(who) + ": internal: a strip's grid exceeds the block sums reserved for it");
+    MleTables T;
+    for (uint32_t k = 0; k < MLE_MAX_TABLES; k++) T.p[k] = nullptr;
+    for (uint32_t k = 0; k < num_tables; k++) {
+      const uint8_t* src = fr ? (const uint8_t*)tfr[k] : (const uint8_t*)tu32[k];
+      if (on_host) {
+        uint8_t* dst = base + o_strip + (size_t)k * strip_bytes;
+        HIPCHK(c, hipMemcpyAsync(dst, src + e0 * elem, (size_t)(e1 - e0) * elem, hipMemcpyHostToDevice, c->stream));
+        T.p[k] = dst;
+      } else T.p[k] = src;
+    }
+    const uint32_t seq = next_seq(c);
+    {
+      ProfScope ps(c, LASSO_K_DOT, (double)num_tables * (double)(e1 - e0) * (double)elem);
+      if (fr) hipLaunchKernelGGL((k_tables_mle<true>), dim3(P.nx * num_tables), dim3(LASSO_BLOCK), 0, c->stream, T, P.nx, num_tables, (const fr_t*)hi, (const fr_t*)lo, P.lo_bits, P.row_first, P.rows, P.rows_per_task,
+                                 e0, e1, (fr_t*)(base + o_part), c->d_counters, RES(c), seq);
+      else hipLaunchKernelGGL((k_tables_mle<false>), dim3(P.nx * num_tables), dim3(LASSO_BLOCK), 0, c->stream, T, P.nx, num_tables, (const fr_t*)hi, (const fr_t*)lo, P.lo_bits, P.row_first, P.rows, P.rows_per_task,
+                              e0, e1, (fr_t*)(base + o_part), c->d_counters, RES(c), seq);
+    }
+    HIPCHK(c, hipGetLastError());
+    rc = wait_flag(c, seq, num_tables, part.data(), c->tagged); if (rc) return rc;
+    for (uint32_t k = 0; k < num_tables; k++) acc[k] = fr_add(acc[k], to_fr(&part[k]));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (uint32_t k = 0; k < num_tables; k++) memcpy(out + k, acc[k].v, 32);
+  return 0;
+}
+int32_t lasso_tables_mle(lasso_ctx* c, const uint32_t* const* tables_u32, const lasso_fr* const* tables_fr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out) {
+  return tables_mle_impl(c, "lasso_tables_mle", tables_u32, tables_fr, num_tables, log_m, point, out, true);
+}
+int32_t lasso_tables_mle_dev(lasso_ctx* c, const uint32_t* const* d_tables_u32, const lasso_fr* const* d_tables_fr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out) {
+  return tables_mle_impl(c, "lasso_tables_mle_dev", d_tables_u32, d_tables_fr, num_tables, log_m, point, out, false);
+}
 __global__ void __launch_bounds__(256) k_scale_to_integers(const fr_t* __restrict__ src, size_t n, fr_t scale, fr_t t0, fr_t t1, fr_t* __restrict__ dst) {
   const fr29 ss = fr29_unpack_s(scale); fr29 k32 = fr29_zero(); k32.v[0] = 32;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = fr29_store(fr29_mul(fr29_mul(fr29_unpack_u(src[i]), ss), k32));   // (u * s) = u-form, then -> integer

@@ -227,6 +227,42 @@ static inline MsmPlan msm_plan(const MsmShape& s, const MsmHave& have, const Msm
   return p;
 }
 
+// ------------------------------------------------------------------ the MLE of caller-defined tables (lasso_tables_mle, mle_kernels.cuh)
+// Entry i of a table of 2^log_m entries is (row i_hi, column i_lo), i = i_hi 2^lo_bits + i_lo, with the FIRST ceil(log_m / 2) coordinates of the point in the row factor:
+// log_m = 1 and 2 leave the column factor with zero and one variable (a one-entry table [1] is a legal factor table).  A lane's task is one column i_lo over a run of
+// rows_per_task rows, so a workgroup tile is 256 tasks; entries [e0, e1) of the table — a strip, or all of it — touch rows e0 >> lo_bits .. (e1 - 1) >> lo_bits.
+// MLE_ROWS_PER_TASK rows per task where that fills at most MLE_MAX_NX workgroups per table; above that the runs grow instead, so the block sums stay within 2 MiB for 32 tables.
+#define MLE_ROWS_PER_TASK 64u
+#define MLE_MAX_NX 2048u
+#define MLE_MAX_TABLES 32u
+#define MLE_STRIP_BYTES ((size_t)64 << 20)   // the host form's strips, all tables together, unless LASSO_MLE_STRIP names a length
+struct MlePlan { uint32_t hi_bits, lo_bits, row_first, rows, rows_per_task; uint64_t tasks; unsigned nx; };
+static inline MlePlan mle_plan_rows(uint32_t log_m, uint32_t row_first, uint32_t rows) {
+  MlePlan p; p.hi_bits = (log_m + 1) / 2; p.lo_bits = log_m - p.hi_bits;
+  p.row_first = row_first; p.rows = rows;
+  p.rows_per_task = MLE_ROWS_PER_TASK;
+  const uint64_t max_runs = ((uint64_t)MLE_MAX_NX * LASSO_BLOCK) >> p.lo_bits;   // >= 16: lo_bits <= 15
+  if (((uint64_t)p.rows + p.rows_per_task - 1) / p.rows_per_task > max_runs) p.rows_per_task = (uint32_t)(((uint64_t)p.rows + max_runs - 1) / max_runs);
+  const uint64_t runs = ((uint64_t)p.rows + p.rows_per_task - 1) / p.rows_per_task;
+  p.tasks = runs << p.lo_bits; p.nx = (unsigned)((p.tasks + LASSO_BLOCK - 1) / LASSO_BLOCK);
+  return p;
+}
+static inline MlePlan mle_plan(uint32_t log_m, uint64_t e0, uint64_t e1) {
+  const uint32_t lo_bits = log_m - (log_m + 1) / 2, row_first = (uint32_t)(e0 >> lo_bits);
+  return mle_plan_rows(log_m, row_first, (uint32_t)((e1 - 1) >> lo_bits) + 1 - row_first);
+}
+// the widest grid any strip of `strip_len` entries can ask for: a strip that starts inside a row touches one row more than one that starts on a row boundary (nx grows with rows)
+static inline unsigned mle_max_nx(uint32_t log_m, uint64_t strip_len) {
+  const uint32_t hi_bits = (log_m + 1) / 2, lo_bits = log_m - hi_bits;
+  uint64_t rows = ((strip_len + (((uint64_t)1 << lo_bits) - 1)) >> lo_bits) + 1; if (rows > ((uint64_t)1 << hi_bits)) rows = (uint64_t)1 << hi_bits;
+  return mle_plan_rows(log_m, 0, (uint32_t)rows).nx;
+}
+// entries of every table per strip of the host form: strip_sw > 0 (LASSO_MLE_STRIP) as given, else what MLE_STRIP_BYTES holds for all tables, a multiple of 256, at least 256
+static inline uint64_t mle_strip_len(uint32_t num_tables, size_t elem_bytes, long long strip_sw) {
+  if (strip_sw > 0) return (uint64_t)strip_sw;
+  uint64_t n = MLE_STRIP_BYTES / ((size_t)num_tables * elem_bytes); n &= ~(uint64_t)255; return n < 256 ? 256 : n;
+}
+
 // ------------------------------------------------------------------ the guard behind the context's own buffers (LASSO_SCRATCH_GUARD, tests)
 // Every request of the scratch, the sort buffer of the 12-bit-window kernels and the big-result buffer names its size as a hand-written sum of sub-buffers, and the buffers'
 // floors (4 MiB of scratch) hide a sum that is too small at every shape a test runs.  With the switch on a buffer of capacity `cap` is allocated with SCRATCH_GUARD_BYTES more,

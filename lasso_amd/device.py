@@ -388,6 +388,42 @@ class Device:
         self._chk(fn(self.ctx, C.c_void_p(d_points), C.c_void_p(d_scalars), n, _vp(out)))
         return out
 
+    def _tables_mle_fn(self, name):
+        if not hasattr(self, "_mle_ok"):
+            try:
+                _abi.declare_mle(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_tables_mle (include/lasso_hip_mle.h)")
+            self._mle_ok = True
+        return getattr(self.lib, name)
+
+    def tables_mle(self, tables, point):
+        """out[k] = sum_i tables[k][i] * EqPolynomial(point).evals()[i] (include/lasso_hip_mle.h lasso_tables_mle): `tables` = up to 32 host arrays of one form — all 1-D
+        uint32 of 2^log_m entries, or all (2^log_m, 4) uint64 memory words — and `point` = (log_m, 4) uint64.  Returns (len(tables), 4) uint64, fully reduced.  A library
+        without the entry point is an error, not a fall-back."""
+        fn = self._tables_mle_fn("lasso_tables_mle")
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        tables = [np.asarray(t) for t in tables]
+        field = bool(tables) and tables[0].ndim == 2
+        if any((t.ndim == 2) != field for t in tables):
+            raise LassoError("tables_mle: all tables use one form (32-bit integers or field elements)")
+        tables = [np.ascontiguousarray(t, dtype=np.uint64 if field else np.uint32) for t in tables]
+        if any(t.shape[0] != 1 << point.shape[0] for t in tables):
+            raise LassoError("tables_mle: every table has 2^len(point) entries")
+        ptrs = self._ptrs([t.ctypes.data for t in tables])
+        out = np.zeros((len(tables), 4), dtype=np.uint64)
+        self._chk(fn(self.ctx, None if field else ptrs, ptrs if field else None, len(tables), point.shape[0], _vp(point), _vp(out)))
+        return out
+
+    def tables_mle_dev(self, d_tables, point, field):
+        """tables_mle over tables that are already on the device (lasso_tables_mle_dev): `d_tables` = device pointers, `field` = whether they hold field elements"""
+        fn = self._tables_mle_fn("lasso_tables_mle_dev")
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        ptrs = self._ptrs(list(d_tables))
+        out = np.zeros((len(d_tables), 4), dtype=np.uint64)
+        self._chk(fn(self.ctx, None if field else ptrs, ptrs if field else None, len(d_tables), point.shape[0], _vp(point), _vp(out)))
+        return out
+
     def msm_dev(self, bases, d_scalars, n):
         out = np.empty((1, 16), dtype=np.uint64)
         self._chk(self.lib.lasso_msm_dev(self.ctx, C.c_void_p(bases), C.c_void_p(d_scalars), n, _vp(out)))

@@ -8,6 +8,8 @@
 #include "../../include/lasso_hip_msm.h"
 #include "../../include/lasso_hip_operands.h"
 #include "../../include/lasso_hip_gens.h"
+#include "../../include/lasso_hip_mle.h"
+#include "../../include/lasso_prover_mle.h"
 
 using namespace lasso;
 
@@ -34,6 +36,11 @@ extern "C" int32_t lasso_densify_dim_operands(lasso_ctx*, const uint64_t*, const
 // entry point exists; LASSO_GENS_DEVICE_MIN is the smallest set that goes to the device, LASSO_GENS_DEVICE_BATCH caps the candidates per call (switches.hpp).
 extern "C" int32_t lasso_points_from_candidates(lasso_ctx*, const uint64_t*, const uint8_t*, size_t, lasso_affine*, uint8_t*) __attribute__((weak));
 
+// The MLEs of caller-defined subtables on the device (include/lasso_hip_mle.h) are optional in the same way: a weak reference, null against an implementation of lasso_hip.h
+// alone — the verifier then keeps its host loop (2^log_m products per subtable), and lasso_host_tables_mle(where = 1) says so.  LASSO_VERIFY_DEVICE_MLE=0 keeps the host loop
+// where the entry point exists; LASSO_MLE_DEVICE_MIN is the smallest num_subtables * 2^log_m that goes to the device (switches.hpp).
+extern "C" int32_t lasso_tables_mle(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -44,6 +51,8 @@ struct lasso_host {
   uint64_t msm_points_calls = 0;     // Verifier::msm_points calls of this host that took lasso_msm_points (lasso_host_msm_stats)
   uint64_t operand_dims = 0;         // dimensions densified by lasso_densify_dim_operands for this host (lasso_host_densify_stats)
   uint64_t gens_device_candidates = 0;   // candidates handed to lasso_points_from_candidates for this host (lasso_host_gens_stats)
+  uint64_t mle_device_tables = 0;        // caller-defined tables evaluated by lasso_tables_mle for this host (lasso_host_mle_stats)
+  TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = &mle_device_tables; } return m; }
   GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = &gens_device_candidates; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
   WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
@@ -293,7 +302,7 @@ int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_stra
     ProofTranscript t(tv, tu);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm());
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm(), h->tables_mle());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     HostClock::dump();
     return 0;)
@@ -306,7 +315,7 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
     ProofTranscript t(tl);
     ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
     check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm());
+    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm(), h->tables_mle());
     *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
     HostClock::dump();
     return 0;)
@@ -410,6 +419,33 @@ int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_
     if (device_candidates) *device_candidates = h->gens_device_candidates;
     if (available) *available = lasso_points_from_candidates ? 1 : 0;
     if (reset) h->gens_device_candidates = 0;
+    return 0;)
+}
+// include/lasso_prover_mle.h: SubtableStrategy::evaluate_subtable_mle for every subtable of a strategy of any kind
+int32_t lasso_host_tables_mle(lasso_host* h, const lasso_strategy* st, const lasso_fr* point, size_t point_len, int32_t where, lasso_fr* out) {
+  GUARD(
+    if (!h || !st || !out || (!point && point_len) || (where != 0 && where != 1)) throw Error("lasso_host_tables_mle: null argument, or `where` is neither 0 (host) nor 1 (device)");
+    const Strategy S = Strategy::from_abi(st);
+    if (point_len != S.abi.log_m) throw Error("lasso_host_tables_mle: the point must have log_m coordinates");
+    ScVec pt; for (size_t i = 0; i < point_len; i++) pt.push_back(Sc::from_abi(point[i]));
+    const size_t n = S.num_subtables();
+    if (S.custom() && where == 1) {
+      if (!lasso_tables_mle) throw Error("lasso_host_tables_mle: the device entry (lasso_tables_mle, include/lasso_hip_mle.h) is not available in the device library this host was linked against");
+      TablesMle m; m.fn = &lasso_tables_mle; m.counter = &h->mle_device_tables;
+      std::vector<size_t> ks(n); for (size_t k = 0; k < n; k++) ks[k] = k;
+      const ScVec v = custom_subtable_mles_device(h->dev, S, m, ks, pt);
+      for (size_t k = 0; k < n; k++) out[k] = v[k].abi();
+      return 0;
+    }
+    for (size_t k = 0; k < n; k++) out[k] = evaluate_subtable_mle(S, k, pt).abi();
+    return 0;)
+}
+int32_t lasso_host_mle_stats(lasso_host* h, uint64_t* device_tables, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_mle_stats: null host");
+    if (device_tables) *device_tables = h->mle_device_tables;
+    if (available) *available = lasso_tables_mle ? 1 : 0;
+    if (reset) h->mle_device_tables = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

@@ -8,6 +8,9 @@ namespace lasso { namespace sw {
 inline bool unless0(const char* e) { return !(e && e[0] == '0'); }   // default on
 inline bool if1(const char* e) { return e && e[0] == '1'; }           // default off
 #define LASSO_SWITCH(type, name, value) inline type name() { static const type v = (value); return v; }
+// LASSO_MLE_DEVICE_MIN's default: the smallest MEASURED num_subtables * 2^log_m from which the device route's slowest verify stays below the host loop's fastest
+// (4 subtables of 2^12 entries: 12.24 ms [12.05, 12.33] against 13.30 ms [12.92, 13.48]; profiles/verify_device_mle.json) — smaller strategies stay on the host
+#define LASSO_MLE_DEVICE_MIN_DEFAULT ((size_t)16384)
 LASSO_SWITCH(int, trace, [] { const char* e = getenv("LASSO_TRACE"); return e && e[0] >= '1' && e[0] <= '3' ? e[0] - '0' : 0; }())   // 0; 1: wall-clock spans (Trace), 2: host time buckets (HostClock), 3: device bytes per span
 LASSO_SWITCH(bool, capacity, if1(getenv("LASSO_CAPACITY")))                  // off; capacity mode for every host (Dev::capacity; lasso_host_set_capacity sets it per host)
 LASSO_SWITCH(bool, capacity_compact, unless0(getenv("LASSO_CAPACITY_COMPACT")))   // on; capacity mode holds dim / read as 32-bit integers
@@ -33,6 +36,8 @@ LASSO_SWITCH(bool, densify_operands, unless0(getenv("LASSO_DENSIFY_OPERANDS"))) 
 LASSO_SWITCH(bool, gens_device, unless0(getenv("LASSO_GENS_DEVICE")))                     // on; label-derived generators: the candidates' arithmetic in one lasso_points_from_candidates launch (off: one by one on the host)
 LASSO_SWITCH(size_t, gens_device_min, [] { const char* e = getenv("LASSO_GENS_DEVICE_MIN"); const long long x = e ? atoll(e) : 8194; return (size_t)(x < 1 ? 1 : x); }())   // 8194 (the smallest set measured with the device ahead on both curves), at least 1; smaller sets stay on the host
 LASSO_SWITCH(size_t, gens_device_batch, [] { const char* e = getenv("LASSO_GENS_DEVICE_BATCH"); const long long x = e ? atoll(e) : 0; return (size_t)(x < 1 ? 0 : x); }())   // 0 = no cap; most candidates per device call (bounds the call's scratch: 98 bytes per candidate)
+LASSO_SWITCH(bool, verify_device_mle, unless0(getenv("LASSO_VERIFY_DEVICE_MLE")))         // on; the verifier evaluates a caller-defined strategy's subtable MLEs in one lasso_tables_mle call (off: the host loop, 2^log_m products per subtable)
+LASSO_SWITCH(size_t, mle_device_min, [] { const char* e = getenv("LASSO_MLE_DEVICE_MIN"); if (!e) return LASSO_MLE_DEVICE_MIN_DEFAULT; const long long x = atoll(e); return (size_t)(x < 0 ? 0 : x); }())   // see LASSO_MLE_DEVICE_MIN_DEFAULT; strategies with num_subtables * 2^log_m below it stay on the host
 // the two read per CALL, not per process (a test sets them between calls):
 inline bool slab_rccl() { return unless0(getenv("LASSO_SLAB_RCCL")); }             // on; slab mode's bulk exchange over RCCL (lasso_host_set_comm_shm)
 inline bool debug_cubic_host() { return if1(getenv("LASSO_DEBUG_CUBIC_HOST")); }   // off; lasso_host_debug_prove_cubic_batched runs the HOST rounds

@@ -22,6 +22,7 @@
 #include "prover.hpp"
 #include "../../include/lasso_hip_wire.h"
 #include "../../include/lasso_hip_msm.h"
+#include "../../include/lasso_hip_mle.h"
 
 namespace lasso {
 
@@ -109,6 +110,13 @@ struct PointsMsm {
   uint64_t* counter = nullptr;    // Verifier::msm_points calls that took it, per host (lasso_host_msm_stats)
 };
 
+// The MLEs of caller-defined tables on the device as the verifier sees them (prover_capi.cpp fills it in: lasso_tables_mle is a weak reference too, include/lasso_hip_mle.h)
+struct TablesMle {
+  int32_t (*fn)(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) = nullptr;
+  size_t min_entries = 0;         // strategies with num_subtables * 2^log_m below this stay on the host (LASSO_MLE_DEVICE_MIN)
+  uint64_t* counter = nullptr;    // tables evaluated on the device, per host (lasso_host_mle_stats)
+};
+
 // ------------------------------------------------------------------ reader of the ark-serialize byte stream
 struct ProofReader {
   const uint8_t* p; size_t n, pos = 0;
@@ -170,7 +178,8 @@ inline WireProof read_proof(const Strategy& S, ProofReader& r) {
 inline WireProof read_proof(const Strategy& S, const uint8_t* bytes, size_t n) { ProofReader r(bytes, n); return read_proof(S, r); }
 
 // ------------------------------------------------------------------ host side of SubtableStrategy the verifier needs (subtables/*.rs)
-// A caller-defined table has no closed form: its MLE at a point is the dot product of the table with EqPolynomial(point).evals() (2^log_m products, on the host).  The
+// A caller-defined table has no closed form: its MLE at a point is the dot product of the table with EqPolynomial(point).evals() — 2^log_m products on one thread here (the
+// host route: LASSO_VERIFY_DEVICE_MLE=0, strategies below LASSO_MLE_DEVICE_MIN, device libraries without lasso_tables_mle), or custom_subtable_mles_device below.  The
 // tables are part of the STATEMENT — fixed by the strategy prover and verifier agreed on, never taken from the prover (include/lasso_hip.h lasso_strategy_custom).
 inline Sc evaluate_subtable_mle(const Strategy& S, size_t k, const ScVec& point) {
   const int kind = S.abi.kind; const size_t n = point.size();
@@ -211,6 +220,19 @@ inline Sc evaluate_subtable_mle(const Strategy& S, size_t k, const ScVec& point)
   }
   return res;
 }
+// the same for the subtables `ks` of a caller-defined strategy in ONE device call (lasso_tables_mle): the eq table is never formed, the tables are read once.  A device
+// status propagates like every other (Dev::chk): there is no fall-back to the host loop.
+inline ScVec custom_subtable_mles_device(const Dev& d, const Strategy& S, const TablesMle& dev, const std::vector<size_t>& ks, const ScVec& point) {
+  LASSO_REQUIRE(S.custom() && dev.fn && point.size() == S.abi.log_m && !ks.empty());
+  std::vector<const uint32_t*> tu; std::vector<const lasso_fr*> tf;
+  for (size_t k : ks) { LASSO_REQUIRE(k < S.cabi.num_subtables); if (S.cabi.tables_u32) tu.push_back(S.cabi.tables_u32[k]); else tf.push_back(S.cabi.tables_fr[k]); }
+  std::vector<lasso_fr> pt(point.size()), out(ks.size());
+  for (size_t i = 0; i < point.size(); i++) pt[i] = point[i].abi();
+  d.chk(dev.fn(d.ctx, tu.empty() ? nullptr : tu.data(), tf.empty() ? nullptr : tf.data(), (uint32_t)ks.size(), S.abi.log_m, pt.data(), out.data()), "lasso_tables_mle");
+  if (dev.counter) *dev.counter += ks.size();
+  ScVec res; for (auto& o : out) res.push_back(Sc::from_abi(o));
+  return res;
+}
 inline Sc combine_lookups(const Strategy& S, const ScVec& vals) {
   if (S.custom()) {   // the caller's term list: g(v) = sum_t coeff_t prod_j v[mem_{t,j}]
     Sc sum = Sc::zero();
@@ -230,7 +252,7 @@ inline Sc combine_lookups(const Strategy& S, const ScVec& vals) {
 
 // ------------------------------------------------------------------ the verifier
 class Verifier {
-  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t; WireDecoder decoder; PointsMsm points_msm;
+  const Dev& d; const Strategy& S; const SparsePolyCommitmentGens& gens; ProofTranscript& t; WireDecoder decoder; PointsMsm points_msm; TablesMle tables_mle;
 
   // sumcheck.rs:286-328
   bool sumcheck_verify(const SumcheckProof& proof, const Sc& claim, size_t num_rounds, size_t degree_bound, Sc& e_out, ScVec& r_out) {
@@ -353,7 +375,7 @@ class Verifier {
   }
 
  public:
-  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder(), const PointsMsm& m_ = PointsMsm()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_), points_msm(m_) {}
+  Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder(), const PointsMsm& m_ = PointsMsm(), const TablesMle& e_ = TablesMle()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_), points_msm(m_), tables_mle(e_) {}
 
   // Proof and commitment with every point decoded in ONE device call.  false = not taken (no device decoder, a batch below the threshold) or not clean (the bytes do
   // not walk, a scalar is not canonical, some encoding is rejected): the caller then runs the sequential reader, which finds the FIRST error in stream order and
@@ -445,6 +467,14 @@ class Verifier {
     const Sc g2 = gamma.square();
     auto h = [&](const Sc& a, const Sc& v, const Sc& ts) { return ts * g2 + v * gamma + a - tau; };
     std::map<size_t, Sc> mle_of;   // one evaluation per subtable, not per memory (a caller-defined table costs 2^log_m products)
+    // a caller-defined strategy on the device route: the distinct subtables its memories use, all in ONE lasso_tables_mle call at rand_mem (the built-in kinds keep their closed forms)
+    if (S.custom() && tables_mle.fn && (uint64_t)S.cabi.num_subtables << log_m >= tables_mle.min_entries) {
+      std::vector<size_t> ks;
+      for (size_t i = 0; i < alpha; i++) { const size_t k = S.memory_to_subtable_index(i); if (std::find(ks.begin(), ks.end(), k) == ks.end()) ks.push_back(k); }
+      HostClock hc("verify: subtable MLEs (device)");
+      const ScVec v = custom_subtable_mles_device(d, S, tables_mle, ks, rand_mem);
+      for (size_t q = 0; q < ks.size(); q++) mle_of[ks[q]] = v[q];
+    }
     for (size_t i = 0; i < alpha; i++) {
       const size_t j = S.memory_to_dimension_index(i), k = S.memory_to_subtable_index(i);
       if (!mle_of.count(k)) mle_of[k] = evaluate_subtable_mle(S, k, rand_mem);

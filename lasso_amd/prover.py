@@ -304,6 +304,38 @@ class HostProver:
         self._chk(self.lib.lasso_host_gens_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
         return {"device_candidates": k.value, "available": bool(a.value)}
 
+    def _mle_fns(self):
+        """include/lasso_prover_mle.h, declared on first use (a prover library built before that header existed does not export it)"""
+        if not hasattr(self, "_mle_ok"):
+            try:
+                self.lib.lasso_host_tables_mle.argtypes = [C.c_void_p, C.POINTER(_abi.Strategy), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
+                self.lib.lasso_host_mle_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int32]
+            except AttributeError:
+                raise LassoError("this prover library does not export lasso_host_tables_mle (include/lasso_prover_mle.h)")
+            self._mle_ok = True
+        return self.lib
+
+    def tables_mle(self, strategy, point, where=0):
+        """SubtableStrategy::evaluate_subtable_mle for every subtable of `strategy` (any kind) at `point` = (log_m, 4) uint64: (num_subtables, 4) uint64, fully reduced.
+        Built-in kinds and Spark: their closed forms.  A CustomStrategy: where=0 the host loop, where=1 one lasso_tables_mle call on the device (LassoError when the device
+        library has no such entry) — lasso_host_tables_mle"""
+        lib = self._mle_fns()
+        point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
+        kind = strategy.desc.base.kind if hasattr(strategy, "desc") else strategy.kind
+        c = strategy.c
+        n = strategy.num_subtables if hasattr(strategy, "desc") else {_abi.KINDS["lt"]: 2, _abi.KINDS["range"]: 3, _abi.KINDS["spark"]: c}.get(kind, 1)
+        out = np.zeros((n, 4), dtype=np.uint64)
+        self._chk(lib.lasso_host_tables_mle(self.h, strategy_ptr(strategy), point.ctypes.data_as(C.c_void_p), point.shape[0], where, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def mle_stats(self, reset=False):
+        """{"device_tables": caller-defined tables this host evaluated on the device so far, "available": whether the device library has lasso_tables_mle}
+        (lasso_host_mle_stats)"""
+        lib = self._mle_fns()
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(lib.lasso_host_mle_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"device_tables": k.value, "available": bool(a.value)}
+
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
         self._chk(self.lib.lasso_host_strategy_check(strategy_ptr(strategy)))
