@@ -42,6 +42,15 @@ LASSO_DSWITCH(bool, bullet_ahead, unless0(getenv("LASSO_BULLET_AHEAD")))       /
 LASSO_DSWITCH(bool, bullet_tail_ahead, unless0(getenv("LASSO_BULLET_TAIL_AHEAD")))   // on; the opening's last fold, heads and delta MSM as one chain enqueued ahead of the last challenge
 // ---- the context's own buffers
 LASSO_DSWITCH(bool, scratch_guard, if1(getenv("LASSO_SCRATCH_GUARD")))         // off; tests: a guard pattern directly behind the REQUESTED size of every scratch / sort / big-result request, verified by lasso_sync and lasso_trim (launch_plan.cuh SCRATCH_GUARD_BYTES)
+LASSO_DSWITCH(bool, poison, if1(getenv("LASSO_POISON")))                       // off; tests: every allocation the library makes, and the requested range of every first scratch / sort / big-result request of a call, starts as POISON_WORD repeated instead of as whatever was there (launch_plan.cuh poison_range)
+// the fill of LASSO_POISON, as 32-bit words: a stale field element, counter or flag is non-zero, and a stale word used as an index stays inside any table of two or more entries
+// (all-ones or random bytes would turn a stray indexed read into an access out of bounds).  The oracle's mock fills its lasso_alloc with the same word.
+static const uint32_t POISON_WORD = 0x00000001u;
+// host memory [p, p + bytes) as `word` repeated from p on (p 4-byte aligned; a tail of 1..3 bytes gets the word's first bytes in memory order)
+inline void poison_fill_host(void* p, size_t bytes, uint32_t word) {
+  uint32_t* w = (uint32_t*)p; for (size_t i = 0; i < bytes / 4; i++) w[i] = word;
+  for (size_t i = bytes & ~(size_t)3; i < bytes; i++) ((uint8_t*)p)[i] = ((const uint8_t*)&word)[i & 3];
+}
 // ---- the four read per CALL, not per process (a commitment of that size is milliseconds; one test process runs both forms):
 inline long long mle_strip() { const char* e = getenv("LASSO_MLE_STRIP"); const long long x = e ? atoll(e) : 0; return x < 0 ? 0 : x; }   // 0 (unset): 64 MiB of strips over all tables; N: lasso_tables_mle uploads N entries of every table per strip (tests: strip boundaries within small tables)
 inline bool msm_pip() { return unless0(getenv("LASSO_MSM_PIP")); }   // on; many long rows of full-width scalars by the 12-bit-window kernels (k_msm_pip_*) instead of the bucket kernel

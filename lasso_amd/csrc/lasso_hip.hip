@@ -52,6 +52,9 @@ struct lasso_ctx {
   // LASSO_SCRATCH_GUARD=1 (tests): the most recent request of d_scratch / d_pip / d_big has the guard pattern behind its requested size (guard_place); guard_err: the first damage seen, reported by lasso_sync / lasso_trim
   struct Guarded { uint8_t* base = nullptr; size_t req = 0; } guarded[3];
   std::string guard_err;
+  // LASSO_POISON=1 (tests): entry_depth counts the public entry points on the stack (EntryScope, in REQUIRE); the outermost one zeroes poison_done, the bytes of each of the
+  // three buffers the call in progress has requested so far: 0 = its first request of that buffer is still to come (poison_request).  Outside a public call nothing is filled
+  size_t poison_done[3] = {~(size_t)0, ~(size_t)0, ~(size_t)0}; int entry_depth = 0;
   // Small results (round polynomials, claims) return through HOST-MAPPED pinned memory: the producing kernel stores straight into
   // h_small (d_small is the device alias of the same pages), then a sequence number is stored to h_flag and the host spins on it.
   // No hipMemcpy, no stream synchronisation: 6.7 us per round trip instead of 13.6 us (tools/latency_bench.hip on MI355X).
@@ -115,12 +118,40 @@ static int32_t fail(lasso_ctx* c, int32_t code, const std::string& msg) { if (c)
 // Every entry point runs on the context's device whatever the calling thread's current device is (two contexts on different devices driven from one
 // thread, or worker threads that default to device 0): hipGetDevice/hipSetDevice are thread-local state in the runtime, a few tens of nanoseconds.
 static inline bool bind_device(lasso_ctx* c) { if (!c) return true; int d = -1; if (hipGetDevice(&d) == hipSuccess && d == c->device) return true; return hipSetDevice(c->device) == hipSuccess; }
-#define REQUIRE(c, cond) do { if (!bind_device(c)) return fail((c), LASSO_ERR_HIP, "hipSetDevice failed for the context's device"); \
+// A public call, from its first REQUIRE to its return (a REQUIRE is a declaration: it needs a block of its own behind an `if` or a `for`).  The outermost scope on a context
+// marks each of the three guarded buffers "not yet requested by this call" (poison_done = 0); a public entry point called from another one, and a second REQUIRE of the same
+// call, change nothing.
+struct EntryScope {
+  lasso_ctx* c;
+  explicit EntryScope(lasso_ctx* c_) : c(c_) { if (c && c->entry_depth++ == 0) for (size_t& d : c->poison_done) d = 0; }
+  ~EntryScope() { if (c) c->entry_depth--; }
+  EntryScope(const EntryScope&) = delete; EntryScope& operator=(const EntryScope&) = delete;
+};
+#define LASSO_CAT2(a, b) a##b
+#define LASSO_CAT(a, b) LASSO_CAT2(a, b)
+#define REQUIRE(c, cond) EntryScope LASSO_CAT(entry_scope_, __LINE__)(c); \
+                         do { if (!bind_device(c)) return fail((c), LASSO_ERR_HIP, "hipSetDevice failed for the context's device"); \
                               if (!(cond)) return fail((c), LASSO_ERR_INVALID, std::string("invalid argument: ") + #cond); } while (0)
 
+// ---- LASSO_POISON=1 (tests; device_switches.cuh POISON_WORD, launch_plan.cuh poison_range): no allocation of the library starts as zeros, and no call finds in the scratch, the
+// sort buffer or the big-result buffer what an earlier call left there.  The word repeated over a range of device memory, on stream `s`:
+static hipError_t poison_device(void* p, const PoisonRange& r, hipStream_t s) {
+  hipError_t e = r.words ? hipMemsetD32Async((hipDeviceptr_t)((uint8_t*)p + r.begin), (int)dsw::POISON_WORD, r.words, s) : hipSuccess;
+  for (size_t at = r.begin + 4 * r.words, i = 0; e == hipSuccess && i < r.tail_bytes; i++) e = hipMemsetAsync((uint8_t*)p + at + i, ((const uint8_t*)&dsw::POISON_WORD)[(at + i) & 3], 1, s);
+  return e;
+}
+// a new allocation, before anybody has its address: the whole of it, on the null stream, and complete on return (the context's stream does not wait for the null stream)
+static hipError_t poison_new(void* p, size_t bytes) {
+  if (!dsw::poison()) return hipSuccess;
+  const PoisonRange r = {0, bytes / 4, bytes & 3};
+  hipError_t e = poison_device(p, r, nullptr);
+  return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
+}
+static void poison_new_host(void* p, size_t bytes) { if (dsw::poison()) dsw::poison_fill_host(p, bytes, dsw::POISON_WORD); }
 // hipMalloc / hipFree with the context's byte accounting (lasso_mem_stats)
 static hipError_t dmalloc(lasso_ctx* c, void** p, size_t bytes) {
   hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess && (e = poison_new(*p, bytes)) != hipSuccess) { (void)hipFree(*p); *p = nullptr; return e; }
   if (e == hipSuccess && c) { std::lock_guard<std::mutex> g(c->mem_mu); c->mem_sizes[*p] = bytes; c->mem_live += bytes; if (c->mem_live > c->mem_peak) c->mem_peak = c->mem_live; }
   return e;
 }
@@ -139,7 +170,18 @@ static int32_t grow_guard(lasso_ctx* c) {
 // pattern directly behind the size it ASKED for, in stream order: a kernel that writes past a hand-summed request damages it although the write stays far inside the buffer's floor.
 // Nothing keeps data in these buffers across calls, and a launch enqueued ahead shares the stream with the round in front of it, so the memset never lands in live data.
 // The mapped result buffers (ensure_small) are left out: they may hold a pending result of another size.
+// LASSO_POISON=1 checks that invariant by the same argument: the FIRST request a public call makes of a buffer fills [0, bytes) with POISON_WORD in stream order, in front of the
+// guard.  A call that asks again (a launch behind the reservation made for it, hyrax_commit_impl's 32 bytes per scalar behind its 4) may have its own data in what it asked for
+// before: such a request fills only what lies beyond that, [done, bytes).  "First" is explicit: lasso_ctx::poison_done, zeroed by the outermost EntryScope of a call and
+// advanced here.  Exempt from the fill, by entry point: none.
 enum { GUARD_SCRATCH = 0, GUARD_PIP = 1, GUARD_BIG = 2 };
+static int32_t poison_request(lasso_ctx* c, int which, void* base, size_t bytes, size_t cap) {
+  if (!dsw::poison() || bytes <= c->poison_done[which]) return 0;
+  const PoisonRange r = poison_range(bytes, cap, dsw::scratch_guard(), c->poison_done[which]);
+  c->poison_done[which] = bytes;
+  HIPCHK(c, poison_device(base, r, c->stream));
+  return 0;
+}
 // the stream is drained: read the guard of the buffer's most recent request back, once
 static void guard_check(lasso_ctx* c, int which) {
   static const char* const names[3] = {"scratch", "sort (k_msm_pip_*)", "big-result"};
@@ -151,7 +193,8 @@ static void guard_check(lasso_ctx* c, int which) {
   if (bad < SCRATCH_GUARD_BYTES && c->guard_err.empty())
     c->guard_err = std::string("LASSO_SCRATCH_GUARD: the ") + names[which] + " buffer was written behind its request of " + std::to_string(g.req) + " bytes: first damaged byte at offset " + std::to_string(g.req + bad);
 }
-static int32_t guard_place(lasso_ctx* c, int which, void* base, size_t bytes) {
+static int32_t guard_place(lasso_ctx* c, int which, void* base, size_t bytes, size_t cap) {
+  if (int32_t p = poison_request(c, which, base, bytes, cap)) return p;
   if (!dsw::scratch_guard()) return 0;
   if (c->guarded[which].base) { if (hipStreamQuery(c->stream) == hipSuccess) guard_check(c, which); else (void)hipGetLastError(); }   // an idle stream: the request before this one can be judged now
   HIPCHK(c, hipMemsetAsync((uint8_t*)base + bytes, SCRATCH_GUARD_BYTE, SCRATCH_GUARD_BYTES, c->stream));
@@ -165,18 +208,18 @@ static int32_t guard_report(lasso_ctx* c) {
   std::string m; m.swap(c->guard_err); return fail(c, LASSO_ERR_INVALID, m);
 }
 static int32_t ensure_scratch(lasso_ctx* c, size_t bytes) {
-  if (bytes <= c->scratch_cap) return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes);
+  if (bytes <= c->scratch_cap) return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes, c->scratch_cap);
   if (int32_t g = grow_guard(c)) return g;
   if (c->d_scratch) { HIPCHK(c, hipStreamSynchronize(c->stream)); guard_check(c, GUARD_SCRATCH); HIPCHK(c, dfree(c, c->d_scratch)); c->d_scratch = nullptr; c->scratch_cap = 0; }
   size_t cap = bytes < ((size_t)1 << 22) ? ((size_t)1 << 22) : bytes;
-  HIPCHK(c, dmalloc(c, &c->d_scratch, guard_alloc_bytes(cap, dsw::scratch_guard()))); c->scratch_cap = cap; return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes);
+  HIPCHK(c, dmalloc(c, &c->d_scratch, guard_alloc_bytes(cap, dsw::scratch_guard()))); c->scratch_cap = cap; return guard_place(c, GUARD_SCRATCH, c->d_scratch, bytes, c->scratch_cap);
 }
 static int32_t ensure_pip(lasso_ctx* c, size_t bytes) {
-  if (bytes <= c->pip_cap) return guard_place(c, GUARD_PIP, c->d_pip, bytes);
+  if (bytes <= c->pip_cap) return guard_place(c, GUARD_PIP, c->d_pip, bytes, c->pip_cap);
   if (!c->proto.may_grow()) return LASSO_ERR_UNSUPPORTED;   // the caller takes the bucket kernel instead
   if (c->d_pip) { HIPCHK(c, hipStreamSynchronize(c->stream)); guard_check(c, GUARD_PIP); HIPCHK(c, dfree(c, c->d_pip)); c->d_pip = nullptr; c->pip_cap = 0; }
   if (dmalloc(c, &c->d_pip, guard_alloc_bytes(bytes, dsw::scratch_guard())) != hipSuccess) { (void)hipGetLastError(); c->d_pip = nullptr; return LASSO_ERR_UNSUPPORTED; }   // no room: not an error, the bucket kernel serves the commitment
-  c->pip_cap = bytes; return guard_place(c, GUARD_PIP, c->d_pip, bytes);
+  c->pip_cap = bytes; return guard_place(c, GUARD_PIP, c->d_pip, bytes, c->pip_cap);
 }
 static int32_t ensure_small(lasso_ctx* c, size_t count) {
   if (count <= c->small_cap) return 0;
@@ -186,16 +229,18 @@ static int32_t ensure_small(lasso_ctx* c, size_t count) {
   c->h_small = nullptr; c->d_small = nullptr; c->small_cap = 0;
   size_t cap = count < 4096 ? 4096 : count;
   HIPCHK(c, hipHostMalloc((void**)&c->h_small, cap * sizeof(fr_t), hipHostMallocMapped | hipHostMallocCoherent));
+  poison_new_host(c->h_small, cap * sizeof(fr_t));
   HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_small, c->h_small, 0));
   if (c->h_tag) (void)hipHostFree(c->h_tag);
   c->h_tag = nullptr; c->d_tag = nullptr;
   HIPCHK(c, hipHostMalloc((void**)&c->h_tag, cap * 48, hipHostMallocMapped | hipHostMallocCoherent));
+  poison_new_host(c->h_tag, cap * 48);
   memset(c->h_tag, 0, cap * 48);
   HIPCHK(c, hipHostGetDevicePointer((void**)&c->d_tag, c->h_tag, 0));
   c->small_cap = cap; return 0;
 }
 static int32_t ensure_big(lasso_ctx* c, size_t count) {
-  if (count <= c->big_cap) return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t));
+  if (count <= c->big_cap) return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t), c->big_cap * sizeof(fr_t));
   if (int32_t g = grow_guard(c)) return g;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   guard_check(c, GUARD_BIG);
@@ -205,7 +250,8 @@ static int32_t ensure_big(lasso_ctx* c, size_t count) {
   size_t cap = count < 8192 ? 8192 : count;
   HIPCHK(c, dmalloc(c, (void**)&c->d_big, guard_alloc_bytes(cap * sizeof(fr_t), dsw::scratch_guard())));
   HIPCHK(c, hipHostMalloc((void**)&c->h_big, cap * sizeof(fr_t), hipHostMallocDefault));
-  c->big_cap = cap; return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t));
+  poison_new_host(c->h_big, cap * sizeof(fr_t));
+  c->big_cap = cap; return guard_place(c, GUARD_BIG, c->d_big, count * sizeof(fr_t), c->big_cap * sizeof(fr_t));
 }
 // profiling: bracket a launch with an event pair on the context's stream
 struct ProfScope {
@@ -224,7 +270,7 @@ struct ProfScope {
   // device counter the MSM kernels add their executed mixed additions to; NULL (no counting, no cost) unless every launch is being bracketed
   uint32_t* counter() {
     if (idx < 0 || idx >= LASSO_PROF_COUNT_SLOTS || (c->prof_mask & 0x40000000u)) return nullptr;
-    if (!c->d_prof_counts) { if (hipMalloc((void**)&c->d_prof_counts, LASSO_PROF_COUNT_SLOTS * 256) != hipSuccess || hipMemset(c->d_prof_counts, 0, LASSO_PROF_COUNT_SLOTS * 256) != hipSuccess) { (void)hipGetLastError(); c->d_prof_counts = nullptr; return nullptr; } }
+    if (!c->d_prof_counts) { if (hipMalloc((void**)&c->d_prof_counts, LASSO_PROF_COUNT_SLOTS * 256) != hipSuccess || poison_new(c->d_prof_counts, LASSO_PROF_COUNT_SLOTS * 256) != hipSuccess || hipMemset(c->d_prof_counts, 0, LASSO_PROF_COUNT_SLOTS * 256) != hipSuccess) { (void)hipGetLastError(); c->d_prof_counts = nullptr; return nullptr; } }
     c->events[idx].counted = true;
     return c->d_prof_counts + (size_t)idx * 64;
   }
@@ -487,9 +533,10 @@ int32_t lasso_ctx_create_background(int32_t device, int32_t background, lasso_ct
   if (e != hipSuccess || (e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, background ? prio_lo : prio_hi)) != hipSuccess) {
     std::string m = hipGetErrorString(e); delete c; return fail(nullptr, LASSO_ERR_HIP, m);
   }
-  if (hipMalloc((void**)&c->d_flags, 64) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "flags alloc"); }
-  if (hipMalloc((void**)&c->d_counters, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess || hipMemset(c->d_counters, 0, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "counters alloc"); }
+  if (hipMalloc((void**)&c->d_flags, 64) != hipSuccess || poison_new(c->d_flags, 64) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "flags alloc"); }
+  if (hipMalloc((void**)&c->d_counters, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess || poison_new(c->d_counters, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess || hipMemset(c->d_counters, 0, (LASSO_MAX_PTRS + 40) * 4) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "counters alloc"); }
   if (hipHostMalloc((void**)&c->h_flag, 256, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer((void**)&c->d_flag, c->h_flag, 0) != hipSuccess) { delete c; return fail(nullptr, LASSO_ERR_OOM, "mapped flag alloc"); }
+  poison_new_host(c->h_flag, 256);
   *c->h_flag = 0;
   c->tagged = dsw::tagged_results();   // A/B switch: the flag protocol for every hand-off
   if (dsw::seq_start() >= 0) c->seq = (uint32_t)dsw::seq_start();   // tests: start close to the end of a sequence epoch (next_seq)
@@ -499,6 +546,7 @@ int32_t lasso_ctx_create_background(int32_t device, int32_t background, lasso_ct
   rc = ensure_scratch(c, (size_t)1 << 22); if (rc) { g_create_err = c->err; delete c; return rc; }
   if (dmalloc(c, (void**)&c->d_gmail, 128) != hipSuccess || hipMemset(c->d_gmail, 0, 128) != hipSuccess) { g_create_err = "gmail alloc"; delete c; return LASSO_ERR_OOM; }
   if (hipHostMalloc((void**)&c->pmail_h, LASSO_PMAIL_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer((void**)&c->pmail_d, c->pmail_h, 0) != hipSuccess) { g_create_err = "point mailbox alloc"; delete c; return LASSO_ERR_OOM; }
+  poison_new_host(c->pmail_h, LASSO_PMAIL_BYTES);
   memset(c->pmail_h, 0, LASSO_PMAIL_BYTES);
   if (dmalloc(c, (void**)&c->d_gpoint, LASSO_GPOINT_BYTES) != hipSuccess || hipMemset(c->d_gpoint, 0, LASSO_GPOINT_BYTES) != hipSuccess) { g_create_err = "gpoint alloc"; delete c; return LASSO_ERR_OOM; }
   { std::lock_guard<std::mutex> g(g_ctx_mu); g_ctx_live.push_back(c); }
@@ -1843,7 +1891,7 @@ int32_t lasso_msm_points_dev(lasso_ctx* c, const lasso_affine* d_points, const l
 // The host form walks the tables strip by strip — upload, one launch over the strip's entries, the strip's sums added on the host — so its scratch does not grow with log_m.
 static int32_t tables_mle_impl(lasso_ctx* c, const char* who, const uint32_t* const* tu32, const lasso_fr* const* tfr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out, bool on_host) {
   REQUIRE(c, point && out && (tu32 != nullptr) != (tfr != nullptr) && num_tables >= 1 && num_tables <= MLE_MAX_TABLES && log_m >= 1 && log_m <= 30);
-  for (uint32_t k = 0; k < num_tables; k++) REQUIRE(c, tu32 ? tu32[k] != nullptr : tfr[k] != nullptr);
+  for (uint32_t k = 0; k < num_tables; k++) { REQUIRE(c, tu32 ? tu32[k] != nullptr : tfr[k] != nullptr); }
   const bool fr = tfr != nullptr; const size_t elem = fr ? sizeof(lasso_fr) : sizeof(uint32_t);
   const uint64_t m = (uint64_t)1 << log_m;
   const uint64_t strip = on_host ? mle_strip_len(num_tables, elem, dsw::mle_strip()) : m, strip_len = strip < m ? strip : m;
@@ -1966,7 +2014,7 @@ int32_t lasso_bullet_round_slab(lasso_ctx* c, const lasso_bases* b, size_t n, ui
                                 lasso_fr* d_b_out, lasso_fr* d_w_out, size_t nk, const lasso_fr* u, const lasso_fr* u_inv, const lasso_fr* blinds, lasso_point* out) {
   REQUIRE(c, b && d_a_in && d_b_in && d_w_in && blinds && out && n >= 2 && (n & (n - 1)) == 0 && nk >= 2 && nk <= n && (nk & (nk - 1)) == 0);
   REQUIRE(c, world >= 1 && (world & (world - 1)) == 0 && rank < world && world <= n && n / world + 2 <= b->n);
-  if (u) REQUIRE(c, u_inv && d_a_out && d_b_out && d_w_out && 2 * nk <= n && d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in);
+  if (u) { REQUIRE(c, u_inv && d_a_out && d_b_out && d_w_out && 2 * nk <= n && d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in); }
   if (!b->d_mult) return fail(c, LASSO_ERR_UNSUPPORTED, "lasso_bullet_round_slab needs the digit-multiple table of the bases (lasso_bases_has_direct)");
   return bullet_round_fused(c, b, n, d_a_in, d_b_in, d_w_in, d_a_out, d_b_out, d_w_out, nk, u, u_inv, blinds, out, world, rank);
 }
@@ -1987,7 +2035,7 @@ int32_t lasso_bullet_round(lasso_ctx* c, const lasso_bases* b, size_t n, const l
                            lasso_fr* d_w_out, size_t nk, const lasso_fr* u, const lasso_fr* u_inv, const lasso_fr* blinds, lasso_point* out) {
   REQUIRE(c, b && d_a_in && d_b_in && d_w_in && blinds && out && n >= 2 && (n & (n - 1)) == 0 && nk >= 2 && nk <= n && (nk & (nk - 1)) == 0 && n + 2 <= b->n);
   const bool fold = u != nullptr;
-  if (fold) REQUIRE(c, u_inv && d_a_out && d_b_out && d_w_out && 2 * nk <= n && d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in);
+  if (fold) { REQUIRE(c, u_inv && d_a_out && d_b_out && d_w_out && 2 * nk <= n && d_a_out != d_a_in && d_b_out != d_b_in && d_w_out != d_w_in); }
   const bool direct = b->d_mult && dsw::msm_direct();
   if (direct && dsw::msm_fused()) return bullet_round_fused(c, b, n, d_a_in, d_b_in, d_w_in, d_a_out, d_b_out, d_w_out, nk, u, u_inv, blinds, out, 1, 0);
   const size_t row = direct ? n / 2 + 2 : n + 2;   // compact rows for k_msm_direct: only the non-zero half

@@ -272,3 +272,25 @@ static inline uint64_t mle_strip_len(uint32_t num_tables, size_t elem_bytes, lon
 static inline size_t guard_alloc_bytes(size_t cap, bool guard) { return guard ? cap + SCRATCH_GUARD_BYTES : cap; }
 // the first byte of a guard read back that no longer holds the pattern, or SCRATCH_GUARD_BYTES: intact
 static inline size_t guard_first_damage(const uint8_t* g) { size_t i = 0; while (i < SCRATCH_GUARD_BYTES && g[i] == SCRATCH_GUARD_BYTE) i++; return i; }
+
+// ------------------------------------------------------------------ the fill in front of a call's own data (LASSO_POISON, tests; device_switches.cuh POISON_WORD)
+// A request a public call makes of the scratch, the sort buffer or the big-result buffer fills what it ASKED for and this call has not asked for before, [done, req), with the
+// word in stream order: whatever the call reads from there it must have stored itself.  done = 0 at the call's first request of the buffer (all of [0, req) is filled); a later
+// request of the same call leaves [0, done) alone — the call's own data may live there — and fills only what lies beyond (hyrax_commit_impl asks for 4 bytes per scalar first
+// and for 32 when a scalar turns out wide).  The fill is issued as whole 32-bit words plus a tail of single bytes, every byte the one its position in the repeated word gives it.
+// It starts at the first word boundary at or behind `done` (the bytes in front of it went out with the word that held the earlier request's last byte), and the word that
+// holds this request's last bytes is written whole where it still lies inside the allocation (cap bytes, SCRATCH_GUARD_BYTES more with the guard on: guard_place then puts the
+// guard over its last 1..3 bytes); where it does not — a request of an odd size that is the capacity itself, guard off — the tail goes out as bytes.  A request above the
+// capacity fills nothing: the buffer grows first, and dmalloc has filled the new allocation.
+struct PoisonRange { size_t begin, words, tail_bytes; };   // [begin, begin + 4 * words) as words, then tail_bytes (0..3) single bytes
+static inline PoisonRange poison_range(size_t req, size_t cap, bool guard, size_t done) {
+  PoisonRange r = {0, 0, 0};
+  if (req > cap || req <= done) return r;
+  const size_t alloc = guard_alloc_bytes(cap, guard), whole = (req + 3) & ~(size_t)3;
+  r.begin = (done + 3) & ~(size_t)3;
+  if (r.begin > alloc) { r.begin = done; r.tail_bytes = req - done; return r; }   // both requests end in the allocation's last, partial word: its remaining bytes one by one
+  if (r.begin >= req) { r.begin = 0; return r; }                                 // ... in a word the earlier request's fill wrote whole
+  if (whole <= alloc) r.words = (whole - r.begin) / 4;
+  else { r.words = ((req & ~(size_t)3) - r.begin) / 4; r.tail_bytes = req & 3; }
+  return r;
+}

@@ -8,6 +8,7 @@
 // Each function restates the reference loop it stands for, serially, exactly as cited in lasso_hip.h.
 #include "lasso_oracle.hpp"
 #include "../include/lasso_hip.h"
+#include "../lasso_amd/csrc/device_switches.cuh"   // LASSO_POISON and its word: the one switch of the device library the mock shares
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -67,6 +68,7 @@ void* lasso_stream(lasso_ctx*) { return nullptr; }
 // can be checked on the CPU: per context live / peak bytes, and the number of lasso_alloc calls (mock_alloc_calls: a steady state of repeated proofs must make none)
 int32_t lasso_alloc(lasso_ctx* c, size_t bytes, void** d) {
   REQ(c, d); *d = malloc(bytes ? bytes : 1); if (!*d) return LASSO_ERR_OOM;
+  if (lasso::dsw::poison()) lasso::dsw::poison_fill_host(*d, bytes ? bytes : 1, lasso::dsw::POISON_WORD);   // tests: as the device library's dmalloc, so that the host prover runs over non-zero allocations on the CPU
   std::lock_guard<std::mutex> g(c->mem_mu); c->mem_sizes[*d] = bytes ? bytes : 1; c->mem_live += bytes ? bytes : 1; if (c->mem_live > c->mem_peak) c->mem_peak = c->mem_live; c->alloc_calls++;
   return 0;
 }

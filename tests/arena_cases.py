@@ -16,8 +16,12 @@ Groups (the prefix of a case's name; `-k` selects them):
 On the device every child runs with LASSO_SCRATCH_GUARD=1 (tests/test_gpu_write_contract.py): the library puts a guard of 64 KiB directly behind the REQUESTED size of every request
 of its scratch, sort and big-result buffers, and the lasso_sync before the audit fails the case that damaged one.
 
-NOT covered (tests/arenautil.py): the generator tables, the mapped result buffers and every other allocation the library owns outside those three buffers, stray reads, a stray
-write of the pattern's own bytes, the collectives of slab mode."""
+They also run with LASSO_POISON=1: every allocation of the library (scratch, sort and big-result buffers, generator tables, mapped result buffers, lasso_alloc) starts as the
+word 0x00000001 repeated, and the first request a call makes of one of the three buffers fills the requested range with it, so a kernel that reads what this call did not store
+fails the case's own parity assertion.  The last two test_sens_ cases show that the switch is live in the child.
+
+NOT covered (tests/arenautil.py): stray writes into the generator tables, the mapped result buffers and every other allocation the library owns outside those three buffers,
+stray reads that do not change a result, a stray write of the pattern's own bytes, the collectives of slab mode."""
 import inspect
 import os
 
@@ -335,3 +339,62 @@ def test_sens_densify_contract_shrunk_by_one_element(devs):
     lo = _off(arena, outs[3]) + 32 * (m - 1)
     text = _expect_one(arena, lo, "in buffer #4 (fr,", planted=False)
     assert "lasso_densify_dim" in text
+
+
+# ---- LASSO_POISON (device only: the children of tests/test_gpu_write_contract.py set it): the switch is live in this process.  Every case above then ran with the library's own
+# allocations, and the requested range of each call's first scratch / sort / big-result request, holding the fill word instead of zeros or an earlier call's bytes.
+
+POISON_WORD = 0x00000001      # lasso_amd/csrc/device_switches.cuh POISON_WORD
+
+
+def _raw_alloc_bytes(arena, nbytes):
+    """a lasso_alloc of the library's own (not the arena's bump allocation), read back before anything is written to it"""
+    import ctypes as C
+    p = C.c_void_p()
+    assert arena.raw.lasso_alloc(arena.ctx, nbytes, C.byref(p)) == 0 and p.value
+    try:
+        out = np.empty(nbytes, dtype=np.uint8)
+        assert arena.raw.lasso_download(arena.ctx, out.ctypes.data_as(C.c_void_p), p, nbytes) == 0
+    finally:
+        arena.raw.lasso_free(arena.ctx, p)
+    return out
+
+
+def _assert_fill(got):
+    want = np.zeros(len(got), dtype=np.uint8); want[::4] = POISON_WORD      # little-endian 0x00000001 repeated; an odd tail gets the word's first bytes
+    bad = np.flatnonzero(got != want)
+    assert len(bad) == 0, f"{len(bad)} of {len(got)} bytes of a fresh lasso_alloc do not hold the fill word, the first at offset {bad[0]}: {got[bad[0] & ~3:(bad[0] & ~3) + 8]}"
+
+
+def _live_bytes(arena):
+    import ctypes as C
+    live, peak = C.c_uint64(), C.c_uint64()
+    assert arena.raw.lasso_mem_stats(arena.ctx, C.byref(live), C.byref(peak), 0) == 0
+    return live.value
+
+
+if not OVER_MOCK:
+    def test_sens_fresh_allocation_holds_the_fill_word(devs):
+        assert os.environ.get("LASSO_POISON") == "1", "the child runs without LASSO_POISON=1"
+        for nbytes in (4096, 8192, 6001, 1):
+            _assert_fill(_raw_alloc_bytes(devs[0], nbytes))
+
+    def test_sens_zz_allocation_after_growth_and_trim_holds_the_fill_word(devs):
+        """the last case of its child: after the cases above, and after this one has grown the scratch beyond its floor with live data, trimmed it and grown it again, an
+        allocation of the size just freed (what the allocator hands back first) and small ones hold the fill word, not what the scratch held"""
+        arena = devs[0]
+        assert os.environ.get("LASSO_POISON") == "1", "the child runs without LASSO_POISON=1"
+        n = 1 << 18
+        src = arena.upload(rand_fr(np.random.default_rng(18), n))
+        arena.sync()
+        assert arena.raw.lasso_trim(arena.ctx) == 0      # the scratch at its floor, whatever the cases before left
+        live0 = _live_bytes(arena)
+        for rep in range(2):
+            arena.fr_to_bytes(src, n)      # 8 MiB of scratch: twice its floor
+            arena.sync()
+            grown = _live_bytes(arena)
+            assert grown >= live0 + (4 << 20), (live0, grown)
+            assert arena.raw.lasso_trim(arena.ctx) == 0
+            assert _live_bytes(arena) <= grown - (4 << 20)
+            for nbytes in (8 << 20, 4096, 8192 + 2):
+                _assert_fill(_raw_alloc_bytes(arena, nbytes))

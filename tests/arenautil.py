@@ -12,8 +12,13 @@ The same classes run over the oracle's mock, whose device memory is host memory 
 The library's own scratch, sort and big-result buffers are held by the library itself: under LASSO_SCRATCH_GUARD=1 (lasso_amd/csrc/device_switches.cuh) each request has a guard of
 64 KiB directly behind its requested size and lasso_sync reports a damaged one, which is why a case ends with sync() before audit().
 
-NOT covered: the generator tables, the mapped result buffers and every other allocation the library owns outside those three buffers; stray READS; a stray write that happens
-to store the pattern's own bytes at that position; the collectives of slab mode."""
+What those buffers and every other allocation of the library hold BEFORE a call is varied by LASSO_POISON=1 (the same table): each new allocation — scratch, sort and
+big-result buffers, generator tables, term lists, mapped result buffers, lasso_alloc — starts as the 32-bit word 0x00000001 repeated, and the first request a public call makes
+of one of the three buffers fills its requested range with the word in stream order.  A kernel that reads a partial, a bucket or a table entry this call did not store then
+computes with the word, not with zeros or with what an identical call left there, and the case's own parity assertion fails.
+
+NOT covered: stray WRITES into the generator tables, the mapped result buffers and every other allocation the library owns outside those three buffers; stray READS that do not
+change a result (of the word, or of caller memory); a stray write that happens to store the pattern's own bytes at that position; the collectives of slab mode."""
 import ctypes as C
 
 import numpy as np

@@ -241,6 +241,60 @@ int main() {
     for (size_t at : {(size_t)0, (size_t)1, (size_t)4095, SCRATCH_GUARD_BYTES - 1}) { g[at] ^= 1; CHECK(guard_first_damage(g) == at); g[at] ^= 1; }
     g[7] = 0; g[9] = 0; CHECK(guard_first_damage(g) == 7);
   }
+  // LASSO_POISON: default off; the word; the host fill (whole words, then the word's first bytes in memory order); which range a request fills
+  CHECK(!lasso::dsw::poison());   // the test runs without the variable
+  CHECK(lasso::dsw::POISON_WORD == 1u);   // non-zero as a value, a counter and a flag; as an index inside any table of two or more entries
+  {
+    alignas(4) uint8_t m[24];
+    for (size_t bytes = 0; bytes <= 19; bytes++) {
+      memset(m, 0xEE, sizeof(m)); lasso::dsw::poison_fill_host(m, bytes, lasso::dsw::POISON_WORD);
+      for (size_t i = 0; i < sizeof(m); i++) CHECK(m[i] == (i >= bytes ? 0xEE : (i & 3) == 0 ? 1 : 0));
+    }
+    memset(m, 0xEE, sizeof(m)); lasso::dsw::poison_fill_host(m, 7, 0x04030201u);
+    for (size_t i = 0; i < 7; i++) CHECK(m[i] == 1 + (i & 3)); CHECK(m[7] == 0xEE);
+  }
+  {
+    const size_t cap = (size_t)1 << 22;
+    for (int guard = 0; guard < 2; guard++) {
+      // inside the capacity: the word that holds the request's last bytes is written whole, nothing beyond it
+      for (size_t req : {(size_t)0, (size_t)1, (size_t)3, (size_t)4, (size_t)5, (size_t)129 * 7, (size_t)98 * 3, cap - 5, cap - 4, cap - 3, cap}) {
+        const PoisonRange r = poison_range(req, cap, guard != 0, 0);
+        CHECK(r.begin == 0 && r.tail_bytes == 0 && r.words == (req + 3) / 4 && 4 * r.words >= req && 4 * r.words < req + 4 && 4 * r.words <= cap);
+      }
+      // above the capacity: nothing (the buffer grows first, and its new allocation is filled as a whole)
+      for (size_t req : {cap + 1, cap + 4, 2 * cap}) { const PoisonRange r = poison_range(req, cap, guard != 0, 0); CHECK(r.words == 0 && r.tail_bytes == 0); }
+    }
+    // a capacity of an odd size asked for whole (the scratch grows to exactly the request above its floor: 129 n and 98 n bytes): without the guard's room behind it the last
+    // 1..3 bytes go out as bytes, with it as one more word, which the guard then overwrites
+    for (size_t odd : {((size_t)1 << 22) + 1, ((size_t)1 << 22) + 2, ((size_t)1 << 22) + 3, (size_t)129 * 40001, (size_t)98 * 50001}) {
+      const PoisonRange a = poison_range(odd, odd, false, 0), b = poison_range(odd, odd, true, 0);
+      CHECK(a.words == odd / 4 && a.tail_bytes == (odd & 3) && 4 * a.words + a.tail_bytes == odd);
+      CHECK(b.tail_bytes == 0 && b.words == (odd + 3) / 4 && 4 * b.words <= guard_alloc_bytes(odd, true) && 4 * b.words - odd < SCRATCH_GUARD_BYTES);
+      const PoisonRange below = poison_range(odd - 4, odd, false, 0);   // ... and a request whose last word ends inside that capacity keeps the whole word
+      CHECK(below.tail_bytes == 0 && 4 * below.words == ((odd - 4 + 3) & ~(size_t)3) && 4 * below.words <= odd);
+    }
+    // a later request of the same call (done > 0): nothing in front of `done` is touched, everything from the first word boundary at or behind it to the request's end is filled
+    // (the bytes between `done` and that boundary went out with the earlier request's last word), and a request that is not larger fills nothing
+    {
+      const PoisonRange same = poison_range(4096, cap, false, 4096), smaller = poison_range(100, cap, true, 4096); CHECK(same.words == 0 && same.tail_bytes == 0 && smaller.words == 0 && smaller.tail_bytes == 0);
+      const PoisonRange r = poison_range((size_t)32 * 1000 + 7, cap, false, (size_t)4 * 1000 + 256 + 3);   // 4 bytes per scalar, then 32: hyrax_commit_impl's two requests
+      CHECK(r.begin == 4260 && r.tail_bytes == 0 && r.begin + 4 * r.words == 32008);
+      const PoisonRange within = poison_range(4099, cap, false, 4097); CHECK(within.words == 0 && within.tail_bytes == 0);   // inside the word the earlier fill wrote whole
+    }
+    for (size_t c2 : {(size_t)8, (size_t)9, (size_t)10, (size_t)11, (size_t)131}) for (size_t done = 0; done <= c2; done++) for (size_t req = 0; req <= c2; req++) for (int guard = 0; guard < 2; guard++) {
+      const size_t alloc = guard_alloc_bytes(c2, guard != 0);
+      const PoisonRange first = poison_range(done, c2, guard != 0, 0), r = poison_range(req, c2, guard != 0, done);
+      const size_t covered = done ? first.begin + 4 * first.words + first.tail_bytes : 0, end = r.begin + 4 * r.words + r.tail_bytes;   // where the earlier request's fill ended
+      if (req <= done) { CHECK(r.words == 0 && r.tail_bytes == 0); continue; }
+      if (r.words == 0 && r.tail_bytes == 0) { CHECK(covered >= req); continue; }       // nothing to do: the earlier fill reached past this request
+      CHECK(r.begin >= done && r.begin <= covered && (r.words == 0 || r.begin % 4 == 0) && r.tail_bytes < 4 && end >= req && end <= alloc && (r.tail_bytes == 0 || end == req));
+    }
+    // every filled byte lies inside the allocation, and every requested byte is filled
+    for (size_t c2 : {(size_t)1, (size_t)2, (size_t)7, (size_t)8, (size_t)4097}) for (size_t req = 0; req <= c2; req++) for (int guard = 0; guard < 2; guard++) {
+      const PoisonRange r = poison_range(req, c2, guard != 0, 0);
+      CHECK(r.tail_bytes < 4 && 4 * r.words + r.tail_bytes >= req && 4 * r.words + r.tail_bytes <= guard_alloc_bytes(c2, guard != 0) && (r.tail_bytes == 0 || 4 * r.words + r.tail_bytes == req));
+    }
+  }
   printf("OK %ld checks\n", checks);
   return 0;
 }

@@ -14,7 +14,7 @@ def load_mock():
     from lasso_amd import _abi
     name = "libmock_hip_bn254.so" if CURVE == "bn254" else "libmock_hip.so"
     so = os.path.join(ROOT, "oracle", name)
-    srcs = [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")] + [os.path.join(ROOT, "include", "lasso_hip.h")]
+    srcs = [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")] + [os.path.join(ROOT, "include", "lasso_hip.h"), os.path.join(ROOT, "lasso_amd", "csrc", "device_switches.cuh")]
     if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), name])
     lib = ctypes.CDLL(so)

@@ -147,3 +147,8 @@ def test_gpu_bn254_pass_variants():
 def test_gpu_bn254_write_contract():
     """tests/test_gpu_write_contract.py on the BN254 build: every child of it (the arena cases of tests/arena_cases.py by group and switch setting) inherits LASSO_TEST_CURVE."""
     _rerun_on_bn254("test_gpu_write_contract.py", timeout=1800)
+
+
+def test_gpu_bn254_stale_memory():
+    """tests/test_gpu_stale_memory.py on the BN254 build: the BN254 proofs above and the verifier and set-up modules under LASSO_POISON=1 (its children inherit LASSO_TEST_CURVE)."""
+    _rerun_on_bn254("test_gpu_stale_memory.py", timeout=900)

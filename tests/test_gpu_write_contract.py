@@ -7,10 +7,17 @@ Every child runs with LASSO_SCRATCH_GUARD=1: the library puts 64 KiB of guard pa
 buffers, and the lasso_sync that ends each case (tests/arena_cases.py arena_case) fails the case that damaged one.  A child that does not finish in its time limit, or is ended
 by a signal, is the last one started: the tests after it fail at once.
 
-Measured on an MI355X, per build: 814 cases in 22 children, 131 s for the module; the longest child is the curve group (73 cases, 38 s: the commitments' reference runs on the
-mock), then LASSO_REDUCE_NX=3 (77 rows, 18 s) and the round group (120 cases, 14 s); every other child takes 2 to 8 s.  Cases per group: sensitivity 11, kernels 184 + 73 + 120,
-field edges 66 + 77, operands 65, MSM over caller points 22, wire points 8, candidates 8, table rows 60 / 5 / 8 / 4 / 77 / 8 / 7 / 1 / 1 / 9 in the order of SETTINGS.  No stray
-write and no damaged guard was found on either build."""
+Every child also runs with LASSO_POISON=1: each allocation of the library starts as the word 0x00000001 repeated, and the first request a public call makes of the scratch, sort
+or big-result buffer fills its requested range with the word in stream order (in front of the guard).  A case whose kernels read a partial, a bucket sum or a table entry that
+the call did not store then computes with the word instead of with zeros or with what the identical call before it left there, and fails its own parity assertion; nothing else
+is asserted for it.  The last two sensitivity cases read fresh lasso_alloc memory back and require the word everywhere, the second after the scratch has grown beyond its floor
+with live data and been trimmed, twice.
+
+Measured on an MI355X with both switches on: 816 cases in 22 children, 131 to 134 s for the module on the curve25519 build and 116 to 122 s on the BN254 build (131 s before the fill
+was added: the memsets do not show); the longest child is the curve group (73 cases, 38 s / 33 s: the commitments' reference runs on the mock), then LASSO_REDUCE_NX=3 (77 rows,
+19 s) and the round group (120 cases, 14 s); every other child takes 2 to 9 s.  Cases per group: sensitivity 13, kernels 184 + 73 + 120, field edges 66 + 77, operands 65, MSM
+over caller points 22, wire points 8, candidates 8, table rows 60 / 5 / 8 / 4 / 77 / 8 / 7 / 1 / 1 / 9 in the order of SETTINGS.  No stray write, no damaged guard and no
+stale read was found on either build."""
 import os
 import re
 import subprocess
@@ -52,10 +59,11 @@ MAY_BE_EMPTY = ("kernels_rest", "field_edges_rest")
 
 def run_child(select, setting, timeout):
     """tests/arena_cases.py -k `select` on the device, in a fresh process under SETTINGS[setting] -> the number of cases that passed"""
-    env = {k: v for k, v in os.environ.items() if k not in RV.SWITCHES + PV.SWITCHES and not k.startswith("LASSO_MSM_") and k != "LASSO_ARENA_OVER"}
+    env = {k: v for k, v in os.environ.items() if k not in RV.SWITCHES + PV.SWITCHES and not k.startswith("LASSO_MSM_") and k not in ("LASSO_ARENA_OVER", "LASSO_POISON")}
     env.update(SETTINGS[setting])
     env["LASSO_ARENA_SETTING"] = str(setting)
     env["LASSO_SCRATCH_GUARD"] = "1"      # the library's own buffers: a guard behind every request's size, reported by the lasso_sync that ends each case
+    env["LASSO_POISON"] = "1"             # ... and in front of every call's own data the fill word, not zeros or an earlier call's bytes: a stale read fails the case's parity
     if _STOPPED:
         pytest.fail(f"not started: {_STOPPED[0]}")
     t0 = time.perf_counter()
