@@ -209,3 +209,15 @@ def declare_mle(lib):
 
 
 HEADER_SYMBOLS = None
+
+
+VALUES_FR, VALUES_U64 = 0, 1   # include/lasso_hip_values.h lasso_values_form
+
+
+def declare_values(lib):
+    """include/lasso_hip_values.h — the lookup results as a vector.  Declared apart from declare(), as declare_mle is: an implementation of lasso_hip.h alone does not
+    have it.  AttributeError = the library does not export it."""
+    fn = lib.lasso_lookup_values
+    fn.restype = i32
+    fn.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_size_t, i32, vp]
+    return ["lasso_lookup_values"]

@@ -18,6 +18,7 @@ LASSO_DSWITCH(bool, msm_tagged, unless0(getenv("LASSO_MSM_TAGGED")))           /
 // ---- the sumcheck rounds
 LASSO_DSWITCH(long, cubic_nx, [] { const char* e = getenv("LASSO_CUBIC_NX"); return e ? atol(e) : 0L; }())   // 0 (unset or <= 0): about 512 workgroups over the whole grid; > 0: the x-extent cap of the round grids itself (experiments)
 LASSO_DSWITCH(long, reduce_nx, [] { const char* e = getenv("LASSO_REDUCE_NX"); return e ? atol(e) : 0L; }())   // 0 (unset or <= 0): each launch's own cap; > 0: the x-extent cap of the reduction launches outside the round grids (combine rounds and claims, multi_dot, inner_products_lr; tests)
+LASSO_DSWITCH(long, values_nx, [] { const char* e = getenv("LASSO_VALUES_NX"); return e ? atol(e) : 0L; }())   // 0 (unset or <= 0): up to 4096 workgroups; > 0: the x-extent cap of lasso_lookup_values' launch (tests: several grid-stride passes per lane on small arrays)
 LASSO_DSWITCH(bool, cubic_wide,unless0(getenv("LASSO_CUBIC_WIDE")))           // on; double-width accumulators in the two-sum fused round
 LASSO_DSWITCH(unsigned, direct_nx, [] { const char* e = getenv("LASSO_DIRECT_NX"); const long x = e ? atol(e) : 16; return (unsigned)(x < 0 ? 0 : x > 64 ? 64 : x); }())   // 16, 0..64; launches of up to this many workgroups per circuit hand over every workgroup's block sums (0: never)
 LASSO_DSWITCH(bool, eq_inline_big, if1(getenv("LASSO_EQ_INLINE_BIG")))         // off; eq tables above 2^14 entries formed inside round 0 (EqGlobal) instead of by k_eq_outer in front of it

@@ -25,6 +25,8 @@
 #include "gens_kernels.cuh"
 #include "../../include/lasso_hip_mle.h"
 #include "mle_kernels.cuh"
+#include "../../include/lasso_hip_values.h"
+#include "values_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -1947,6 +1949,69 @@ int32_t lasso_tables_mle(lasso_ctx* c, const uint32_t* const* tables_u32, const 
 }
 int32_t lasso_tables_mle_dev(lasso_ctx* c, const uint32_t* const* d_tables_u32, const lasso_fr* const* d_tables_fr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out) {
   return tables_mle_impl(c, "lasso_tables_mle_dev", d_tables_u32, d_tables_fr, num_tables, log_m, point, out, false);
+}
+// include/lasso_hip_values.h: the lookup results as a vector (values_kernels.cuh).  Every rule is checked, and a caller-defined term list staged, before the one launch.
+static int32_t values_fail(lasso_ctx* c, int32_t code, const char* why) { return fail(c, code, std::string("lasso_lookup_values: ") + why); }
+int32_t lasso_lookup_values(lasso_ctx* c, const lasso_strategy* s, const uint32_t* const* d_dim, const uint32_t* const* d_tables_u32, const lasso_fr* const* d_tables_fr, size_t n, int32_t form, void* d_out) {
+  REQUIRE(c, s && d_dim && d_out);
+  if (form != LASSO_VALUES_FR && form != LASSO_VALUES_U64) return values_fail(c, LASSO_ERR_INVALID, "form is neither LASSO_VALUES_FR nor LASSO_VALUES_U64");
+  if ((d_tables_u32 != nullptr) == (d_tables_fr != nullptr)) return values_fail(c, LASSO_ERR_INVALID, "exactly one of d_tables_u32 / d_tables_fr must be given");
+  if ((uintptr_t)d_out & 15u) return values_fail(c, LASSO_ERR_INVALID, "d_out must be 16-byte aligned");
+  const int32_t kind = s->kind; const bool custom = kind == LASSO_CUSTOM, spark = kind == LASSO_SPARK_UNCONFIRMED, lt = kind == LASSO_LT, ints = d_tables_u32 != nullptr;
+  if (kind < LASSO_AND || kind > LASSO_CUSTOM) return values_fail(c, LASSO_ERR_INVALID, "unknown strategy kind");
+  const lasso_strategy_custom* cs = custom ? (const lasso_strategy_custom*)s : nullptr;
+  if (custom) { if (const char* why = custom_strategy_check(cs, 0)) return fail(c, LASSO_ERR_INVALID, why); }
+  else if (s->log_m < 1 || s->log_m > 32) return values_fail(c, LASSO_ERR_INVALID, "log_m must be in 1..32");
+  const uint32_t C = s->c, alpha = custom ? cs->num_memories : lt ? 2 * C : C, nsub = custom ? cs->num_subtables : lt ? 2u : kind == LASSO_RANGE ? 3u : spark ? C : 1u;
+  if (C < 1 || C > LASSO_MAX_ALPHA || alpha > LASSO_MAX_ALPHA) return values_fail(c, LASSO_ERR_INVALID, "c must be at least 1 and NUM_MEMORIES at most 32 (LASSO_MAX_ALPHA)");
+  const uint32_t inc = values_inc(kind, s->log_m);
+  if (values_kind_linear(kind) && (uint64_t)(C - 1) * inc >= 64) return values_fail(c, LASSO_ERR_INVALID, "the weights 2^(i * inc) need (C - 1) * inc below 64");
+  if (!custom && ints == spark) return values_fail(c, LASSO_ERR_INVALID, spark ? "Spark's subtables hold field elements: d_tables_fr" : "this kind's subtables hold integers: d_tables_u32");
+  if (form == LASSO_VALUES_U64 && (custom || spark || !ints || !values_u64_offered(kind, C, s->log_m))) return values_fail(c, LASSO_ERR_UNSUPPORTED, VALUES_MSG_U64);
+  for (uint32_t i = 0; i < C; i++) if (!d_dim[i] || ((uintptr_t)d_dim[i] & 7u)) return values_fail(c, LASSO_ERR_INVALID, "an address column is null or not 8-byte aligned");
+  for (uint32_t k = 0; k < nsub; k++) if (ints ? !d_tables_u32[k] : !d_tables_fr[k]) return values_fail(c, LASSO_ERR_INVALID, "a table pointer is null");
+  if (!n) return 0;
+  ValuesMems M;
+  for (uint32_t i = 0; i < LASSO_MAX_ALPHA; i++) { M.dim[i] = nullptr; M.tab[i] = nullptr; M.shift[i] = 0; }
+  for (uint32_t i = 0; i < alpha; i++) {
+    uint32_t sub, dim;
+    if (custom) { sub = cs->memory_subtable ? cs->memory_subtable[i] : i % nsub; dim = cs->memory_dimension ? cs->memory_dimension[i] : i / nsub; }
+    else if (kind == LASSO_RANGE) { sub = (uint64_t)i * s->log_m > s->log_r ? 2u : (uint64_t)(i + 1) * s->log_m > s->log_r ? 1u : 0u; dim = i; }   // range_check.rs:62-73
+    else { sub = i % nsub; dim = spark ? i : i / nsub; }                                                                                          // subtables/mod.rs:64-74
+    M.dim[i] = d_dim[dim]; M.tab[i] = ints ? (const void*)d_tables_u32[sub] : (const void*)d_tables_fr[sub];
+    M.shift[i] = values_kind_linear(kind) ? (uint8_t)(i * inc) : 0;
+  }
+  const uint32_t mask = s->log_m >= 32 ? 0xffffffffu : (((uint32_t)1 << s->log_m) - 1);
+  const bool terms = custom || spark; uint32_t nt = 0, nf = 0;
+  if (terms) {
+    uint32_t Q = 1; int32_t rc;
+    if (custom) { rc = pack_custom_terms(c, cs, Q); nt = cs->num_terms; nf = cs->term_start[cs->num_terms]; }
+    else {   // Spark: g = prod_i v_i is the list of one term with C factors and coefficient 1
+      uint32_t start[2] = {0, C}, mem[LASSO_MAX_ALPHA]; for (uint32_t i = 0; i < C; i++) mem[i] = i;
+      const fr_t one = fr_one(); lasso_fr cf; memcpy(&cf, one.v, sizeof cf);
+      lasso_strategy_custom sp; memset(&sp, 0, sizeof sp);
+      sp.base = *s; sp.base.kind = LASSO_CUSTOM; sp.num_subtables = C; sp.num_memories = C; sp.num_terms = 1; sp.coeff = &cf; sp.term_start = start; sp.term_mem = mem;
+      if (C > LASSO_CUSTOM_MAX_DEGREE - 1) return values_fail(c, LASSO_ERR_INVALID, "Spark: c must be at most 16");
+      rc = pack_custom_terms(c, &sp, Q); nt = 1; nf = C;
+    }
+    if (rc) return rc;
+  }
+  const ValuesPlan P = values_plan(n, !terms, dsw::values_nx());
+  {
+    ProfScope ps(c, LASSO_K_MISC, (4.0 * C + (form == LASSO_VALUES_U64 ? 8.0 : 32.0)) * n);   // addresses in, values out; the table gathers are L2 traffic (values_kernels.cuh)
+    const dim3 grid(P.nx), block(LASSO_BLOCK);
+    if (terms) {
+      if (ints) hipLaunchKernelGGL((k_lookup_values_terms<false>), grid, block, 0, c->stream, M, mask, (const CustomTermsDev*)c->d_terms, nt, nf, n, (fr_t*)d_out);
+      else hipLaunchKernelGGL((k_lookup_values_terms<true>), grid, block, 0, c->stream, M, mask, (const CustomTermsDev*)c->d_terms, nt, nf, n, (fr_t*)d_out);
+    } else if (lt) {
+      if (form == LASSO_VALUES_U64) hipLaunchKernelGGL((k_lookup_values_int<true, true>), grid, block, 0, c->stream, M, alpha, mask, n, d_out);
+      else hipLaunchKernelGGL((k_lookup_values_int<true, false>), grid, block, 0, c->stream, M, alpha, mask, n, d_out);
+    } else {
+      if (form == LASSO_VALUES_U64) hipLaunchKernelGGL((k_lookup_values_int<false, true>), grid, block, 0, c->stream, M, alpha, mask, n, d_out);
+      else hipLaunchKernelGGL((k_lookup_values_int<false, false>), grid, block, 0, c->stream, M, alpha, mask, n, d_out);
+    }
+  }
+  HIPCHK(c, hipGetLastError()); return 0;
 }
 __global__ void __launch_bounds__(256) k_scale_to_integers(const fr_t* __restrict__ src, size_t n, fr_t scale, fr_t t0, fr_t t1, fr_t* __restrict__ dst) {
   const fr29 ss = fr29_unpack_s(scale); fr29 k32 = fr29_zero(); k32.v[0] = 32;

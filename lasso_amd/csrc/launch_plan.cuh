@@ -263,6 +263,22 @@ static inline uint64_t mle_strip_len(uint32_t num_tables, size_t elem_bytes, lon
   uint64_t n = MLE_STRIP_BYTES / ((size_t)num_tables * elem_bytes); n &= ~(uint64_t)255; return n < 256 ? 256 : n;
 }
 
+// ------------------------------------------------------------------ the lookup values (lasso_lookup_values, values_kernels.cuh)
+// A lane's item is TWO consecutive lookups in the integer kernels (`pair`: one 16-byte store in the 64-bit form, an odd n leaves the last item with one lookup) and one
+// lookup in the term-list kernel.  Lanes walk the items grid-stride; VALUES_MAX_NX workgroups are 16 per compute unit, above that a lane takes several passes.
+// values_nx_sw = LASSO_VALUES_NX (tests: a few workgroups bring several passes per lane within reach of small arrays).
+#define VALUES_MAX_NX 4096u
+struct ValuesPlan { uint32_t per_item; uint64_t items; unsigned nx; uint64_t passes, last_block_items; };
+static inline ValuesPlan values_plan(size_t n, bool pair, long values_nx_sw) {
+  ValuesPlan p; p.per_item = pair ? 2u : 1u;
+  p.items = pair ? ((uint64_t)n + 1) / 2 : (uint64_t)n;
+  p.nx = grid_for((size_t)p.items, values_nx_sw > 0 ? (unsigned)values_nx_sw : VALUES_MAX_NX);
+  const uint64_t stride = (uint64_t)p.nx * LASSO_BLOCK;
+  p.passes = (p.items + stride - 1) / stride;                      // of the busiest lane (lane 0 of workgroup 0)
+  p.last_block_items = p.items % LASSO_BLOCK;                      // non-zero: the last tile of 256 items is ragged
+  return p;
+}
+
 // ------------------------------------------------------------------ the guard behind the context's own buffers (LASSO_SCRATCH_GUARD, tests)
 // Every request of the scratch, the sort buffer of the 12-bit-window kernels and the big-result buffer names its size as a hand-written sum of sub-buffers, and the buffers'
 // floors (4 MiB of scratch) hide a sum that is too small at every shape a test runs.  With the switch on a buffer of capacity `cap` is allocated with SCRATCH_GUARD_BYTES more,

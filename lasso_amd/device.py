@@ -424,6 +424,20 @@ class Device:
         self._chk(fn(self.ctx, None if field else ptrs, ptrs if field else None, len(d_tables), point.shape[0], _vp(point), _vp(out)))
         return out
 
+    def lookup_values(self, strategy, d_dims, d_tables, field_tables, n, form, d_out):
+        """d_out[k] = combine_lookups of lookup k < n (include/lasso_hip_values.h lasso_lookup_values), enqueued on the context's stream: `strategy` = a pointer as
+        lasso_amd.custom.strategy_ptr makes it, `d_dims` = c device pointers to n addresses each, `d_tables` = the subtables' device pointers (`field_tables`: field
+        elements instead of 32-bit integers), `form` = _abi.VALUES_FR / _abi.VALUES_U64, `d_out` = a device pointer to n elements.  A library without the entry point is
+        an error, not a fall-back."""
+        if not hasattr(self, "_values_ok"):
+            try:
+                _abi.declare_values(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_lookup_values (include/lasso_hip_values.h)")
+            self._values_ok = True
+        dims, tabs = self._ptrs(list(d_dims)), self._ptrs(list(d_tables))
+        self._chk(self.lib.lasso_lookup_values(self.ctx, strategy, dims, tabs if not field_tables else None, tabs if field_tables else None, n, form, C.c_void_p(d_out)))
+
     def msm_dev(self, bases, d_scalars, n):
         out = np.empty((1, 16), dtype=np.uint64)
         self._chk(self.lib.lasso_msm_dev(self.ctx, C.c_void_p(bases), C.c_void_p(d_scalars), n, _vp(out)))

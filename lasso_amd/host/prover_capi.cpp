@@ -10,6 +10,9 @@
 #include "../../include/lasso_hip_gens.h"
 #include "../../include/lasso_hip_mle.h"
 #include "../../include/lasso_prover_mle.h"
+#include "../../include/lasso_hip_values.h"
+#include "../../include/lasso_prover_values.h"
+#include "../csrc/values_combine.cuh"
 
 using namespace lasso;
 
@@ -41,6 +44,12 @@ extern "C" int32_t lasso_points_from_candidates(lasso_ctx*, const uint64_t*, con
 // where the entry point exists; LASSO_MLE_DEVICE_MIN is the smallest num_subtables * 2^log_m that goes to the device (switches.hpp).
 extern "C" int32_t lasso_tables_mle(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
 
+// The lookup results as a vector (include/lasso_hip_values.h) are optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
+// lasso_host_lookup_values then says so; lasso_host_lookup_values_ref needs no device.  lasso_host_values_evaluate takes lasso_tables_mle above (host vectors) or its
+// device-resident form.
+extern "C" int32_t lasso_lookup_values(lasso_ctx*, const lasso_strategy*, const uint32_t* const*, const uint32_t* const*, const lasso_fr* const*, size_t, int32_t, void*) __attribute__((weak));
+extern "C" int32_t lasso_tables_mle_dev(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -52,6 +61,7 @@ struct lasso_host {
   uint64_t operand_dims = 0;         // dimensions densified by lasso_densify_dim_operands for this host (lasso_host_densify_stats)
   uint64_t gens_device_candidates = 0;   // candidates handed to lasso_points_from_candidates for this host (lasso_host_gens_stats)
   uint64_t mle_device_tables = 0;        // caller-defined tables evaluated by lasso_tables_mle for this host (lasso_host_mle_stats)
+  uint64_t values_device_lookups = 0;    // elements lasso_lookup_values wrote for this host (lasso_host_values_stats)
   TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = &mle_device_tables; } return m; }
   GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = &gens_device_candidates; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
@@ -75,7 +85,7 @@ struct lasso_host_dense {
 };
 
 static thread_local std::string g_err;
-#define GUARD(body) try { body } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
+#define GUARD(...) try { __VA_ARGS__ } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
 static int32_t emit(const std::vector<uint8_t>& b, uint8_t* out, size_t cap, size_t* len) { if (len) *len = b.size(); if (!out || b.size() > cap) { g_err = "output buffer too small"; return -2; } memcpy(out, b.data(), b.size()); return 0; }
 
 extern "C" {
@@ -446,6 +456,126 @@ int32_t lasso_host_mle_stats(lasso_host* h, uint64_t* device_tables, int32_t* av
     if (device_tables) *device_tables = h->mle_device_tables;
     if (available) *available = lasso_tables_mle ? 1 : 0;
     if (reset) h->mle_device_tables = 0;
+    return 0;)
+}
+// ---- include/lasso_prover_values.h: the lookup results as a vector, a vector's evaluation at r, the claim inside the proof bytes
+// the refusal of the 64-bit form in the words the device entry reports it with (Dev::chk of lasso_lookup_values' LASSO_ERR_UNSUPPORTED): one text whichever route ran
+static void values_check_form(const Strategy& S, int32_t form) {
+  if (form != LASSO_VALUES_FR && form != LASSO_VALUES_U64) throw Error("lookup values: form is neither LASSO_VALUES_FR (0) nor LASSO_VALUES_U64 (1)");
+  if (form == LASSO_VALUES_U64 && (S.custom() || S.spark() || !S.integer_tables() || !values_u64_offered(S.abi.kind, S.abi.c, S.abi.log_m)))
+    throw Error("lasso_lookup_values failed (" + std::to_string((int)LASSO_ERR_UNSUPPORTED) + "): lasso_lookup_values: " VALUES_MSG_U64);
+}
+int32_t lasso_host_lookup_values_ref(const lasso_strategy* st, const uint64_t* indices, size_t n, int32_t form, void* out, size_t cap, size_t* count) {
+  GUARD(
+    const Strategy S = Strategy::from_abi(st);
+    if (!indices || n < 1) throw Error("lasso_host_lookup_values_ref: null indices, or no lookups");
+    if (S.abi.kind < LASSO_AND || S.abi.kind > LASSO_CUSTOM || S.C() < 1 || S.abi.log_m < 1 || S.abi.log_m > 32) throw Error("lasso_host_lookup_values_ref: unknown strategy kind, c = 0, or log_m outside 1..32");
+    values_check_form(S, form);
+    const size_t s = next_pow2(n), C = S.C(), alpha = S.num_memories(); const uint64_t m = (uint64_t)1 << S.abi.log_m;
+    if (count) *count = s;
+    if (!out || cap < s) { g_err = "output buffer too small"; return -2; }
+    for (size_t k = 0; k < n * C; k++) if (indices[k] >= m) throw Error("lasso_host_lookup_values_ref: an index is not below 2^log_m");
+    // materialize_subtables (subtables/*.rs), or the caller's
+    std::vector<std::vector<uint32_t>> ti; std::vector<ScVec> tf; const bool ints = S.integer_tables();
+    if (S.custom()) {
+      for (size_t i = 0; i < S.num_subtables(); i++) {
+        if (ints) ti.emplace_back(S.cabi.tables_u32[i], S.cabi.tables_u32[i] + m);
+        else { ScVec t(m); for (uint64_t j = 0; j < m; j++) t[j] = Sc::from_abi(S.cabi.tables_fr[i][j]); tf.push_back(std::move(t)); }
+      }
+    } else if (ints) ti = S.materialize_subtables();
+    else { const std::vector<ScVec> tau = S.spark_point(); for (size_t i = 0; i < S.num_subtables(); i++) tf.push_back(eq_evals_host(tau[i].data(), tau[i].size())); }
+    const ScVec w = S.linear() ? S.weights() : ScVec();
+    const uint32_t inc = values_inc(S.abi.kind, S.abi.log_m);
+    ScVec vals(alpha); std::vector<uint32_t> iv(alpha);
+    for (size_t k = 0; k < s; k++) {
+      for (size_t i = 0; i < alpha; i++) {
+        const uint64_t a = k < n ? indices[k * C + S.memory_to_dimension_index(i)] : 0;   // access_sequence.resize(s, 0): densified.rs:38
+        const size_t sub = S.memory_to_subtable_index(i);
+        if (ints) { iv[i] = ti[sub][a]; vals[i] = Sc::from_u64(iv[i]); } else vals[i] = tf[sub][a];
+      }
+      if (form == LASSO_VALUES_U64) {   // values_check_form: a built-in integer kind whose result fits
+        uint64_t g;
+        if (S.abi.kind == LASSO_LT) { g = iv[2 * (C - 1)]; for (size_t c = C - 1; c-- > 0;) g = values_lt_step(iv[2 * c], iv[2 * c + 1], g); }
+        else { values_u128 acc = 0; for (size_t i = 0; i < alpha; i++) values_linear_add(acc, iv[i], (uint32_t)i * inc); g = (uint64_t)acc; }
+        ((uint64_t*)out)[k] = g;
+        continue;
+      }
+      Sc g = Sc::zero();   // combine_lookups as the strategies state it
+      if (S.custom()) {
+        for (uint32_t t = 0; t < S.cabi.num_terms; t++) { Sc term = Sc::from_abi(S.cabi.coeff[t]); for (uint32_t j = S.cabi.term_start[t]; j < S.cabi.term_start[t + 1]; j++) term *= vals[S.cabi.term_mem[j]]; g += term; }
+      } else if (S.spark()) { g = Sc::one(); for (size_t i = 0; i < alpha; i++) g *= vals[i]; }
+      else if (S.abi.kind == LASSO_LT) { Sc eq_prod = Sc::one(); for (size_t c = 0; c < C; c++) { g += vals[2 * c] * eq_prod; eq_prod *= vals[2 * c + 1]; } }   // lt.rs:62-71
+      else for (size_t i = 0; i < alpha; i++) g += w[i] * vals[i];
+      ((lasso_fr*)out)[k] = (g * Sc::one()).abi();
+    }
+    return 0;)
+}
+int32_t lasso_host_lookup_values(lasso_host* h, lasso_host_dense* dn, const lasso_strategy* st, int32_t form, int32_t out_on_device, void* out) {
+  GUARD(
+    if (!h || !dn || !dn->d || !out || (out_on_device != 0 && out_on_device != 1)) throw Error("lasso_host_lookup_values: null argument, or `out_on_device` is neither 0 (host) nor 1 (device)");
+    const Strategy S = Strategy::from_abi(st);
+    const DensifiedRepresentation& D = *dn->d; const Dev& d = h->dev;
+    if (S.C() != D.C || S.abi.log_m != D.log_m) throw Error("lasso_host_lookup_values: the strategy's c / log_m do not match the densified representation");
+    if (d.comm.sharded() || D.s_loc != D.s) throw Error("lasso_host_lookup_values: a slab-mode representation holds one residue class of the lookups per rank; the values of a sharded proof are not offered");
+    values_check_form(S, form);
+    if (!lasso_lookup_values) throw Error("lasso_host_lookup_values: the device entry (lasso_lookup_values, include/lasso_hip_values.h) is not available in the device library this host was linked against");
+    // the tables on the device, as Prover::prove makes them (materialised by the device, Spark's eq tables, or the caller's uploaded); they go back to the pool on return
+    const size_t m = D.m, s = D.s; const bool ints = S.integer_tables();
+    std::vector<DBufU32> tu; std::vector<DBuf> tf; std::vector<const uint32_t*> pu; std::vector<const lasso_fr*> pf;
+    for (size_t i = 0; i < S.num_subtables(); i++) {
+      if (ints) {
+        tu.emplace_back(d, m);
+        if (S.custom()) d.chk(lasso_upload(d.ctx, tu.back().p, S.cabi.tables_u32[i], m * sizeof(uint32_t)), "lasso_upload");
+        else d.chk(lasso_materialize_subtable_u32(d.ctx, &S.abi, (uint32_t)i, tu.back().p), "lasso_materialize_subtable_u32");
+        pu.push_back(tu.back().p);
+      } else {
+        tf.emplace_back(d, m);
+        if (S.custom()) d.chk(lasso_upload(d.ctx, tf.back().p, S.cabi.tables_fr[i], m * sizeof(lasso_fr)), "lasso_upload");
+        else { const std::vector<ScVec> tau = S.spark_point(); std::vector<lasso_fr> tv; for (auto& x : tau[i]) tv.push_back(x.abi()); d.chk(lasso_eq_evals(d.ctx, tv.data(), (uint32_t)tv.size(), tf.back().p), "lasso_eq_evals"); }
+        pf.push_back(tf.back().p);
+      }
+    }
+    std::vector<const uint32_t*> dims; for (size_t i = 0; i < D.C; i++) dims.push_back(D.dim_u32[i].p);
+    const size_t bytes = s * (form == LASSO_VALUES_U64 ? sizeof(uint64_t) : sizeof(lasso_fr));
+    void* d_out = out_on_device ? out : d.alloc_bytes(bytes);
+    try {
+      d.chk(lasso_lookup_values(d.ctx, S.abi_ptr(), dims.data(), ints ? pu.data() : nullptr, ints ? nullptr : pf.data(), s, form, d_out), "lasso_lookup_values");
+      if (out_on_device) d.chk(lasso_sync(d.ctx), "lasso_sync"); else d.chk(lasso_download(d.ctx, out, d_out, bytes), "lasso_download");
+    } catch (...) { if (!out_on_device) d.free(d_out); throw; }
+    if (!out_on_device) d.free(d_out);
+    h->values_device_lookups += s;
+    return 0;)
+}
+int32_t lasso_host_dense_len(lasso_host_dense* dn, size_t* s) { GUARD(if (!dn || !dn->d || !s) throw Error("lasso_host_dense_len: null argument"); *s = dn->d->s; return 0;) }
+int32_t lasso_host_values_evaluate(lasso_host* h, const lasso_fr* values, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len, lasso_fr* out) {
+  GUARD(
+    if (!h || !values || !out || (!r && r_len) || (on_device != 0 && on_device != 1)) throw Error("lasso_host_values_evaluate: null argument, or `values_on_device` is neither 0 (host) nor 1 (device)");
+    if (r_len > 30 || s != ((size_t)1 << r_len)) throw Error("lasso_host_values_evaluate: the vector must have 2^r_len elements, r_len at most 30");
+    if (r_len == 0) {   // the polynomial in no variables is its one value
+      lasso_fr v; if (on_device) h->dev.chk(lasso_download(h->dev.ctx, &v, values, sizeof v), "lasso_download"); else v = values[0];
+      *out = (Sc::from_abi(v) * Sc::one()).abi(); return 0;
+    }
+    auto fn = on_device ? lasso_tables_mle_dev : lasso_tables_mle;
+    if (!fn) throw Error("lasso_host_values_evaluate: the device entry (lasso_tables_mle / lasso_tables_mle_dev, include/lasso_hip_mle.h) is not available in the device library this host was linked against");
+    const lasso_fr* one[1] = {values};
+    h->dev.chk(fn(h->dev.ctx, nullptr, one, 1, (uint32_t)r_len, r, out), on_device ? "lasso_tables_mle_dev" : "lasso_tables_mle");
+    return 0;)
+}
+int32_t lasso_host_proof_claimed_evaluation(const uint8_t* proof, size_t proof_len, lasso_fr* out) {
+  GUARD(
+    if (!proof || !out) throw Error("lasso_host_proof_claimed_evaluation: null argument");
+    ProofReader r(proof, proof_len);
+    std::vector<const uint8_t*> skipped; r.collect = &skipped;   // comm_derefs' points are stepped over, not decoded (read_proof's structural pass)
+    (void)r.pts_vec(); (void)r.sumcheck();                       // surge.rs:92-104: comm_derefs, the primary sumcheck, then the scalar
+    *out = r.sc().abi();
+    return 0;)
+}
+int32_t lasso_host_values_stats(lasso_host* h, uint64_t* device_lookups, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_values_stats: null host");
+    if (device_lookups) *device_lookups = h->values_device_lookups;
+    if (available) *available = lasso_lookup_values ? 1 : 0;
+    if (reset) h->values_device_lookups = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

@@ -336,6 +336,95 @@ class HostProver:
         self._chk(lib.lasso_host_mle_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
         return {"device_tables": k.value, "available": bool(a.value)}
 
+    def _values_fns(self):
+        """include/lasso_prover_values.h, declared on first use (a prover library built before that header existed does not export it)"""
+        if not hasattr(self, "_values_ok"):
+            vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
+            try:
+                self.lib.lasso_host_lookup_values_ref.argtypes = [C.POINTER(_abi.Strategy), vp, sz, i32, vp, sz, C.POINTER(sz)]
+                self.lib.lasso_host_lookup_values.argtypes = [vp, vp, C.POINTER(_abi.Strategy), i32, i32, vp]
+                self.lib.lasso_host_values_evaluate.argtypes = [vp, vp, i32, sz, vp, sz, vp]
+                self.lib.lasso_host_proof_claimed_evaluation.argtypes = [C.c_char_p, sz, vp]
+                self.lib.lasso_host_values_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(i32), i32]
+                self.lib.lasso_host_dense_len.argtypes = [vp, C.POINTER(sz)]
+            except AttributeError:
+                raise LassoError("this prover library does not export lasso_host_lookup_values (include/lasso_prover_values.h)")
+            self._values_ok = True
+        return self.lib
+
+    @staticmethod
+    def _values_form(form):
+        if form not in ("field", "u64"):
+            raise LassoError('lookup values: form is "field" or "u64"')
+        return 1 if form == "u64" else 0
+
+    def lookup_values_ref(self, strategy, indices, form="field"):
+        """the lookup results v[k] = combine_lookups(T[dim(k)]) of the (n, c) uint64 `indices`, on the CPU (lasso_host_lookup_values_ref: the normative statement):
+        s = next_pow2(n) elements — (s, 4) uint64 fully reduced memory words, or (s,) uint64 for form="u64" (LassoError where that form is not offered) — the rows
+        behind n being the rows densify pads with (address 0)"""
+        lib = self._values_fns()
+        indices = np.ascontiguousarray(indices, dtype=np.uint64)
+        f = self._values_form(form)
+        n = indices.shape[0]
+        s = 1 << max((n - 1).bit_length(), 0)
+        out = np.zeros((s,) if f else (s, 4), dtype=np.uint64)
+        cnt = C.c_size_t()
+        self._chk(lib.lasso_host_lookup_values_ref(strategy_ptr(strategy), indices.ctypes.data_as(C.c_void_p), n, f, out.ctypes.data_as(C.c_void_p), s, C.byref(cnt)))
+        return out
+
+    def lookup_values(self, dense, strategy, form="field", out=None):
+        """the same vector for a densified representation, written by the device from the representation's own address columns (lasso_host_lookup_values).  out=None: a
+        numpy array as lookup_values_ref returns it.  `out`: a torch tensor ALREADY ON THE GPU of this host's context — contiguous int64 (reinterpreted as unsigned), shape
+        (s,) for form="u64" or (s, 4) for "field", s the representation's padded number of lookups — which receives the vector and is returned."""
+        lib = self._values_fns()
+        f = self._values_form(form)
+        n = C.c_size_t()
+        self._chk(lib.lasso_host_dense_len(dense, C.byref(n)))
+        s = n.value
+        if out is None:
+            host = np.zeros((s,) if f else (s, 4), dtype=np.uint64)
+            self._chk(lib.lasso_host_lookup_values(self.h, dense, strategy_ptr(strategy), f, 0, host.ctypes.data_as(C.c_void_p)))
+            return host
+        import torch
+        ok = hasattr(out, "data_ptr") and out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.device.index == self.device
+        if not ok or tuple(out.shape) != ((s,) if f else (s, 4)) or out.data_ptr() % 16:
+            raise LassoError(f"lookup_values: `out` must be a contiguous int64 tensor of shape ({s},) (u64) or ({s}, 4) (field), 16-byte aligned, on GPU {self.device}, the device of this host's context")
+        torch.cuda.current_stream(out.device).synchronize()      # nothing of the caller's may still be writing `out`; the call below returns when the vector is complete
+        self._chk(lib.lasso_host_lookup_values(self.h, dense, strategy_ptr(strategy), f, 1, C.c_void_p(out.data_ptr())))
+        return out
+
+    def values_evaluate(self, values, r):
+        """DensePolynomial::evaluate of `values` — (s, 4) uint64 memory words as a numpy array, or an (s, 4) contiguous int64 torch tensor on this host's GPU — at
+        r = (log2 s, 4) uint64: (4,) uint64, fully reduced (lasso_host_values_evaluate: one lasso_tables_mle call, no eq table)"""
+        lib = self._values_fns()
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(4, dtype=np.uint64)
+        if hasattr(values, "data_ptr") and hasattr(values, "is_cuda"):
+            import torch
+            if not values.is_cuda or values.dtype != torch.int64 or not values.is_contiguous() or values.dim() != 2 or values.shape[1] != 4 or values.device.index != self.device:
+                raise LassoError(f"values_evaluate: a tensor must be contiguous int64 of shape (s, 4) on GPU {self.device}, the device of this host's context")
+            torch.cuda.current_stream(values.device).synchronize()
+            self._chk(lib.lasso_host_values_evaluate(self.h, C.c_void_p(values.data_ptr()), 1, values.shape[0], r.ctypes.data_as(C.c_void_p), r.shape[0], out.ctypes.data_as(C.c_void_p)))
+            return out
+        values = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 4)
+        self._chk(lib.lasso_host_values_evaluate(self.h, values.ctypes.data_as(C.c_void_p), 0, values.shape[0], r.ctypes.data_as(C.c_void_p), r.shape[0], out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def claimed_evaluation(self, proof):
+        """claimed_evaluation inside the proof bytes as (4,) uint64 memory words, fully reduced (lasso_host_proof_claimed_evaluation); LassoError on bytes that do not
+        deserialize that far"""
+        lib = self._values_fns()
+        out = np.zeros(4, dtype=np.uint64)
+        self._chk(lib.lasso_host_proof_claimed_evaluation(bytes(proof), len(proof), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def values_stats(self, reset=False):
+        """{"device_lookups": elements lasso_lookup_values wrote for this host so far, "available": whether the device library has that entry} (lasso_host_values_stats)"""
+        lib = self._values_fns()
+        k, a = C.c_uint64(), C.c_int32()
+        self._chk(lib.lasso_host_values_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
+        return {"device_lookups": k.value, "available": bool(a.value)}
+
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
         self._chk(self.lib.lasso_host_strategy_check(strategy_ptr(strategy)))
