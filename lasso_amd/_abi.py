@@ -221,3 +221,16 @@ def declare_values(lib):
     fn.restype = i32
     fn.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_size_t, i32, vp]
     return ["lasso_lookup_values"]
+
+
+def declare_poly(lib):
+    """include/lasso_hip_poly.h — a vector of 64-bit integers as a polynomial.  Declared apart from declare(), as declare_values is: an implementation of lasso_hip.h
+    alone does not have it.  AttributeError = the library does not export it."""
+    sig = {"lasso_u64_or": [vp, vp, sz, C.POINTER(u64)],
+           "lasso_hyrax_commit_compressed_u64": [vp, vp, u64, sz, sz, vp, vp],
+           "lasso_matvec_left_u64_dev": [vp, vp, vp, sz, sz, vp]}
+    for name, args in sig.items():
+        fn = getattr(lib, name)
+        fn.restype = i32
+        fn.argtypes = args
+    return sorted(sig)

@@ -207,6 +207,17 @@ LHD fr_t fr29_pack(const fr29& a) {
 }
 #endif
 
+// acc += z * b, z a 64-bit integer, b as an unpack function returns it: 27 multiply-adds; up to FR29_U64_ACC_PERIOD of them between two fr29_acc_carry passes (mont29.cuh
+// m29_mul_acc_u64 derives the number).  With b in s-form (x 2^261), fr29_acc_reduce gives the INTEGER residue sum z x, and one product with R2S its memory form.
+#define FR29_U64_ACC_PERIOD M29_U64_ACC_PERIOD
+LHD void fr29_mul_acc_u64(fr29_acc& acc, uint64_t z, const fr29& b) { m29_mul_acc_u64(acc, z, b); }
+// the carry pass for an accumulator that has taken fr29_mul_acc_u64 products ONLY: they reach columns 0..10, and a sum of up to 2^20 of them is below 2^345, so column 11
+// (everything from 2^319 up: below 2^26) absorbs the top carry and columns 12..16 stay zero — to the compiler too, which then keeps 12 live columns instead of 17
+LHD void fr29_acc_carry_u64(fr29_acc& acc) {
+#pragma unroll
+  for (int k = 0; k < 11; k++) { acc.h[k + 1] += acc.h[k] >> 29; acc.h[k] &= FR29_MASK; }
+}
+
 // 2^261 mod p: fr29_mul(a, ONE_S) = a (mod p) with the magnitude brought back to (-X, p + X)
 LHD fr29 fr29_one_s() { return fr29_from_limbs(FrM29::ONE_S_0, FrM29::ONE_S_1, FrM29::ONE_S_2, FrM29::ONE_S_3, FrM29::ONE_S_4, FrM29::ONE_S_5, FrM29::ONE_S_6, FrM29::ONE_S_7, FrM29::ONE_S_8); }
 // 2^266 mod p: corrects a sum of mul(mul(u, s), u)-style terms that came out 2^5 short

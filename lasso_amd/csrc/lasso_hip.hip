@@ -27,6 +27,8 @@
 #include "mle_kernels.cuh"
 #include "../../include/lasso_hip_values.h"
 #include "values_kernels.cuh"
+#include "../../include/lasso_hip_poly.h"
+#include "poly_u64_kernels.cuh"
 
 __global__ void __launch_bounds__(256) k_inner_lr(const fr_t* __restrict__ a, const fr_t* __restrict__ b, size_t half, fr_t* __restrict__ partials) {
   __shared__ RedScratch S;
@@ -2170,6 +2172,55 @@ int32_t lasso_bullet_fold(lasso_ctx* c, lasso_fr* d_a, lasso_fr* d_b, size_t nk,
   const size_t half = nk / 2;
   ProfScope ps(c, LASSO_K_MISC, 96.0 * nk + 96.0 * nw);
   hipLaunchKernelGGL(k_bullet_fold, dim3(grid_for(half > nw ? half : nw)), dim3(256), 0, c->stream, (fr_t*)d_a, (fr_t*)d_b, half, (const fr_t*)d_w, nw, (fr_t*)d_w_out, to_fr(u), to_fr(u_inv));
+  HIPCHK(c, hipGetLastError()); return 0;
+}
+
+// ---- include/lasso_hip_poly.h: a vector of 64-bit integers as a polynomial (poly_u64_kernels.cuh)
+int32_t lasso_u64_or(lasso_ctx* c, const uint64_t* d_v, size_t n, uint64_t* out) {
+  REQUIRE(c, d_v && out && n >= 1 && ((uintptr_t)d_v & 7) == 0 && !c->proto.waiting_on_device());
+  HIPCHK(c, hipMemsetAsync(c->d_flags, 0, 8, c->stream));
+  {
+    ProfScope ps(c, LASSO_K_MISC, 8.0 * n);
+    hipLaunchKernelGGL(k_u64_or, dim3(grid_for(n, 4096)), dim3(256), 0, c->stream, d_v, n, (unsigned long long*)c->d_flags);
+  }
+  HIPCHK(c, hipGetLastError());
+  uint64_t bits = 0;
+  HIPCHK(c, hipMemcpyAsync(&bits, c->d_flags, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *out = bits; return 0;
+}
+// Z[i] = F::from(d_v[i]) committed row by row.  max_value < 2^32: the low words go to the scratch and the commitment is lasso_hyrax_commit_compressed_u32's from there on (the
+// byte-multiple tables where msm_plan selects them).  Otherwise the bucket kernel reads the 8-byte scalars where they are: W = ceil(bits / 4) <= 16 nibble windows.
+int32_t lasso_hyrax_commit_compressed_u64(lasso_ctx* c, const uint64_t* d_v, uint64_t max_value, size_t l_size, size_t r_size, const lasso_bases* b, uint8_t* out32) {
+  REQUIRE(c, d_v && out32 && b && l_size >= 1 && r_size >= 1 && r_size <= b->n && l_size < ((size_t)1 << 31) && ((uintptr_t)d_v & 7) == 0);
+  const size_t n = l_size * r_size, pts_bytes = msm_pts_bytes(l_size, r_size);
+  uint32_t bits = 0; while (bits < 64 && (max_value >> bits)) bits++;
+  uint32_t W = (bits + 3) / 4; if (W == 0) W = 1;
+  if (bits <= 32) {
+    const size_t scal_bytes = (n * 4 + 255) & ~(size_t)255;
+    int32_t rc = ensure_scratch(c, scal_bytes + pts_bytes + 256); if (rc) return rc;
+    uint8_t* d_scal = (uint8_t*)c->d_scratch;
+    {
+      ProfScope ps(c, LASSO_K_MISC, 12.0 * n);
+      hipLaunchKernelGGL(k_u64_to_u32, dim3(grid_for(n, 4096)), dim3(256), 0, c->stream, d_v, n, (uint32_t*)d_scal);
+    }
+    HIPCHK(c, hipGetLastError());
+    return run_msm(c, d_scal, 4, W, r_size * 4, l_size, r_size, b, d_scal + scal_bytes, nullptr, out32);
+  }
+  int32_t rc = ensure_scratch(c, pts_bytes + 256); if (rc) return rc;
+  return run_msm(c, (const uint8_t*)d_v, 8, W, r_size * 8, l_size, r_size, b, (uint8_t*)c->d_scratch, nullptr, out32);
+}
+// out[col] = sum_j L[j] * F::from(d_Z[j * r_size + col]): lasso_matvec_left_dev over integers, same scratch (the row-chunk partials), same second stage
+int32_t lasso_matvec_left_u64_dev(lasso_ctx* c, const uint64_t* d_Z, const lasso_fr* d_L, size_t l_size, size_t r_size, lasso_fr* d_out) {
+  REQUIRE(c, d_Z && d_L && d_out && l_size >= 1 && r_size >= 1 && l_size < ((size_t)1 << 31) && r_size < ((size_t)1 << 31) && ((uintptr_t)d_Z & 15) == 0);
+  const MatvecPlan mp = matvec_plan(l_size, r_size); const size_t col_blocks = mp.col_blocks, nchunks = mp.nchunks, rows_per_chunk = mp.rows_per_chunk;
+  if (rows_per_chunk > ((size_t)1 << 20)) return fail(c, LASSO_ERR_INVALID, "lasso_matvec_left_u64_dev: more than 2^20 rows per row chunk (l_size above 2^30)");
+  int32_t rc = ensure_scratch(c, nchunks * r_size * sizeof(fr_t)); if (rc) return rc;
+  fr_t* partials = (fr_t*)c->d_scratch;
+  const size_t pairs = (r_size + 1) / 2;
+  ProfScope ps(c, LASSO_K_MATVEC, 8.0 * l_size * r_size);
+  hipLaunchKernelGGL(k_matvec_left_u64, dim3((unsigned)((pairs + LASSO_BLOCK - 1) / LASSO_BLOCK), (unsigned)nchunks), dim3(LASSO_BLOCK), 0, c->stream, d_Z, (const fr_t*)d_L, l_size, r_size, rows_per_chunk, partials);
+  hipLaunchKernelGGL(k_matvec_reduce, dim3((unsigned)col_blocks), dim3(LASSO_BLOCK), 0, c->stream, (const fr_t*)partials, nchunks, r_size, (fr_t*)d_out);
   HIPCHK(c, hipGetLastError()); return 0;
 }
 

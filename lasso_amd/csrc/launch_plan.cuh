@@ -173,7 +173,7 @@ static inline BulletPlan bullet_plan(size_t n, size_t nk, uint32_t world, bool m
 }
 
 struct MsmSwitches { bool direct, rows8, rows8w, full8, pip; size_t rows8w_waves, pip_min_cols, pip_scratch_mb; long direct_wgs; };
-struct MsmShape { uint32_t bps, W; size_t rows, n_cols; bool compressed, dev_rows; };   // bps: bytes per scalar (4: W nibbles populated; 32: full width); compressed / dev_rows: wire bytes for the host / pt29 row sums left on the device
+struct MsmShape { uint32_t bps, W; size_t rows, n_cols; bool compressed, dev_rows; };   // bps: bytes per scalar (4, 8: W nibbles populated, W <= 8 / 16; 32: full width; 8 is served by the bucket kernel alone — every other kernel asks for 4 or 32); compressed / dev_rows: wire bytes for the host / pt29 row sums left on the device
 // n generators; the digit- and byte-multiple tables of the openings; tab8 / pip_scratch: false once the byte-window tables of the commitments (ensure_tab8) / the scratch of the
 // 12-bit-window kernels (ensure_pip) have been asked for and refused
 struct MsmHave { size_t n; bool mult, mult8, tab8, pip_scratch; };
@@ -222,7 +222,7 @@ static inline MsmPlan msm_plan(const MsmShape& s, const MsmHave& have, const Msm
   // two waves per SIMD, all resident at once) measured 0.966 ms against 0.896 ms at one row per wave on the headline's E, profiles/r06_madd_bench_curve25519.txt section C: two
   // waves per SIMD hide less than three, the tail of the three-wave schedule costs less than that.
   p.kernel = tab8 ? (sw.rows8w && p.K == 1 && s.rows >= 1024 && s.n_cols * p.W8 <= 8192 ? MSM_K_ROWS8W : MSM_K_ROWS8) : p.pip_group ? MSM_K_PIP : full8 ? MSM_K_FULL8 : MSM_K_BUCKETS;
-  p.ref_adds = msm_ref_adds(s.rows, s.n_cols, s.bps == 4 ? 4 * s.W : FR_MODULUS_BITS);
+  p.ref_adds = msm_ref_adds(s.rows, s.n_cols, s.bps == 32 ? FR_MODULUS_BITS : 4 * s.W);
   p.adds = (double)s.rows * s.n_cols * (tab8 ? p.W8 : full8 ? 32 : p.pip_group ? MSM_PIP_WINDOWS : s.W);
   return p;
 }

@@ -186,6 +186,21 @@ template <class M> LHD void m29_mul_acc(m29_acc<M>& acc, const m29<M>& a, const 
 #pragma unroll
     for (int j = 0; j < 9; j++) acc.h[i + j] += (int64_t)a.v[i] * b.v[j];
 }
+// acc += z * b for a 64-bit INTEGER z (not a field element) and a masked operand b (every limb in [0, 2^29): what m29_unpack_words / _shl5 return for any memory word,
+// whichever modulus and however lazily the word is reduced).  z = z0 + z1 2^29 + z2 2^58 with z0, z1 < 2^29, z2 < 2^6: 27 multiply-adds into columns 0..10 instead of 81.
+// How many such products fit between two m29_acc_carry passes.  Column k receives z0 b_k + z1 b_(k-1) + z2 b_(k-2) <= 2 (2^29 - 1)^2 + (2^6 - 1)(2^29 - 1) < 2^59 + 2^35 per product.
+// A carry pass leaves columns 0..15 in [0, 2^29) (column 16 is never reached: a sum of 2^20 products is below 2^(64 + 261 + 20) < 2^(29 * 16)), and during the next pass a
+// column takes a carry below 2^63 / 2^29 = 2^34 before it is shifted itself.  N products are safe when 2^29 + N (2^59 + 2^35) + 2^34 < 2^63 = 16 * 2^59: N <= 15 =
+// M29_U64_ACC_PERIOD (15 * 2^35 + 2^34 + 2^29 < 2^59 is the room the sixteenth 2^59 leaves).  The bound
+// uses the masks alone, so it is the same for both moduli; tests/cpp/test_mul_acc_u64_host.cpp runs 15 products of all-ones limbs, twice, under UBSan.
+#define M29_U64_ACC_PERIOD 15
+template <class M> LHD void m29_mul_acc_u64(m29_acc<M>& acc, uint64_t z, const m29<M>& b) {
+  const int32_t zl[3] = {(int32_t)(z & M29_MASK), (int32_t)((z >> 29) & M29_MASK), (int32_t)(z >> 58)};
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 9; j++) acc.h[i + j] += (int64_t)zl[i] * b.v[j];
+}
 template <class M> LHD void m29_acc_carry(m29_acc<M>& acc) {
 #pragma unroll
   for (int k = 0; k < 16; k++) { acc.h[k + 1] += acc.h[k] >> 29; acc.h[k] &= M29_MASK; }

@@ -438,6 +438,32 @@ class Device:
         dims, tabs = self._ptrs(list(d_dims)), self._ptrs(list(d_tables))
         self._chk(self.lib.lasso_lookup_values(self.ctx, strategy, dims, tabs if not field_tables else None, tabs if field_tables else None, n, form, C.c_void_p(d_out)))
 
+    def _poly_fns(self):
+        if not hasattr(self, "_poly_ok"):
+            try:
+                _abi.declare_poly(self.lib)
+            except AttributeError:
+                raise LassoError("this device library does not export lasso_matvec_left_u64_dev (include/lasso_hip_poly.h)")
+            self._poly_ok = True
+        return self.lib
+
+    def u64_or(self, d_v, n):
+        """the OR of n 64-bit integers on the device (include/lasso_hip_poly.h lasso_u64_or): which bits are populated.  A library without the entry point is an error,
+        not a fall-back."""
+        out = C.c_uint64(0)
+        self._chk(self._poly_fns().lasso_u64_or(self.ctx, C.c_void_p(d_v), n, C.byref(out)))
+        return out.value
+
+    def hyrax_commit_compressed_u64(self, d_u64, max_value, l_size, r_size, bases):
+        """hyrax_commit_compressed for Z[i] = F::from(d_u64[i]), every element at most `max_value` (lasso_hyrax_commit_compressed_u64): (l_size, 32) uint8"""
+        out = np.empty((l_size, 32), dtype=np.uint8)
+        self._chk(self._poly_fns().lasso_hyrax_commit_compressed_u64(self.ctx, C.c_void_p(d_u64), max_value, l_size, r_size, C.c_void_p(bases), _vp(out)))
+        return out
+
+    def matvec_left_u64_dev(self, d_z, d_l, l_size, r_size, d_out):
+        """matvec_left_dev over 64-bit integers, enqueued on the context's stream (lasso_matvec_left_u64_dev)"""
+        self._chk(self._poly_fns().lasso_matvec_left_u64_dev(self.ctx, C.c_void_p(d_z), C.c_void_p(d_l), l_size, r_size, C.c_void_p(d_out)))
+
     def msm_dev(self, bases, d_scalars, n):
         out = np.empty((1, 16), dtype=np.uint64)
         self._chk(self.lib.lasso_msm_dev(self.ctx, C.c_void_p(bases), C.c_void_p(d_scalars), n, _vp(out)))

@@ -1510,7 +1510,10 @@ class Prover {
     return Pt::from_abi(out);
   }
   // d_a0 = x (here L*Z), d_b0 = a (here the R half of the eq table), both of length n and resident on the device; a_bytes = serialize(a)
-  DotProductProofLog dot_product_log_prove(const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y) {
+  // Static over (device, transcript, tape): a Lasso proof's three openings call it through the member form below, the opening of a caller's own vector
+  // (include/lasso_prover_poly.h lasso_host_poly_open) with its own transcript and no Prover at all — one text.
+  DotProductProofLog dot_product_log_prove(const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y) { return dot_product_log_prove(d, t, tape, g, d_a0, d_b0, a_bytes, y); }
+  static DotProductProofLog dot_product_log_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y) {
     static_assert(sizeof(Sc) == sizeof(lasso_fr), "ScVec is uploaded as an array of lasso_fr");
     Trace tr("DotProductProofLog.prove", d.ctx);
     t.append_protocol_name("dot product proof (log)");
@@ -1655,7 +1658,39 @@ class Prover {
     return P;
   }
   // ---- PolyEvalProof::prove (dense_mlpoly.rs:302-359), blinds None
+  // One GPU, the whole polynomial resident: everything stays on the device — the two halves of the eq table (eq_poly.rs:44-52), L*Z (dense_mlpoly.rs:184-207); only
+  // serialize(R) comes back.  Static for the reason dot_product_log_prove is.  matvec_u64 != null: d_poly holds 64-bit integers, Z[i] = F::from(d_poly[i]), and L*Z reads
+  // them as they are (include/lasso_hip_poly.h lasso_matvec_left_u64_dev).  Zr == null: the evaluation is not known yet — it is <L*Z, R>, taken from the vector just
+  // computed (2^right products on the host); *Zr_out receives what the proof is about either way.
+  typedef int32_t (*MatvecU64)(lasso_ctx*, const uint64_t*, const lasso_fr*, size_t, size_t, lasso_fr*);
+  static DotProductProofLog poly_eval_prove_resident(const Dev& d, ProofTranscript& t, RandomTape& tape, const void* d_poly, MatvecU64 matvec_u64, size_t num_vars, const ScVec& r, const Sc* Zr, Sc* Zr_out,
+                                                     const PolyCommitmentGens& g) {
+    Trace tr("DensePolyEval.prove", d.ctx);
+    t.append_protocol_name("polynomial evaluation proof");
+    LASSO_REQUIRE(r.size() == num_vars && d_poly);
+    size_t left = num_vars / 2, right = num_vars - left;
+    const size_t Ln = (size_t)1 << left, Rn = (size_t)1 << right;
+    DBuf d_LZ(d, Rn), d_R(d, Rn);
+    std::vector<uint8_t> a_bytes(32 * Rn);
+    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i < left; i++) rl.push_back(r[i].abi()); for (size_t i = left; i < num_vars; i++) rr.push_back(r[i].abi());
+    DBuf d_L(d, Ln);
+    d.chk(lasso_eq_evals(d.ctx, rl.data(), (uint32_t)left, d_L.p), "lasso_eq_evals");
+    d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)right, d_R.p), "lasso_eq_evals");
+    if (matvec_u64) d.chk(matvec_u64(d.ctx, (const uint64_t*)d_poly, d_L.p, Ln, Rn, d_LZ.p), "lasso_matvec_left_u64_dev");
+    else d.chk(lasso_matvec_left_dev(d.ctx, (const lasso_fr*)d_poly, d_L.p, Ln, Rn, d_LZ.p), "lasso_matvec_left_dev");
+    d.chk(lasso_fr_to_bytes(d.ctx, d_R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
+    Sc y;
+    if (Zr) y = *Zr;
+    else {
+      std::vector<lasso_fr> lz(Rn); d.chk(lasso_download(d.ctx, lz.data(), d_LZ.p, Rn * sizeof(lasso_fr)), "lasso_download");
+      const ScVec R = eq_evals_host(r.data() + left, right);
+      y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(lz[i]) * R[i];
+    }
+    if (Zr_out) *Zr_out = y;
+    return dot_product_log_prove(d, t, tape, g, d_LZ, d_R, a_bytes, y);
+  }
   DotProductProofLog poly_eval_prove(const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const Sc& Zr, const PolyCommitmentGens& g) {
+    if (this->P == 1 && d_poly) return poly_eval_prove_resident(d, t, tape, d_poly, nullptr, num_vars, r, &Zr, nullptr, g);
     Trace tr("DensePolyEval.prove", d.ctx);
     t.append_protocol_name("polynomial evaluation proof");
     LASSO_REQUIRE(r.size() == num_vars);
@@ -1678,14 +1713,7 @@ class Prover {
       d.chk(lasso_upload(d.ctx, ones.p, one_h.data(), nb * sizeof(lasso_fr)), "lasso_upload");
       d.chk(lasso_matvec_left_dev(d.ctx, Mb.p, ones.p, nb, Rn, d_LZ.p), "lasso_matvec_left_dev");
       d.chk(lasso_fr_to_bytes(d.ctx, d_R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    } else if (this->P == 1) {
-      // everything stays on the device: the two halves of the eq table (eq_poly.rs:44-52), L*Z (dense_mlpoly.rs:184-207); only serialize(R) comes back
-      DBuf d_L(d, Ln);
-      d.chk(lasso_eq_evals(d.ctx, rl.data(), (uint32_t)left, d_L.p), "lasso_eq_evals");
-      d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)right, d_R.p), "lasso_eq_evals");
-      d.chk(lasso_matvec_left_dev(d.ctx, d_poly, d_L.p, Ln, Rn, d_LZ.p), "lasso_matvec_left_dev");
-      d.chk(lasso_fr_to_bytes(d.ctx, d_R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    } else {
+    } else {   // (one GPU with the whole polynomial resident: poly_eval_prove_resident above)
       // slab mode: d_poly holds this rank's columns (= rank mod P) of every row, so the rank computes its entries of L*Z in full; the vector is
       // all-gathered and the opening's bullet reduction (latency-bound, sqrt(n)-sized) runs replicated on every rank with the same transcript
       ScVec L = eq_evals_host(r.data(), left);

@@ -13,6 +13,8 @@
 #include "../../include/lasso_hip_values.h"
 #include "../../include/lasso_prover_values.h"
 #include "../csrc/values_combine.cuh"
+#include "../../include/lasso_hip_poly.h"
+#include "../../include/lasso_prover_poly.h"
 
 using namespace lasso;
 
@@ -50,6 +52,14 @@ extern "C" int32_t lasso_tables_mle(lasso_ctx*, const uint32_t* const*, const la
 extern "C" int32_t lasso_lookup_values(lasso_ctx*, const lasso_strategy*, const uint32_t* const*, const uint32_t* const*, const lasso_fr* const*, size_t, int32_t, void*) __attribute__((weak));
 extern "C" int32_t lasso_tables_mle_dev(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
 
+// A vector of 64-bit integers as a polynomial (include/lasso_hip_poly.h) is optional in the same way: weak references, null against an implementation of lasso_hip.h alone —
+// lasso_host_poly_commit / lasso_host_poly_open then lift the integers to field elements on the host and take lasso_hyrax_commit_compressed / lasso_matvec_left_dev: the
+// same bytes.  The three are used together or not at all.
+extern "C" int32_t lasso_u64_or(lasso_ctx*, const uint64_t*, size_t, uint64_t*) __attribute__((weak));
+extern "C" int32_t lasso_hyrax_commit_compressed_u64(lasso_ctx*, const uint64_t*, uint64_t, size_t, size_t, const lasso_bases*, uint8_t*) __attribute__((weak));
+extern "C" int32_t lasso_matvec_left_u64_dev(lasso_ctx*, const uint64_t*, const lasso_fr*, size_t, size_t, lasso_fr*) __attribute__((weak));
+static bool poly_u64_device() { return lasso_u64_or && lasso_hyrax_commit_compressed_u64 && lasso_matvec_left_u64_dev; }
+
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
 // with the last child (Python's GC may release the three in any order).
@@ -62,6 +72,7 @@ struct lasso_host {
   uint64_t gens_device_candidates = 0;   // candidates handed to lasso_points_from_candidates for this host (lasso_host_gens_stats)
   uint64_t mle_device_tables = 0;        // caller-defined tables evaluated by lasso_tables_mle for this host (lasso_host_mle_stats)
   uint64_t values_device_lookups = 0;    // elements lasso_lookup_values wrote for this host (lasso_host_values_stats)
+  uint64_t poly_u64_commit_elems = 0, poly_u64_open_elems = 0;   // 64-bit elements committed to / opened through include/lasso_hip_poly.h for this host (lasso_host_poly_stats)
   TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = &mle_device_tables; } return m; }
   GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = &gens_device_candidates; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
@@ -82,6 +93,11 @@ struct lasso_host_dense {
   lasso_host* owner; std::unique_ptr<DensifiedRepresentation> d;
   explicit lasso_host_dense(lasso_host* h) : owner(h) { h->retain(); }
   ~lasso_host_dense() { d.reset(); owner->release(); }
+};
+struct lasso_host_poly_gens {
+  lasso_host* owner; std::unique_ptr<PolyCommitmentGens> g; size_t num_vars;
+  lasso_host_poly_gens(lasso_host* h, size_t nv) : owner(h), num_vars(nv) { h->retain(); }
+  ~lasso_host_poly_gens() { g.reset(); owner->release(); }
 };
 
 static thread_local std::string g_err;
@@ -576,6 +592,137 @@ int32_t lasso_host_values_stats(lasso_host* h, uint64_t* device_lookups, int32_t
     if (device_lookups) *device_lookups = h->values_device_lookups;
     if (available) *available = lasso_lookup_values ? 1 : 0;
     if (reset) h->values_device_lookups = 0;
+    return 0;)
+}
+// ---- include/lasso_prover_poly.h: a commitment to the caller's vector and its opening at a point
+}  // extern "C"
+// The caller's vector where the device calls read it: 64-bit integers as they are when the device library has include/lasso_hip_poly.h, field elements otherwise (lifted on
+// the host); host memory is uploaded.  A buffer made here goes back to the pool with the object.
+struct PolyOperand {
+  const Dev* dev = nullptr; const void* d = nullptr; bool u64 = false; void* own = nullptr;
+  PolyOperand() {}
+  PolyOperand(const PolyOperand&) = delete; PolyOperand& operator=(const PolyOperand&) = delete;
+  ~PolyOperand() { try { if (own && dev) dev->free(own); } catch (...) {} }
+};
+static void poly_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s) {
+  const std::string w(who);
+  if (!h || !g || !g->g || !values) throw Error(w + ": null argument");
+  if (g->owner != h) throw Error(w + ": the generators belong to another host");
+  if (form != LASSO_VALUES_FR && form != LASSO_VALUES_U64) throw Error(w + ": form is neither LASSO_VALUES_FR (0) nor LASSO_VALUES_U64 (1)");
+  if (on_device != 0 && on_device != 1) throw Error(w + ": `on_device` is neither 0 (host) nor 1 (device)");
+  if (h->dev.comm.sharded()) throw Error(w + ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+  if (s == 0 || (s & (s - 1))) throw Error(w + ": the number of values must be a power of two");
+  if (s != ((size_t)1 << g->num_vars)) throw Error(w + ": the generators were made for 2^" + std::to_string(g->num_vars) + " values, got " + std::to_string(s));
+  if ((uintptr_t)values & (on_device ? 15 : 7)) throw Error(w + ": the values pointer is misaligned for its form (host memory: 8 bytes, device memory: 16 bytes)");
+}
+static void poly_operand(lasso_host* h, const void* values, int32_t form, int32_t on_device, size_t s, PolyOperand& o) {
+  const Dev& d = h->dev; o.dev = &d;
+  const size_t elem = form == LASSO_VALUES_U64 ? sizeof(uint64_t) : sizeof(lasso_fr);
+  if (form == LASSO_VALUES_U64 && !poly_u64_device()) {   // the device library is an implementation of lasso_hip.h alone: F::from on the host, the 32-byte entries from there on
+    std::vector<uint64_t> v(s);
+    if (on_device) d.chk(lasso_download(d.ctx, v.data(), values, s * 8), "lasso_download"); else memcpy(v.data(), values, s * 8);
+    std::vector<lasso_fr> f(s); for (size_t i = 0; i < s; i++) f[i] = Sc::from_u64(v[i]).abi();
+    o.own = d.alloc_bytes(s * sizeof(lasso_fr)); o.d = o.own;
+    d.chk(lasso_upload(d.ctx, o.own, f.data(), s * sizeof(lasso_fr)), "lasso_upload");
+    return;
+  }
+  o.u64 = form == LASSO_VALUES_U64;
+  if (on_device) { o.d = values; return; }
+  o.own = d.alloc_bytes(s * elem); o.d = o.own;
+  d.chk(lasso_upload(d.ctx, o.own, values, s * elem), "lasso_upload");
+}
+static void poly_gens_check(const char* who, lasso_host* h, size_t num_vars, const void* out) {
+  const std::string w(who);
+  if (!h || !out) throw Error(w + ": null argument");
+  if (num_vars < 1 || num_vars > 30) throw Error(w + ": num_vars must be 1 .. 30");
+  if (h->dev.comm.sharded()) throw Error(w + ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+}
+extern "C" {
+int32_t lasso_host_poly_gens_new(lasso_host* h, const char* label, size_t num_vars, lasso_host_poly_gens** out) {
+  GUARD(
+    poly_gens_check("lasso_host_poly_gens_new", h, num_vars, out);
+    if (!label) throw Error("lasso_host_poly_gens_new: null label");
+    std::unique_ptr<lasso_host_poly_gens> g(new lasso_host_poly_gens(h, num_vars));
+    const GenStream gs(h->dev, label, ((size_t)1 << (num_vars - num_vars / 2)) + 2, h->gens_device());
+    g->g.reset(new PolyCommitmentGens(h->dev, gs, num_vars));
+    *out = g.release(); return 0;)
+}
+int32_t lasso_host_poly_gens_from_points(lasso_host* h, size_t num_vars, const lasso_affine* points, size_t n_points, lasso_host_poly_gens** out) {
+  GUARD(
+    poly_gens_check("lasso_host_poly_gens_from_points", h, num_vars, out);
+    std::unique_ptr<lasso_host_poly_gens> g(new lasso_host_poly_gens(h, num_vars));
+    g->g.reset(new PolyCommitmentGens(h->dev, points, n_points, num_vars));
+    *out = g.release(); return 0;)
+}
+void lasso_host_poly_gens_free(lasso_host_poly_gens* g) { delete g; }
+int32_t lasso_host_poly_commit(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, uint8_t* out, size_t cap, size_t* len) {
+  GUARD(
+    poly_check("lasso_host_poly_commit", h, g, values, form, on_device, s);
+    const Dev& d = h->dev; const size_t nv = g->num_vars, L = (size_t)1 << (nv / 2), R = (size_t)1 << (nv - nv / 2);
+    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
+    PolyCommitment c;
+    if (o.u64) {   // the populated bits bound the scalars: the width of the MSM's windows, and below 2^32 the 4-byte route
+      uint64_t bits = 0;
+      d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
+      c.rows = L; c.compressed.resize(32 * L);
+      d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, L, R, g->g->bases, c.compressed.data()), "lasso_hyrax_commit_compressed_u64");
+      h->poly_u64_commit_elems += s;
+    } else c = hyrax_commit(d, (const lasso_fr*)o.d, nv, *g->g);
+    ProofWriter w; w.pts_vec(c.compressed);
+    return emit(w.b, out, cap, len);)
+}
+int32_t lasso_host_poly_commitment_append(const lasso_transcript_vtbl* tv, void* tu, const char* label, const uint8_t* commitment, size_t len) {
+  GUARD(
+    if (!tv || !label || !commitment) throw Error("lasso_host_poly_commitment_append: null argument");
+    ProofReader r(commitment, len);
+    PolyCommitment c; c.rows = r.len(32);
+    if (len != 8 + 32 * c.rows) throw Error("commitment bytes: trailing data");
+    c.compressed.assign(commitment + 8, commitment + len);
+    ProofTranscript t(tv, tu);
+    append_poly_commitment(t, label, c);
+    return 0;)
+}
+int32_t lasso_host_poly_open(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len,
+                             const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, lasso_fr* Zr, uint8_t* proof, size_t cap, size_t* len) {
+  GUARD(
+    poly_check("lasso_host_poly_open", h, g, values, form, on_device, s);
+    if (!r || !tv || !pv) throw Error("lasso_host_poly_open: null argument");
+    if (r_len != g->num_vars) throw Error("lasso_host_poly_open: the point must have num_vars coordinates");
+    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
+    Sc y; DotProductProofLog P;
+    try { P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g); } catch (...) { h->dev.abort_all(); throw; }
+    if (o.u64) h->poly_u64_open_elems += s;
+    if (Zr) *Zr = (y * Sc::one()).abi();
+    ProofWriter w; P.write(w);
+    return emit(w.b, proof, cap, len);)
+}
+int32_t lasso_host_poly_verify(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const lasso_fr* Zr, const lasso_transcript_vtbl* tv, void* tu,
+                               const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
+  GUARD(
+    if (!h || !g || !g->g || !r || !Zr || !tv || !proof || !commitment || !ok) throw Error("lasso_host_poly_verify: null argument");
+    if (g->owner != h) throw Error("lasso_host_poly_verify: the generators belong to another host");
+    if (h->dev.comm.sharded()) throw Error("lasso_host_poly_verify: a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+    if (r_len != g->num_vars) throw Error("lasso_host_poly_verify: the point must have num_vars coordinates");
+    ProofReader pr(proof, proof_len);
+    const WireDotProductProofLog P = read_dpl(pr);
+    if (!pr.done()) throw Error("proof bytes: trailing data");
+    ProofReader cr(commitment, commitment_len);
+    const std::vector<WirePoint> comm = cr.pts_vec();
+    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    ProofTranscript t(tv, tu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    *ok = Verifier::poly_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, rv, Sc::from_abi(*Zr), comm) ? 1 : 0;
+    return 0;)
+}
+int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint64_t* u64_open_elements, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_poly_stats: null host");
+    if (u64_commit_elements) *u64_commit_elements = h->poly_u64_commit_elems;
+    if (u64_open_elements) *u64_open_elements = h->poly_u64_open_elems;
+    if (available) *available = poly_u64_device() ? 1 : 0;
+    if (reset) h->poly_u64_commit_elems = h->poly_u64_open_elems = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

@@ -295,7 +295,9 @@ class Verifier {
   }
   // VariableBaseMSM::msm over arbitrary points (the commitment rows).  The rows are used once, so the table-free MSM takes them where the device library has it
   // (points_msm, LASSO_VERIFY_MSM_POINTS); otherwise a base table is built for this call, then the device MSM.  Same group element either way.
-  Pt msm_points(const std::vector<WirePoint>& pts, const ScVec& scalars) {
+  // Static over (device, the optional table-free MSM): PolyEvalProof::verify_plain below is, so that the opening of a caller's own vector (include/lasso_prover_poly.h
+  // lasso_host_poly_verify) runs it without a Lasso verifier around it.
+  static Pt msm_points(const Dev& d, const PointsMsm& points_msm, const std::vector<WirePoint>& pts, const ScVec& scalars) {
     LASSO_REQUIRE(pts.size() == scalars.size());
     std::vector<lasso_affine> aff; std::vector<lasso_fr> sc;
     for (size_t i = 0; i < pts.size(); i++) { if (pts[i].infinity) continue; lasso_affine a; affine_to_abi(pts[i].p, a); aff.push_back(a); sc.push_back(scalars[i].abi()); }
@@ -317,13 +319,15 @@ class Verifier {
   }
   static void wire(const Pt& p, uint8_t out[32]) { compress_one(p, out); }
   // bullet.rs:158-257 inside dot_product.rs:251-296 inside dense_mlpoly.rs:361-400 (verify_plain: the claimed evaluation is committed with blind 0)
-  bool poly_eval_verify_plain(const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) {
+  bool poly_eval_verify_plain(const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) { return poly_eval_verify_plain(d, t, points_msm, p, g, r, Zr, comm); }
+ public:
+  static bool poly_eval_verify_plain(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) {
     const Pt C_Zr = g.Qmul.mul(Zr);   // Zr.commit(&0, &gens.gens.gens_1) = Zr * G[0] + 0 * h
     t.append_protocol_name("polynomial evaluation proof");
     const size_t left = r.size() / 2;   // EqPolynomial::compute_factored_evals eq_poly.rs:44-52
     const ScVec L = eq_evals_host(r.data(), left), R = eq_evals_host(r.data() + left, r.size() - left);
     if (comm.size() != L.size()) throw Error("commitment: wrong number of rows for this opening");
-    const Pt C_LZ = msm_points(comm, L);
+    const Pt C_LZ = msm_points(d, points_msm, comm, L);
     // DotProductProofLog::verify(n = R.len(), gens, a = R, Cx = C_LZ, Cy = C_Zr)
     const size_t n = R.size();
     if (g.n != n) throw Error("generators: wrong size for this opening");
@@ -357,6 +361,7 @@ class Verifier {
     const Pt rhs = (G_hat + g.Qmul.mul(a_hat)) * p.z1 + g.hmul.mul(p.z2);
     return ed_eq(lhs.p, rhs.p);
   }
+ private:
   // subtables/mod.rs:315-375
   bool combined_table_eval_verify(const WireDotProductProofLog& proof, const ScVec& r, const ScVec& evals_in, const std::vector<WirePoint>& comm) {
     t.append_protocol_name("Lasso CombinedTableEvalProof");

@@ -425,6 +425,127 @@ class HostProver:
         self._chk(lib.lasso_host_values_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
         return {"device_lookups": k.value, "available": bool(a.value)}
 
+    # ---- include/lasso_prover_poly.h: a commitment to the caller's vector and its opening at a point
+    def _poly_fns(self):
+        """include/lasso_prover_poly.h, declared on first use (a prover library built before that header existed does not export it)"""
+        if not hasattr(self, "_poly_ok"):
+            vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
+            vt = C.POINTER(TranscriptVtbl)
+            try:
+                self.lib.lasso_host_poly_gens_new.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp)]
+                self.lib.lasso_host_poly_gens_from_points.argtypes = [vp, sz, vp, sz, C.POINTER(vp)]
+                self.lib.lasso_host_poly_gens_free.argtypes = [vp]
+                self.lib.lasso_host_poly_commit.argtypes = [vp, vp, vp, i32, i32, sz, vp, sz, C.POINTER(sz)]
+                self.lib.lasso_host_poly_commitment_append.argtypes = [vt, vp, C.c_char_p, C.c_char_p, sz]
+                self.lib.lasso_host_poly_open.argtypes = [vp, vp, vp, i32, i32, sz, vp, sz, vt, vp, vt, vp, vp, vp, sz, C.POINTER(sz)]
+                self.lib.lasso_host_poly_verify.argtypes = [vp, vp, vp, sz, vp, vt, vp, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32)]
+                self.lib.lasso_host_poly_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(i32), i32]
+                self.lib.lasso_alloc.argtypes = [vp, sz, C.POINTER(vp)]       # the device library's, reached through the prover library that is linked against it
+                self.lib.lasso_free.argtypes = [vp, vp]
+            except AttributeError:
+                raise LassoError("this prover library does not export lasso_host_poly_commit (include/lasso_prover_poly.h)")
+            self._poly_ok = True
+        return self.lib
+
+    def poly_gens(self, num_vars, label=b"gens_poly", points=None):
+        """PolyCommitmentGens::new(num_vars, label) (lasso_host_poly_gens_new), or with `points` — an (n + 2, 8) uint64 array [G[0..n), gens_1.G[0], h],
+        n = 2^(num_vars - num_vars // 2) — the caller's own generators (lasso_host_poly_gens_from_points).  Release with free(poly_gens=...)."""
+        lib = self._poly_fns()
+        g = C.c_void_p()
+        if points is None:
+            self._chk(lib.lasso_host_poly_gens_new(self.h, label, num_vars, C.byref(g)))
+        else:
+            pts = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+            self._chk(lib.lasso_host_poly_gens_from_points(self.h, num_vars, pts.ctypes.data_as(C.c_void_p), pts.shape[0], C.byref(g)))
+        return g
+
+    def _poly_values(self, values, form):
+        """(pointer, form, on_device, s, what must stay alive): numpy arrays ((s,) uint64 = "u64", (s, 4) uint64 = "field"), torch tensors ALREADY ON THE GPU of this
+        host's context (contiguous int64 of those shapes, reinterpreted as unsigned, 16-byte aligned), or a DeviceVector"""
+        if isinstance(values, DeviceVector):
+            if values.host is not self or not values.ptr:
+                raise LassoError("poly: the DeviceVector belongs to another host, or was freed")
+            return C.c_void_p(values.ptr), self._values_form(values.form), 1, values.s, values
+        if hasattr(values, "data_ptr") and hasattr(values, "is_cuda"):
+            import torch
+            f = self._values_form(form or ("u64" if values.dim() == 1 else "field"))
+            ok = values.is_cuda and values.dtype == torch.int64 and values.is_contiguous() and values.device.index == self.device
+            if not ok or (values.dim() != 1 if f else (values.dim() != 2 or values.shape[1] != 4)) or values.data_ptr() % 16:
+                raise LassoError(f"poly: a tensor must be contiguous int64 of shape (s,) (u64) or (s, 4) (field), 16-byte aligned, on GPU {self.device}, the device of this host's context")
+            torch.cuda.current_stream(values.device).synchronize()
+            return C.c_void_p(values.data_ptr()), f, 1, values.shape[0], values
+        a = np.ascontiguousarray(values, dtype=np.uint64)
+        f = self._values_form(form or ("u64" if a.ndim == 1 else "field"))
+        if (a.ndim != 1) if f else (a.ndim != 2 or a.shape[1] != 4):
+            raise LassoError("poly: an array has shape (s,) (u64) or (s, 4) (field)")
+        return a.ctypes.data_as(C.c_void_p), f, 0, a.shape[0], a
+
+    def poly_commit(self, pgens, values, form=None):
+        """DensePolynomial::commit of `values` (see _poly_values for what they may be) over `pgens`: the bytes [u64 L][L x 32 B] (lasso_host_poly_commit).  The 64-bit
+        form is read as it is on the device where the device library has include/lasso_hip_poly.h"""
+        lib = self._poly_fns()
+        ptr, f, on_dev, s, keep = self._poly_values(values, form)
+        return self._bytes_call(lib.lasso_host_poly_commit, self.h, pgens, ptr, f, on_dev, s)
+
+    def poly_commitment_append(self, transcript, label, commitment):
+        """PolyCommitment::append_to_transcript(label) against a live transcript (a (vtbl, user) pair as Transcript.pair() makes it)"""
+        self._chk(self._poly_fns().lasso_host_poly_commitment_append(transcript[0], transcript[1], label, bytes(commitment), len(commitment)))
+
+    def poly_open(self, pgens, values, r, transcript, tape, form=None):
+        """PolyEvalProof::prove of `values` at r = (num_vars, 4) uint64 against live transcript and tape pairs: (proof bytes, Zr as (4,) uint64 memory words, fully
+        reduced) — Zr = the polynomial's evaluation at r, computed on the way (lasso_host_poly_open)"""
+        lib = self._poly_fns()
+        ptr, f, on_dev, s, keep = self._poly_values(values, form)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        zr = np.zeros(4, dtype=np.uint64)
+        proof = self._bytes_call(lambda *a: lib.lasso_host_poly_open(self.h, pgens, ptr, f, on_dev, s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1],
+                                                                      zr.ctypes.data_as(C.c_void_p), *a))
+        return proof, zr
+
+    def poly_verify(self, pgens, r, zr, proof, commitment, transcript):
+        """PolyEvalProof::verify_plain over the wire bytes against a live transcript pair: True = Ok(()), False = Err; LassoError on bytes that do not deserialize
+        (lasso_host_poly_verify)"""
+        lib = self._poly_fns()
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        zr = np.ascontiguousarray(zr, dtype=np.uint64).reshape(4)
+        ok = C.c_int32(-1)
+        self._chk(lib.lasso_host_poly_verify(self.h, pgens, r.ctypes.data_as(C.c_void_p), r.shape[0], zr.ctypes.data_as(C.c_void_p), transcript[0], transcript[1],
+                                             bytes(proof), len(proof), bytes(commitment), len(commitment), C.byref(ok)))
+        return ok.value == 1
+
+    def values_vector(self, dense, strategy):
+        """the lookup results of `dense` left ON THE DEVICE as a DeviceVector: 64-bit integers where lasso_lookup_values offers that form, field elements otherwise"""
+        lib = self._poly_fns(); self._values_fns()
+        n = C.c_size_t()
+        self._chk(lib.lasso_host_dense_len(dense, C.byref(n)))
+        for form in ("u64", "field"):
+            vec = DeviceVector(self, form, n.value)
+            try:
+                self._chk(lib.lasso_host_lookup_values(self.h, dense, strategy_ptr(strategy), self._values_form(form), 1, C.c_void_p(vec.ptr)))
+                return vec
+            except LassoError as e:
+                vec.free()
+                if form == "field" or "64-bit form" not in str(e):
+                    raise
+
+    def values_commit(self, dense, strategy, pgens):
+        """(commitment bytes, DeviceVector): the lookup results of `dense` written by the device (values_vector), never downloaded, and their commitment over `pgens`;
+        pass the vector on to poly_open and free() it afterwards"""
+        vec = self.values_vector(dense, strategy)
+        try:
+            return self.poly_commit(pgens, vec), vec
+        except Exception:
+            vec.free()
+            raise
+
+    def poly_stats(self, reset=False):
+        """{"u64_commit_elements", "u64_open_elements": 64-bit elements this host committed to / opened through the device entries of include/lasso_hip_poly.h so far,
+        "available": whether the device library has them} (lasso_host_poly_stats)"""
+        lib = self._poly_fns()
+        a, b, av = C.c_uint64(), C.c_uint64(), C.c_int32()
+        self._chk(lib.lasso_host_poly_stats(self.h, C.byref(a), C.byref(b), C.byref(av), 1 if reset else 0))
+        return {"u64_commit_elements": a.value, "u64_open_elements": b.value, "available": bool(av.value)}
+
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
         self._chk(self.lib.lasso_host_strategy_check(strategy_ptr(strategy)))
@@ -439,11 +560,13 @@ class HostProver:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         return self._bytes_call(self.lib.lasso_host_debug_cubic_batched, self.h, dense, gens, strategy_ptr(strategy), k, ell, vp(A), vp(B), vp(rand), vp(coeffs), vp(claim), transcript)
 
-    def free(self, dense=None, gens=None):
+    def free(self, dense=None, gens=None, poly_gens=None):
         if dense:
             self.lib.lasso_host_dense_free(dense)
         if gens:
             self.lib.lasso_host_gens_free(gens)
+        if poly_gens:
+            self._poly_fns().lasso_host_poly_gens_free(poly_gens)
 
     def close(self):
         if self.h:
@@ -466,6 +589,22 @@ class HostProver:
     def set_capacity(self, on=True):
         """capacity mode (lasso_host_set_capacity): large buffers go back to the driver on release; the per-rank high-water mark is the live peak"""
         self._chk(self.lib.lasso_host_set_capacity(self.h, 1 if on else 0))
+
+
+class DeviceVector:
+    """s elements in device memory of a HostProver's context ("u64": 8 bytes each, "field": 32), allocated here and released by free(): what
+    HostProver.values_vector returns and poly_commit / poly_open take without a download"""
+
+    def __init__(self, host, form, s):
+        lib = host._poly_fns()
+        p = C.c_void_p()
+        if lib.lasso_alloc(C.c_void_p(host.ctx()), s * (8 if form == "u64" else 32), C.byref(p)) != 0:
+            raise LassoError("DeviceVector: lasso_alloc failed")
+        self.host, self.form, self.s, self.ptr = host, form, s, p.value
+
+    def free(self):
+        if self.ptr:
+            self.host.lib.lasso_free(C.c_void_p(self.host.ctx()), C.c_void_p(self.ptr)); self.ptr = None
 
 
 class Transcript:
