@@ -1,5 +1,6 @@
 """ctypes prototypes for include/lasso_hip.h (shared by the real device library and, in tests, the oracle's mock)."""
 import ctypes as C
+import functools
 
 u64 = C.c_uint64
 u32 = C.c_uint32
@@ -156,81 +157,74 @@ def declare(lib):
 
 
 WIRE_STATUS = ["ok", "ok-identity", "non-canonical", "bad-flags", "not-on-curve", "not-in-subgroup"]   # include/lasso_hip_wire.h lasso_wire_status
-
-
-def declare_wire(lib):
-    """include/lasso_hip_wire.h — the device decoder of compressed points.  Declared apart from declare(): an implementation of lasso_hip.h alone (the tests' mock) does
-    not have it.  AttributeError = the library does not export it."""
-    fn = lib.lasso_points_decompress
-    fn.restype = i32
-    fn.argtypes = [vp, vp, sz, vp, vp, vp]
-    return ["lasso_points_decompress"]
-
-
-def declare_msm_points(lib):
-    """include/lasso_hip_msm.h — the MSM over the caller's own points, no lasso_bases.  Declared apart from declare(), as declare_wire is: an implementation of
-    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
-    for name in ("lasso_msm_points", "lasso_msm_points_dev"):
-        fn = getattr(lib, name)
-        fn.restype = i32
-        fn.argtypes = [vp, vp, vp, sz, vp]
-    return ["lasso_msm_points", "lasso_msm_points_dev"]
-
-
-def declare_operands(lib):
-    """include/lasso_hip_operands.h — densify from operand columns.  Declared apart from declare(), as declare_wire and declare_msm_points are: an implementation of
-    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
-    fn = lib.lasso_densify_dim_operands
-    fn.restype = i32
-    fn.argtypes = [vp, vp, vp, sz, C.POINTER(OperandLayout), sz, sz, sz, u32, u32, u32, vp, vp, vp, vp]
-    return ["lasso_densify_dim_operands"]
-
-
 CAND_STATUS = ["ok", "non-canonical", "no-point"]   # include/lasso_hip_gens.h lasso_cand_status
-
-
-def declare_gens(lib):
-    """include/lasso_hip_gens.h — stream candidates to generator points.  Declared apart from declare(), as declare_wire and declare_msm_points are: an implementation of
-    lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
-    fn = lib.lasso_points_from_candidates
-    fn.restype = i32
-    fn.argtypes = [vp, vp, vp, sz, vp, vp]
-    return ["lasso_points_from_candidates"]
-
-
-def declare_mle(lib):
-    """include/lasso_hip_mle.h — the multilinear extensions of caller-defined tables at a point.  Declared apart from declare(), as declare_wire and declare_msm_points
-    are: an implementation of lasso_hip.h alone does not have it.  AttributeError = the library does not export it."""
-    for name in ("lasso_tables_mle", "lasso_tables_mle_dev"):
-        fn = getattr(lib, name)
-        fn.restype = i32
-        fn.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), u32, u32, vp, vp]
-    return ["lasso_tables_mle", "lasso_tables_mle_dev"]
-
-
-HEADER_SYMBOLS = None
-
-
 VALUES_FR, VALUES_U64 = 0, 1   # include/lasso_hip_values.h lasso_values_form
 
-
-def declare_values(lib):
-    """include/lasso_hip_values.h — the lookup results as a vector.  Declared apart from declare(), as declare_mle is: an implementation of lasso_hip.h alone does not
-    have it.  AttributeError = the library does not export it."""
-    fn = lib.lasso_lookup_values
-    fn.restype = i32
-    fn.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.c_size_t, i32, vp]
-    return ["lasso_lookup_values"]
+# include/lasso_prover.h lasso_transcript_vtbl: merlin::Transcript as append_message / challenge_bytes callbacks (labels are pointer + length)
+APPEND_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t)
+CHALLENGE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t)
 
 
-def declare_poly(lib):
-    """include/lasso_hip_poly.h — a vector of 64-bit integers as a polynomial.  Declared apart from declare(), as declare_values is: an implementation of lasso_hip.h
-    alone does not have it.  AttributeError = the library does not export it."""
-    sig = {"lasso_u64_or": [vp, vp, sz, C.POINTER(u64)],
-           "lasso_hyrax_commit_compressed_u64": [vp, vp, u64, sz, sz, vp, vp],
-           "lasso_matvec_left_u64_dev": [vp, vp, vp, sz, sz, vp]}
-    for name, args in sig.items():
-        fn = getattr(lib, name)
+class TranscriptVtbl(C.Structure):
+    _fields_ = [("append_message", APPEND_FN), ("challenge_bytes", CHALLENGE_FN)]
+
+
+_P, _vt = C.POINTER, C.POINTER(TranscriptVtbl)
+# The OPTIONAL parts of the device ABI: extension -> (its header beside include/lasso_hip.h, {function: argument types}); every function returns int32_t.  They are declared
+# apart from declare() (declare_ext), on first use: an implementation of lasso_hip.h alone (the tests' mock) has none of them.  The first function of an extension is the one
+# error messages name.  The same rows as EXTS in lasso_amd/host/prover_capi.cpp.
+EXTENSIONS = {
+    "wire": ("lasso_hip_wire.h", {"lasso_points_decompress": [vp, vp, sz, vp, vp, vp]}),                      # the device decoder of compressed points
+    "msm_points": ("lasso_hip_msm.h", {"lasso_msm_points": [vp, vp, vp, sz, vp], "lasso_msm_points_dev": [vp, vp, vp, sz, vp]}),   # the MSM over the caller's own points, no lasso_bases
+    "operands": ("lasso_hip_operands.h", {"lasso_densify_dim_operands": [vp, vp, vp, sz, _P(OperandLayout), sz, sz, sz, u32, u32, u32, vp, vp, vp, vp]}),   # densify from operand columns
+    "gens": ("lasso_hip_gens.h", {"lasso_points_from_candidates": [vp, vp, vp, sz, vp, vp]}),                 # stream candidates to generator points
+    "mle": ("lasso_hip_mle.h", {"lasso_tables_mle": [vp, _P(vp), _P(vp), u32, u32, vp, vp], "lasso_tables_mle_dev": [vp, _P(vp), _P(vp), u32, u32, vp, vp]}),   # the MLEs of caller-defined tables at a point
+    "values": ("lasso_hip_values.h", {"lasso_lookup_values": [vp, vp, _P(vp), _P(vp), _P(vp), sz, i32, vp]}),   # the lookup results as a vector
+    "poly": ("lasso_hip_poly.h", {"lasso_matvec_left_u64_dev": [vp, vp, vp, sz, sz, vp], "lasso_u64_or": [vp, vp, sz, _P(u64)],   # a vector of 64-bit integers as a polynomial
+                                  "lasso_hyrax_commit_compressed_u64": [vp, vp, u64, sz, sz, vp, vp]}),
+}
+# The optional headers of the host prover's ABI (beside include/lasso_prover.h), in the same shape: a prover library built before a header existed does not export it.
+PROVER_EXTENSIONS = {
+    "mle": ("lasso_prover_mle.h", {"lasso_host_tables_mle": [vp, _P(Strategy), vp, sz, i32, vp], "lasso_host_mle_stats": [vp, _P(u64), _P(i32), i32]}),
+    "values": ("lasso_prover_values.h", {"lasso_host_lookup_values": [vp, vp, _P(Strategy), i32, i32, vp], "lasso_host_lookup_values_ref": [_P(Strategy), vp, sz, i32, vp, sz, _P(sz)],
+                                         "lasso_host_values_evaluate": [vp, vp, i32, sz, vp, sz, vp], "lasso_host_proof_claimed_evaluation": [C.c_char_p, sz, vp],
+                                         "lasso_host_values_stats": [vp, _P(u64), _P(i32), i32], "lasso_host_dense_len": [vp, _P(sz)]}),
+    "poly": ("lasso_prover_poly.h", {"lasso_host_poly_commit": [vp, vp, vp, i32, i32, sz, vp, sz, _P(sz)], "lasso_host_poly_gens_new": [vp, C.c_char_p, sz, _P(vp)],
+                                     "lasso_host_poly_gens_from_points": [vp, sz, vp, sz, _P(vp)], "lasso_host_poly_gens_free": [vp],
+                                     "lasso_host_poly_commitment_append": [_vt, vp, C.c_char_p, C.c_char_p, sz],
+                                     "lasso_host_poly_open": [vp, vp, vp, i32, i32, sz, vp, sz, _vt, vp, _vt, vp, vp, vp, sz, _P(sz)],
+                                     "lasso_host_poly_verify": [vp, vp, vp, sz, vp, _vt, vp, C.c_char_p, sz, C.c_char_p, sz, _P(i32)],
+                                     "lasso_host_poly_stats": [vp, _P(u64), _P(u64), _P(i32), i32]}),
+}
+
+
+def declare_ext(lib, name, table=EXTENSIONS):
+    """the prototypes of extension `name` of `table`; returns its function names, sorted.  AttributeError = the library does not export it."""
+    sig = table[name][1]
+    for fn_name, args in sig.items():
+        fn = getattr(lib, fn_name)
         fn.restype = i32
         fn.argtypes = args
     return sorted(sig)
+
+
+# the names the extensions' own tests and tools declare them by: each is declare_ext for one row of EXTENSIONS
+declare_wire = functools.partial(declare_ext, name="wire")
+declare_msm_points = functools.partial(declare_ext, name="msm_points")
+declare_operands = functools.partial(declare_ext, name="operands")
+declare_gens = functools.partial(declare_ext, name="gens")
+declare_mle = functools.partial(declare_ext, name="mle")
+declare_values = functools.partial(declare_ext, name="values")
+declare_poly = functools.partial(declare_ext, name="poly")
+
+
+def declared_ext(owner, name, table, what, error):
+    """owner.lib with extension `name` declared on first use; a library without it is an error (`error`, naming the extension's first function), not a fall-back"""
+    done = owner.__dict__.setdefault("_exts", set())
+    if name not in done:
+        try:
+            declare_ext(owner.lib, name, table)
+        except AttributeError:
+            raise error(f"this {what} library does not export {next(iter(table[name][1]))} (include/{table[name][0]})") from None
+        done.add(name)
+    return owner.lib

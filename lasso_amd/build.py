@@ -20,6 +20,12 @@ def _glob(d, exts):
     return [os.path.join(d, f) for f in sorted(os.listdir(d)) if f.endswith(exts)]
 
 
+def _headers(prefix):
+    """include/<prefix>.h and its optional extension headers (include/<prefix>_<extension>.h, lasso_amd/_abi.py EXTENSIONS / PROVER_EXTENSIONS), and the check both libraries share"""
+    inc = os.path.join(ROOT, "include")
+    return [os.path.join(inc, f) for f in sorted(os.listdir(inc)) if f == prefix + ".h" or f.startswith(prefix + "_")] + [os.path.join(inc, "lasso_custom_check.h")]
+
+
 CURVES = {"curve25519": ("", []), "bn254": ("_bn254", ["-DLASSO_BN254", "-Wl,-Bsymbolic"])}   # library suffix, extra compile flags
 
 
@@ -29,7 +35,7 @@ def build_device(force=False, verbose=False, curve="curve25519"):
     suffix, flags = CURVES[curve]
     csrc = os.path.join(HERE, "csrc")
     target = os.path.join(HERE, f"liblasso_hip{suffix}.so")
-    sources = _glob(csrc, (".hip", ".cuh")) + [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_hip_msm.h", "lasso_hip_operands.h", "lasso_hip_gens.h", "lasso_hip_mle.h", "lasso_hip_values.h", "lasso_hip_poly.h", "lasso_custom_check.h")]
+    sources = _glob(csrc, (".hip", ".cuh")) + _headers("lasso_hip")
     if force or _stale(target, sources):
         extra = os.environ.get("LASSO_EXTRA_HIPCC_FLAGS", "").split()   # A/B builds of compile-time switches (e.g. -DLASSO_PLAIN_PARTIALS), on the GPU box
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-result", *flags, *extra,
@@ -61,7 +67,7 @@ def build_host(force=False, verbose=False, curve="curve25519"):
     suffix, flags = CURVES[curve]
     hdir = os.path.join(HERE, "host")
     target = os.path.join(HERE, f"liblasso_prover{suffix}.so")
-    sources = _glob(hdir, (".cpp", ".hpp")) + _glob(os.path.join(HERE, "csrc"), (".cuh",)) + [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_hip_msm.h", "lasso_hip_operands.h", "lasso_hip_gens.h", "lasso_hip_mle.h", "lasso_hip_values.h", "lasso_hip_poly.h", "lasso_prover.h", "lasso_prover_mle.h", "lasso_prover_values.h", "lasso_prover_poly.h", "lasso_custom_check.h")]
+    sources = _glob(hdir, (".cpp", ".hpp")) + _glob(os.path.join(HERE, "csrc"), (".cuh",)) + _headers("lasso_hip") + _headers("lasso_prover")
     if not os.path.exists(os.path.join(hdir, "prover_capi.cpp")):
         return None
     dev = build_device(force=False, verbose=verbose, curve=curve)

@@ -59,6 +59,10 @@ class Device:
         if rc != 0:
             raise LassoError(f"lasso error {rc}: {self.lib.lasso_last_error(self.ctx).decode()}")
 
+    def _ext(self, name):
+        """the library with the optional extension `name` (_abi.EXTENSIONS) declared on first use; LassoError when the library does not export it"""
+        return _abi.declared_ext(self, name, _abi.EXTENSIONS, "device", LassoError)
+
     # ---- memory
     def alloc(self, nbytes):
         p = C.c_void_p()
@@ -291,12 +295,7 @@ class Device:
         """ark-serialize compressed points decoded and validated on the device (include/lasso_hip_wire.h lasso_points_decompress): `wire` = n x 32 bytes (bytes, or a uint8
         array).  Returns (affine (n, 8) uint64 as bases_create takes it, canonical (n, 32) uint8, status (n,) uint8 — _abi.WIRE_STATUS names the values); rejected
         encodings leave zero rows.  A library without the decoder is an error, not a fall-back."""
-        if not hasattr(self, "_wire"):
-            try:
-                _abi.declare_wire(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_points_decompress (include/lasso_hip_wire.h)")
-            self._wire = True
+        self._ext("wire")
         w = np.ascontiguousarray(np.frombuffer(wire, dtype=np.uint8) if isinstance(wire, (bytes, bytearray, memoryview)) else np.asarray(wire, dtype=np.uint8)).reshape(-1)
         if w.size % 32:
             raise LassoError("points_decompress: the input is not a whole number of 32-byte encodings")
@@ -309,12 +308,7 @@ class Device:
         """candidates of a label's generator stream turned into points on the device (include/lasso_hip_gens.h lasso_points_from_candidates): `limbs` = (n, 4) uint64, the
         Montgomery representation of the coordinate as the stream yields it; `greatest` = (n,) root choices.  Returns (affine (n, 8) uint64 as bases_create takes it,
         status (n,) uint8 — _abi.CAND_STATUS names the values); a candidate without a point leaves a zero row.  A library without the entry is an error, not a fall-back."""
-        if not hasattr(self, "_gens"):
-            try:
-                _abi.declare_gens(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_points_from_candidates (include/lasso_hip_gens.h)")
-            self._gens = True
+        self._ext("gens")
         limbs = np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)
         g = np.ascontiguousarray(np.asarray(greatest).astype(bool), dtype=np.uint8).reshape(-1)
         n = limbs.shape[0]
@@ -359,20 +353,11 @@ class Device:
         self._chk(self.lib.lasso_msm(self.ctx, C.c_void_p(bases), _vp(scalars), scalars.shape[0], _vp(out)))
         return out
 
-    def _msm_points_fn(self, name):
-        if not hasattr(self, "_msm_points_ok"):
-            try:
-                _abi.declare_msm_points(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_msm_points (include/lasso_hip_msm.h)")
-            self._msm_points_ok = True
-        return getattr(self.lib, name)
-
     def msm_points(self, points, scalars):
         """sum_j scalars[j] * points[j] over the caller's own points, nothing prepared (include/lasso_hip_msm.h lasso_msm_points): `points` = (n, 8) uint64 affine
         Montgomery limbs as bases_create takes them (an all-zero row is the identity), `scalars` = (n, 4) uint64.  Returns a (1, 16) projective point, as msm does.
         A library without the entry point is an error, not a fall-back."""
-        fn = self._msm_points_fn("lasso_msm_points")
+        fn = self._ext("msm_points").lasso_msm_points
         points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
         scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
         if points.shape[0] != scalars.shape[0]:
@@ -383,25 +368,16 @@ class Device:
 
     def msm_points_dev(self, d_points, d_scalars, n):
         """msm_points over arrays that are already on the device (lasso_msm_points_dev)"""
-        fn = self._msm_points_fn("lasso_msm_points_dev")
+        fn = self._ext("msm_points").lasso_msm_points_dev
         out = np.empty((1, 16), dtype=np.uint64)
         self._chk(fn(self.ctx, C.c_void_p(d_points), C.c_void_p(d_scalars), n, _vp(out)))
         return out
-
-    def _tables_mle_fn(self, name):
-        if not hasattr(self, "_mle_ok"):
-            try:
-                _abi.declare_mle(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_tables_mle (include/lasso_hip_mle.h)")
-            self._mle_ok = True
-        return getattr(self.lib, name)
 
     def tables_mle(self, tables, point):
         """out[k] = sum_i tables[k][i] * EqPolynomial(point).evals()[i] (include/lasso_hip_mle.h lasso_tables_mle): `tables` = up to 32 host arrays of one form — all 1-D
         uint32 of 2^log_m entries, or all (2^log_m, 4) uint64 memory words — and `point` = (log_m, 4) uint64.  Returns (len(tables), 4) uint64, fully reduced.  A library
         without the entry point is an error, not a fall-back."""
-        fn = self._tables_mle_fn("lasso_tables_mle")
+        fn = self._ext("mle").lasso_tables_mle
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
         tables = [np.asarray(t) for t in tables]
         field = bool(tables) and tables[0].ndim == 2
@@ -417,7 +393,7 @@ class Device:
 
     def tables_mle_dev(self, d_tables, point, field):
         """tables_mle over tables that are already on the device (lasso_tables_mle_dev): `d_tables` = device pointers, `field` = whether they hold field elements"""
-        fn = self._tables_mle_fn("lasso_tables_mle_dev")
+        fn = self._ext("mle").lasso_tables_mle_dev
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
         ptrs = self._ptrs(list(d_tables))
         out = np.zeros((len(d_tables), 4), dtype=np.uint64)
@@ -429,40 +405,26 @@ class Device:
         lasso_amd.custom.strategy_ptr makes it, `d_dims` = c device pointers to n addresses each, `d_tables` = the subtables' device pointers (`field_tables`: field
         elements instead of 32-bit integers), `form` = _abi.VALUES_FR / _abi.VALUES_U64, `d_out` = a device pointer to n elements.  A library without the entry point is
         an error, not a fall-back."""
-        if not hasattr(self, "_values_ok"):
-            try:
-                _abi.declare_values(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_lookup_values (include/lasso_hip_values.h)")
-            self._values_ok = True
+        self._ext("values")
         dims, tabs = self._ptrs(list(d_dims)), self._ptrs(list(d_tables))
         self._chk(self.lib.lasso_lookup_values(self.ctx, strategy, dims, tabs if not field_tables else None, tabs if field_tables else None, n, form, C.c_void_p(d_out)))
-
-    def _poly_fns(self):
-        if not hasattr(self, "_poly_ok"):
-            try:
-                _abi.declare_poly(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_matvec_left_u64_dev (include/lasso_hip_poly.h)")
-            self._poly_ok = True
-        return self.lib
 
     def u64_or(self, d_v, n):
         """the OR of n 64-bit integers on the device (include/lasso_hip_poly.h lasso_u64_or): which bits are populated.  A library without the entry point is an error,
         not a fall-back."""
         out = C.c_uint64(0)
-        self._chk(self._poly_fns().lasso_u64_or(self.ctx, C.c_void_p(d_v), n, C.byref(out)))
+        self._chk(self._ext("poly").lasso_u64_or(self.ctx, C.c_void_p(d_v), n, C.byref(out)))
         return out.value
 
     def hyrax_commit_compressed_u64(self, d_u64, max_value, l_size, r_size, bases):
         """hyrax_commit_compressed for Z[i] = F::from(d_u64[i]), every element at most `max_value` (lasso_hyrax_commit_compressed_u64): (l_size, 32) uint8"""
         out = np.empty((l_size, 32), dtype=np.uint8)
-        self._chk(self._poly_fns().lasso_hyrax_commit_compressed_u64(self.ctx, C.c_void_p(d_u64), max_value, l_size, r_size, C.c_void_p(bases), _vp(out)))
+        self._chk(self._ext("poly").lasso_hyrax_commit_compressed_u64(self.ctx, C.c_void_p(d_u64), max_value, l_size, r_size, C.c_void_p(bases), _vp(out)))
         return out
 
     def matvec_left_u64_dev(self, d_z, d_l, l_size, r_size, d_out):
         """matvec_left_dev over 64-bit integers, enqueued on the context's stream (lasso_matvec_left_u64_dev)"""
-        self._chk(self._poly_fns().lasso_matvec_left_u64_dev(self.ctx, C.c_void_p(d_z), C.c_void_p(d_l), l_size, r_size, C.c_void_p(d_out)))
+        self._chk(self._ext("poly").lasso_matvec_left_u64_dev(self.ctx, C.c_void_p(d_z), C.c_void_p(d_l), l_size, r_size, C.c_void_p(d_out)))
 
     def msm_dev(self, bases, d_scalars, n):
         out = np.empty((1, 16), dtype=np.uint64)
@@ -498,12 +460,7 @@ class Device:
         """densify_dim with the dimension's addresses formed on the device from operand columns (include/lasso_hip_operands.h lasso_densify_dim_operands): d_x, d_y = device
         pointers of n_lookups uint64 each (d_y None for a one-operand layout), layout = _abi.OperandLayout; world / rank as lasso_densify_dim_slab.  A library without
         the entry point is an error, not a fall-back."""
-        if not hasattr(self, "_operands"):
-            try:
-                _abi.declare_operands(self.lib)
-            except AttributeError:
-                raise LassoError("this device library does not export lasso_densify_dim_operands (include/lasso_hip_operands.h)")
-            self._operands = True
+        self._ext("operands")
         self._chk(self.lib.lasso_densify_dim_operands(self.ctx, C.c_void_p(d_x), C.c_void_p(d_y) if d_y else None, n_lookups, C.byref(layout), c, dim, s, log_m, world, rank,
                                                       C.c_void_p(d_dim_u32), C.c_void_p(d_dim), C.c_void_p(d_read), C.c_void_p(d_final)))
 

@@ -18,47 +18,43 @@
 
 using namespace lasso;
 
-// The device decoder of compressed points is an OPTIONAL part of the device library (include/lasso_hip_wire.h, not lasso_hip.h): a weak reference, null when these
-// sources are linked against an implementation of lasso_hip.h alone — the verifier then decodes on the host, and lasso_host_points_decompress(where = 1) says so.
+// ---- The optional parts of the device ABI, stated once.  Each is a header beside include/lasso_hip.h whose entry points are WEAK references here: null when these sources are
+// linked against an implementation of lasso_hip.h alone.  The host then takes the route it had before the entry existed (named per line below), and a call that cannot do
+// without the entry refuses in ext_unavailable's words.  Where the entry exists a switch (switches.hpp) can still keep the earlier route: the A/B handle.
+// wire: the verifier decodes on the host.  LASSO_VERIFY_DEVICE_POINTS=0 keeps that; LASSO_WIRE_DEVICE_MIN = the smallest batch handed over (default: the smallest MEASURED ahead, profiles/verify_device_points.json)
 extern "C" int32_t lasso_points_decompress(lasso_ctx*, const uint8_t*, size_t, lasso_affine*, uint8_t*, uint8_t*) __attribute__((weak));
-// switches.hpp: LASSO_VERIFY_DEVICE_POINTS=0: the verifier decodes every point on the host, as it did before the device decoder existed.
-// LASSO_WIRE_DEVICE_MIN: the smallest batch the verifier hands to the device.  The default is the smallest batch MEASURED with the device ahead (376 points: AND, C = 1,
-// 2^10 lookups on curve25519, 91 ms -> 59 ms; profiles/verify_device_points.json) — smaller batches have not been measured and stay on the host.
-
-// The table-free MSM over caller points (include/lasso_hip_msm.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone — the
-// verifier's MSMs over commitment rows then build a lasso_bases per call as before.  LASSO_VERIFY_MSM_POINTS=0 keeps that path where the entry point exists (A/B switch).
-// No size threshold (LASSO_MSM_POINTS_MIN) yet: tools/verify_bench.py --ab msm_points is what one would be set from.
+// msm: the verifier's MSMs over commitment rows build a lasso_bases per call.  LASSO_VERIFY_MSM_POINTS=0 keeps that; no size threshold yet (tools/verify_bench.py --ab msm_points is what one would be set from)
 extern "C" int32_t lasso_msm_points(lasso_ctx*, const lasso_affine*, const lasso_fr*, size_t, lasso_point*) __attribute__((weak));
-
-// Densify from operand columns (include/lasso_hip_operands.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
-// lasso_host_densify_operands then expands the operands to indices on the host (lasso_host_operand_indices) and takes lasso_host_densify's path.
-// LASSO_DENSIFY_OPERANDS=0 does the same where the entry point exists (A/B switch).
+// operands: lasso_host_densify_operands expands the operands to indices on the host and takes lasso_host_densify's path.  LASSO_DENSIFY_OPERANDS=0 does the same
 extern "C" int32_t lasso_densify_dim_operands(lasso_ctx*, const uint64_t*, const uint64_t*, size_t, const lasso_operand_layout*, size_t, size_t, size_t, uint32_t, uint32_t, uint32_t, uint32_t*, lasso_fr*,
                                               lasso_fr*, lasso_fr*) __attribute__((weak));
-
-// The arithmetic of label-derived generators (include/lasso_hip_gens.h) is optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
-// lasso_host_gens_new then builds every point on the host, and lasso_host_points_from_candidates(where = 1) says so.  LASSO_GENS_DEVICE=0 keeps the host route where the
-// entry point exists; LASSO_GENS_DEVICE_MIN is the smallest set that goes to the device, LASSO_GENS_DEVICE_BATCH caps the candidates per call (switches.hpp).
+// gens: lasso_host_gens_new builds every point on the host.  LASSO_GENS_DEVICE=0 keeps that; LASSO_GENS_DEVICE_MIN = the smallest set that goes over, LASSO_GENS_DEVICE_BATCH caps the candidates per call
 extern "C" int32_t lasso_points_from_candidates(lasso_ctx*, const uint64_t*, const uint8_t*, size_t, lasso_affine*, uint8_t*) __attribute__((weak));
-
-// The MLEs of caller-defined subtables on the device (include/lasso_hip_mle.h) are optional in the same way: a weak reference, null against an implementation of lasso_hip.h
-// alone — the verifier then keeps its host loop (2^log_m products per subtable), and lasso_host_tables_mle(where = 1) says so.  LASSO_VERIFY_DEVICE_MLE=0 keeps the host loop
-// where the entry point exists; LASSO_MLE_DEVICE_MIN is the smallest num_subtables * 2^log_m that goes to the device (switches.hpp).
+// mle: the verifier keeps its host loop (2^log_m products per subtable).  LASSO_VERIFY_DEVICE_MLE=0 keeps that; LASSO_MLE_DEVICE_MIN = the smallest num_subtables * 2^log_m that goes over
 extern "C" int32_t lasso_tables_mle(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
-
-// The lookup results as a vector (include/lasso_hip_values.h) are optional in the same way: a weak reference, null against an implementation of lasso_hip.h alone —
-// lasso_host_lookup_values then says so; lasso_host_lookup_values_ref needs no device.  lasso_host_values_evaluate takes lasso_tables_mle above (host vectors) or its
-// device-resident form.
-extern "C" int32_t lasso_lookup_values(lasso_ctx*, const lasso_strategy*, const uint32_t* const*, const uint32_t* const*, const lasso_fr* const*, size_t, int32_t, void*) __attribute__((weak));
 extern "C" int32_t lasso_tables_mle_dev(lasso_ctx*, const uint32_t* const*, const lasso_fr* const*, uint32_t, uint32_t, const lasso_fr*, lasso_fr*) __attribute__((weak));
-
-// A vector of 64-bit integers as a polynomial (include/lasso_hip_poly.h) is optional in the same way: weak references, null against an implementation of lasso_hip.h alone —
-// lasso_host_poly_commit / lasso_host_poly_open then lift the integers to field elements on the host and take lasso_hyrax_commit_compressed / lasso_matvec_left_dev: the
-// same bytes.  The three are used together or not at all.
+// values: lasso_host_lookup_values refuses (lasso_host_lookup_values_ref needs no device); lasso_host_values_evaluate takes mle's entry for where its vector lives
+extern "C" int32_t lasso_lookup_values(lasso_ctx*, const lasso_strategy*, const uint32_t* const*, const uint32_t* const*, const lasso_fr* const*, size_t, int32_t, void*) __attribute__((weak));
+// poly: lasso_host_poly_commit / lasso_host_poly_open lift the integers on the host and take lasso_hyrax_commit_compressed / lasso_matvec_left_dev: the same bytes.  The three are used together or not at all
 extern "C" int32_t lasso_u64_or(lasso_ctx*, const uint64_t*, size_t, uint64_t*) __attribute__((weak));
 extern "C" int32_t lasso_hyrax_commit_compressed_u64(lasso_ctx*, const uint64_t*, uint64_t, size_t, size_t, const lasso_bases*, uint8_t*) __attribute__((weak));
 extern "C" int32_t lasso_matvec_left_u64_dev(lasso_ctx*, const uint64_t*, const lasso_fr*, size_t, size_t, lasso_fr*) __attribute__((weak));
-static bool poly_u64_device() { return lasso_u64_or && lasso_hyrax_commit_compressed_u64 && lasso_matvec_left_u64_dev; }
+
+// One row per extension, under the name lasso_amd/_abi.py EXTENSIONS and the tests' mock (-DMOCK_EXT_<NAME>) know it by: its header, what a refusal calls the entry, whether
+// the device library has it, and (lasso_host::ext_count) up to two counters that its lasso_host_*_stats reports.
+enum Ext { EXT_WIRE, EXT_MSM_POINTS, EXT_OPERANDS, EXT_GENS, EXT_MLE, EXT_VALUES, EXT_POLY, EXT_COUNT };
+static const struct { const char *name, *header, *what, *entry; bool (*available)(); } EXTS[EXT_COUNT] = {
+  {"wire", "lasso_hip_wire.h", "the device decoder", "lasso_points_decompress", [] { return lasso_points_decompress != nullptr; }},                 // [0]: compressed points decoded on the device
+  {"msm_points", "lasso_hip_msm.h", "the MSM over caller points", "lasso_msm_points", [] { return lasso_msm_points != nullptr; }},                // [0]: Verifier::msm_points calls that took it
+  {"operands", "lasso_hip_operands.h", "the device entry", "lasso_densify_dim_operands", [] { return lasso_densify_dim_operands != nullptr; }},   // [0]: dimensions densified by it
+  {"gens", "lasso_hip_gens.h", "the device entry", "lasso_points_from_candidates", [] { return lasso_points_from_candidates != nullptr; }},       // [0]: candidates handed to it
+  {"mle", "lasso_hip_mle.h", "the device entry", "lasso_tables_mle", [] { return lasso_tables_mle != nullptr; }},                                 // [0]: caller-defined tables evaluated by it
+  {"values", "lasso_hip_values.h", "the device entry", "lasso_lookup_values", [] { return lasso_lookup_values != nullptr; }},                     // [0]: elements it wrote
+  {"poly", "lasso_hip_poly.h", "the device entry", "lasso_matvec_left_u64_dev", [] { return lasso_u64_or && lasso_hyrax_commit_compressed_u64 && lasso_matvec_left_u64_dev; }},   // [0], [1]: 64-bit elements committed to / opened
+};
+static Error ext_unavailable(const char* who, Ext e, const char* entry = nullptr) {
+  return Error(std::string(who) + ": " + EXTS[e].what + " (" + (entry ? entry : EXTS[e].entry) + ", include/" + EXTS[e].header + ") is not available in the device library this host was linked against");
+}
 
 // Generator and dense-representation objects hold device buffers that belong to their host's context (DBuf keeps a `const Dev*`), so the host
 // must outlive them: it is reference-counted by its children, and lasso_host_destroy only drops the caller's reference — the context goes away
@@ -66,17 +62,11 @@ static bool poly_u64_device() { return lasso_u64_or && lasso_hyrax_commit_compre
 struct lasso_host {
   Dev dev; std::atomic<int> refs{1};
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
-  uint64_t wire_device_points = 0;   // compressed points decoded by lasso_points_decompress for this host (lasso_host_wire_stats)
-  uint64_t msm_points_calls = 0;     // Verifier::msm_points calls of this host that took lasso_msm_points (lasso_host_msm_stats)
-  uint64_t operand_dims = 0;         // dimensions densified by lasso_densify_dim_operands for this host (lasso_host_densify_stats)
-  uint64_t gens_device_candidates = 0;   // candidates handed to lasso_points_from_candidates for this host (lasso_host_gens_stats)
-  uint64_t mle_device_tables = 0;        // caller-defined tables evaluated by lasso_tables_mle for this host (lasso_host_mle_stats)
-  uint64_t values_device_lookups = 0;    // elements lasso_lookup_values wrote for this host (lasso_host_values_stats)
-  uint64_t poly_u64_commit_elems = 0, poly_u64_open_elems = 0;   // 64-bit elements committed to / opened through include/lasso_hip_poly.h for this host (lasso_host_poly_stats)
-  TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = &mle_device_tables; } return m; }
-  GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = &gens_device_candidates; } return g; }
-  PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = &msm_points_calls; } return m; }
-  WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = &wire_device_points; } return w; }
+  uint64_t ext_count[EXT_COUNT][2] = {};   // the counters of EXTS' rows, for this host
+  TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = ext_count[EXT_MLE]; } return m; }
+  GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = ext_count[EXT_GENS]; } return g; }
+  PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = ext_count[EXT_MSM_POINTS]; } return m; }
+  WireDecoder wire_decoder() { WireDecoder w; if (lasso_points_decompress && sw::verify_device_points()) { w.fn = &lasso_points_decompress; w.min_points = sw::wire_device_min(); w.counter = ext_count[EXT_WIRE]; } return w; }
   explicit lasso_host(int device) : dev(device) {}
   void retain() { refs.fetch_add(1, std::memory_order_relaxed); }
   void release() { if (refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete this; }
@@ -103,6 +93,17 @@ struct lasso_host_poly_gens {
 static thread_local std::string g_err;
 #define GUARD(...) try { __VA_ARGS__ } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
 static int32_t emit(const std::vector<uint8_t>& b, uint8_t* out, size_t cap, size_t* len) { if (len) *len = b.size(); if (!out || b.size() > cap) { g_err = "output buffer too small"; return -2; } memcpy(out, b.data(), b.size()); return 0; }
+// every lasso_host_*_stats: the row's counters (c1 only where the row has two), whether the device library has the extension, and the reset
+static int32_t ext_stats(const char* who, lasso_host* h, Ext e, uint64_t* c0, uint64_t* c1, int32_t* available, int32_t reset) {
+  GUARD(
+    if (!h) throw Error(std::string(who) + ": null host");
+    uint64_t* c = h->ext_count[e];
+    if (c0) *c0 = c[0];
+    if (c1) *c1 = c[1];
+    if (available) *available = EXTS[e].available() ? 1 : 0;
+    if (reset) c[0] = c[1] = 0;
+    return 0;)
+}
 
 extern "C" {
 const char* lasso_host_last_error(void) { return g_err.c_str(); }
@@ -239,18 +240,11 @@ int32_t lasso_host_densify_operands(lasso_host* h, const lasso_operand_layout* L
     if (where == 1 && !device)
       throw Error("lasso_host_densify_operands: device-resident operands need lasso_densify_dim_operands (include/lasso_hip_operands.h), which the device library this host was linked against does not have (or LASSO_DENSIFY_OPERANDS=0 keeps out)");
     std::unique_ptr<lasso_host_dense> d(new lasso_host_dense(h));
-    if (device) d->d = DensifiedRepresentation::from_operands(h->dev, &lasso_densify_dim_operands, *L, x, y, where == 1, n, c, log_m, &h->operand_dims);
+    if (device) d->d = DensifiedRepresentation::from_operands(h->dev, &lasso_densify_dim_operands, *L, x, y, where == 1, n, c, log_m, h->ext_count[EXT_OPERANDS]);
     else { std::vector<uint64_t> idx(n * c); expand_operands(*L, x, y, n, c, idx.data()); d->d = DensifiedRepresentation::from_lookup_indices(h->dev, idx.data(), n, c, log_m); }
     *out = d.release(); return 0;)
 }
-int32_t lasso_host_densify_stats(lasso_host* h, uint64_t* operand_dims_on_device, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_densify_stats: null host");
-    if (operand_dims_on_device) *operand_dims_on_device = h->operand_dims;
-    if (available) *available = lasso_densify_dim_operands ? 1 : 0;
-    if (reset) h->operand_dims = 0;
-    return 0;)
-}
+int32_t lasso_host_densify_stats(lasso_host* h, uint64_t* operand_dims_on_device, int32_t* available, int32_t reset) { return ext_stats("lasso_host_densify_stats", h, EXT_OPERANDS, operand_dims_on_device, nullptr, available, reset); }
 int32_t lasso_host_dense_info(lasso_host_dense* d, uint64_t* device_bytes, int32_t* compact) {
   if (!d || !d->d) return LASSO_ERR_INVALID;
   const DensifiedRepresentation& D = *d->d;
@@ -389,46 +383,32 @@ int32_t lasso_host_points_decompress(lasso_host* h, const uint8_t* wire32, size_
   GUARD(
     if (!h || !status || (!wire32 && n) || (where != 0 && where != 1)) throw Error("lasso_host_points_decompress: null argument, or `where` is neither 0 (host) nor 1 (device)");
     if (where == 1) {
-      if (!lasso_points_decompress) throw Error("lasso_host_points_decompress: the device decoder (lasso_points_decompress, include/lasso_hip_wire.h) is not available in the device library this host was linked against");
+      if (!lasso_points_decompress) throw ext_unavailable("lasso_host_points_decompress", EXT_WIRE);
       h->dev.chk(lasso_points_decompress(h->dev.ctx, wire32, n, out, canon32, status), "lasso_points_decompress");
-      h->wire_device_points += n;
+      h->ext_count[EXT_WIRE][0] += n;
       return 0;
     }
     for (size_t i = 0; i < n; i++) status[i] = decompress_point_abi(wire32 + 32 * i, out ? out + i : nullptr, canon32 ? canon32 + 32 * i : nullptr);
     return 0;)
 }
-int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* device_available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_wire_stats: null host");
-    if (device_points) *device_points = h->wire_device_points;
-    if (device_available) *device_available = lasso_points_decompress ? 1 : 0;
-    if (reset) h->wire_device_points = 0;
-    return 0;)
-}
+int32_t lasso_host_wire_stats(lasso_host* h, uint64_t* device_points, int32_t* device_available, int32_t reset) { return ext_stats("lasso_host_wire_stats", h, EXT_WIRE, device_points, nullptr, device_available, reset); }
 int32_t lasso_host_msm_points(lasso_host* h, const lasso_affine* points, const lasso_fr* scalars, size_t n, uint8_t* out_compressed32) {
   GUARD(
     if (!h || !out_compressed32 || (n && (!points || !scalars))) throw Error("lasso_host_msm_points: null argument");
-    if (!lasso_msm_points) throw Error("lasso_host_msm_points: the MSM over caller points (lasso_msm_points, include/lasso_hip_msm.h) is not available in the device library this host was linked against");
+    if (!lasso_msm_points) throw ext_unavailable("lasso_host_msm_points", EXT_MSM_POINTS);
     lasso_point out;
     h->dev.chk(lasso_msm_points(h->dev.ctx, points, scalars, n, &out), "lasso_msm_points");
     compress_one(Pt::from_abi(out), out_compressed32);
     return 0;)
 }
-int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_msm_stats: null host");
-    if (points_calls) *points_calls = h->msm_points_calls;
-    if (available) *available = lasso_msm_points ? 1 : 0;
-    if (reset) h->msm_points_calls = 0;
-    return 0;)
-}
+int32_t lasso_host_msm_stats(lasso_host* h, uint64_t* points_calls, int32_t* available, int32_t reset) { return ext_stats("lasso_host_msm_stats", h, EXT_MSM_POINTS, points_calls, nullptr, available, reset); }
 int32_t lasso_host_points_from_candidates(lasso_host* h, const uint64_t* limbs, const uint8_t* greatest, size_t n, int32_t where, lasso_affine* out, uint8_t* status) {
   GUARD(
     if (!h || !status || ((!limbs || !greatest) && n) || (where != 0 && where != 1)) throw Error("lasso_host_points_from_candidates: null argument, or `where` is neither 0 (host) nor 1 (device)");
     if (where == 1) {
-      if (!lasso_points_from_candidates) throw Error("lasso_host_points_from_candidates: the device entry (lasso_points_from_candidates, include/lasso_hip_gens.h) is not available in the device library this host was linked against");
+      if (!lasso_points_from_candidates) throw ext_unavailable("lasso_host_points_from_candidates", EXT_GENS);
       h->dev.chk(lasso_points_from_candidates(h->dev.ctx, limbs, greatest, n, out, status), "lasso_points_from_candidates");
-      h->gens_device_candidates += n;
+      h->ext_count[EXT_GENS][0] += n;
       return 0;
     }
     for (size_t i = 0; i < n; i++) {
@@ -439,14 +419,7 @@ int32_t lasso_host_points_from_candidates(lasso_host* h, const uint64_t* limbs, 
     }
     return 0;)
 }
-int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_gens_stats: null host");
-    if (device_candidates) *device_candidates = h->gens_device_candidates;
-    if (available) *available = lasso_points_from_candidates ? 1 : 0;
-    if (reset) h->gens_device_candidates = 0;
-    return 0;)
-}
+int32_t lasso_host_gens_stats(lasso_host* h, uint64_t* device_candidates, int32_t* available, int32_t reset) { return ext_stats("lasso_host_gens_stats", h, EXT_GENS, device_candidates, nullptr, available, reset); }
 // include/lasso_prover_mle.h: SubtableStrategy::evaluate_subtable_mle for every subtable of a strategy of any kind
 int32_t lasso_host_tables_mle(lasso_host* h, const lasso_strategy* st, const lasso_fr* point, size_t point_len, int32_t where, lasso_fr* out) {
   GUARD(
@@ -456,8 +429,8 @@ int32_t lasso_host_tables_mle(lasso_host* h, const lasso_strategy* st, const las
     ScVec pt; for (size_t i = 0; i < point_len; i++) pt.push_back(Sc::from_abi(point[i]));
     const size_t n = S.num_subtables();
     if (S.custom() && where == 1) {
-      if (!lasso_tables_mle) throw Error("lasso_host_tables_mle: the device entry (lasso_tables_mle, include/lasso_hip_mle.h) is not available in the device library this host was linked against");
-      TablesMle m; m.fn = &lasso_tables_mle; m.counter = &h->mle_device_tables;
+      if (!lasso_tables_mle) throw ext_unavailable("lasso_host_tables_mle", EXT_MLE);
+      TablesMle m; m.fn = &lasso_tables_mle; m.counter = h->ext_count[EXT_MLE];
       std::vector<size_t> ks(n); for (size_t k = 0; k < n; k++) ks[k] = k;
       const ScVec v = custom_subtable_mles_device(h->dev, S, m, ks, pt);
       for (size_t k = 0; k < n; k++) out[k] = v[k].abi();
@@ -466,14 +439,7 @@ int32_t lasso_host_tables_mle(lasso_host* h, const lasso_strategy* st, const las
     for (size_t k = 0; k < n; k++) out[k] = evaluate_subtable_mle(S, k, pt).abi();
     return 0;)
 }
-int32_t lasso_host_mle_stats(lasso_host* h, uint64_t* device_tables, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_mle_stats: null host");
-    if (device_tables) *device_tables = h->mle_device_tables;
-    if (available) *available = lasso_tables_mle ? 1 : 0;
-    if (reset) h->mle_device_tables = 0;
-    return 0;)
-}
+int32_t lasso_host_mle_stats(lasso_host* h, uint64_t* device_tables, int32_t* available, int32_t reset) { return ext_stats("lasso_host_mle_stats", h, EXT_MLE, device_tables, nullptr, available, reset); }
 // ---- include/lasso_prover_values.h: the lookup results as a vector, a vector's evaluation at r, the claim inside the proof bytes
 // the refusal of the 64-bit form in the words the device entry reports it with (Dev::chk of lasso_lookup_values' LASSO_ERR_UNSUPPORTED): one text whichever route ran
 static void values_check_form(const Strategy& S, int32_t form) {
@@ -534,7 +500,7 @@ int32_t lasso_host_lookup_values(lasso_host* h, lasso_host_dense* dn, const lass
     if (S.C() != D.C || S.abi.log_m != D.log_m) throw Error("lasso_host_lookup_values: the strategy's c / log_m do not match the densified representation");
     if (d.comm.sharded() || D.s_loc != D.s) throw Error("lasso_host_lookup_values: a slab-mode representation holds one residue class of the lookups per rank; the values of a sharded proof are not offered");
     values_check_form(S, form);
-    if (!lasso_lookup_values) throw Error("lasso_host_lookup_values: the device entry (lasso_lookup_values, include/lasso_hip_values.h) is not available in the device library this host was linked against");
+    if (!lasso_lookup_values) throw ext_unavailable("lasso_host_lookup_values", EXT_VALUES);
     // the tables on the device, as Prover::prove makes them (materialised by the device, Spark's eq tables, or the caller's uploaded); they go back to the pool on return
     const size_t m = D.m, s = D.s; const bool ints = S.integer_tables();
     std::vector<DBufU32> tu; std::vector<DBuf> tf; std::vector<const uint32_t*> pu; std::vector<const lasso_fr*> pf;
@@ -559,7 +525,7 @@ int32_t lasso_host_lookup_values(lasso_host* h, lasso_host_dense* dn, const lass
       if (out_on_device) d.chk(lasso_sync(d.ctx), "lasso_sync"); else d.chk(lasso_download(d.ctx, out, d_out, bytes), "lasso_download");
     } catch (...) { if (!out_on_device) d.free(d_out); throw; }
     if (!out_on_device) d.free(d_out);
-    h->values_device_lookups += s;
+    h->ext_count[EXT_VALUES][0] += s;
     return 0;)
 }
 int32_t lasso_host_dense_len(lasso_host_dense* dn, size_t* s) { GUARD(if (!dn || !dn->d || !s) throw Error("lasso_host_dense_len: null argument"); *s = dn->d->s; return 0;) }
@@ -572,7 +538,7 @@ int32_t lasso_host_values_evaluate(lasso_host* h, const lasso_fr* values, int32_
       *out = (Sc::from_abi(v) * Sc::one()).abi(); return 0;
     }
     auto fn = on_device ? lasso_tables_mle_dev : lasso_tables_mle;
-    if (!fn) throw Error("lasso_host_values_evaluate: the device entry (lasso_tables_mle / lasso_tables_mle_dev, include/lasso_hip_mle.h) is not available in the device library this host was linked against");
+    if (!fn) throw ext_unavailable("lasso_host_values_evaluate", EXT_MLE, "lasso_tables_mle / lasso_tables_mle_dev");
     const lasso_fr* one[1] = {values};
     h->dev.chk(fn(h->dev.ctx, nullptr, one, 1, (uint32_t)r_len, r, out), on_device ? "lasso_tables_mle_dev" : "lasso_tables_mle");
     return 0;)
@@ -586,14 +552,7 @@ int32_t lasso_host_proof_claimed_evaluation(const uint8_t* proof, size_t proof_l
     *out = r.sc().abi();
     return 0;)
 }
-int32_t lasso_host_values_stats(lasso_host* h, uint64_t* device_lookups, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_values_stats: null host");
-    if (device_lookups) *device_lookups = h->values_device_lookups;
-    if (available) *available = lasso_lookup_values ? 1 : 0;
-    if (reset) h->values_device_lookups = 0;
-    return 0;)
-}
+int32_t lasso_host_values_stats(lasso_host* h, uint64_t* device_lookups, int32_t* available, int32_t reset) { return ext_stats("lasso_host_values_stats", h, EXT_VALUES, device_lookups, nullptr, available, reset); }
 // ---- include/lasso_prover_poly.h: a commitment to the caller's vector and its opening at a point
 }  // extern "C"
 // The caller's vector where the device calls read it: 64-bit integers as they are when the device library has include/lasso_hip_poly.h, field elements otherwise (lifted on
@@ -618,7 +577,7 @@ static void poly_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, 
 static void poly_operand(lasso_host* h, const void* values, int32_t form, int32_t on_device, size_t s, PolyOperand& o) {
   const Dev& d = h->dev; o.dev = &d;
   const size_t elem = form == LASSO_VALUES_U64 ? sizeof(uint64_t) : sizeof(lasso_fr);
-  if (form == LASSO_VALUES_U64 && !poly_u64_device()) {   // the device library is an implementation of lasso_hip.h alone: F::from on the host, the 32-byte entries from there on
+  if (form == LASSO_VALUES_U64 && !EXTS[EXT_POLY].available()) {   // the device library is an implementation of lasso_hip.h alone: F::from on the host, the 32-byte entries from there on
     std::vector<uint64_t> v(s);
     if (on_device) d.chk(lasso_download(d.ctx, v.data(), values, s * 8), "lasso_download"); else memcpy(v.data(), values, s * 8);
     std::vector<lasso_fr> f(s); for (size_t i = 0; i < s; i++) f[i] = Sc::from_u64(v[i]).abi();
@@ -666,7 +625,7 @@ int32_t lasso_host_poly_commit(lasso_host* h, lasso_host_poly_gens* g, const voi
       d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
       c.rows = L; c.compressed.resize(32 * L);
       d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, L, R, g->g->bases, c.compressed.data()), "lasso_hyrax_commit_compressed_u64");
-      h->poly_u64_commit_elems += s;
+      h->ext_count[EXT_POLY][0] += s;
     } else c = hyrax_commit(d, (const lasso_fr*)o.d, nv, *g->g);
     ProofWriter w; w.pts_vec(c.compressed);
     return emit(w.b, out, cap, len);)
@@ -693,7 +652,7 @@ int32_t lasso_host_poly_open(lasso_host* h, lasso_host_poly_gens* g, const void*
     PolyOperand o; poly_operand(h, values, form, on_device, s, o);
     Sc y; DotProductProofLog P;
     try { P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g); } catch (...) { h->dev.abort_all(); throw; }
-    if (o.u64) h->poly_u64_open_elems += s;
+    if (o.u64) h->ext_count[EXT_POLY][1] += s;
     if (Zr) *Zr = (y * Sc::one()).abi();
     ProofWriter w; P.write(w);
     return emit(w.b, proof, cap, len);)
@@ -716,15 +675,7 @@ int32_t lasso_host_poly_verify(lasso_host* h, lasso_host_poly_gens* g, const las
     *ok = Verifier::poly_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, rv, Sc::from_abi(*Zr), comm) ? 1 : 0;
     return 0;)
 }
-int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint64_t* u64_open_elements, int32_t* available, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_poly_stats: null host");
-    if (u64_commit_elements) *u64_commit_elements = h->poly_u64_commit_elems;
-    if (u64_open_elements) *u64_open_elements = h->poly_u64_open_elems;
-    if (available) *available = poly_u64_device() ? 1 : 0;
-    if (reset) h->poly_u64_commit_elems = h->poly_u64_open_elems = 0;
-    return 0;)
-}
+int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint64_t* u64_open_elements, int32_t* available, int32_t reset) { return ext_stats("lasso_host_poly_stats", h, EXT_POLY, u64_commit_elements, u64_open_elements, available, reset); }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {
   GUARD(const Strategy S = Strategy::from_abi(st); (void)S; return 0;)
 }

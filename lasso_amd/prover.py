@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from . import _abi
+from ._abi import APPEND_FN, CHALLENGE_FN, TranscriptVtbl  # noqa: F401
 from .custom import strategy_ptr
 from .device import LassoError
 
@@ -24,13 +25,6 @@ def load_prover_library(path=None, curve="curve25519"):
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)   # (user, send, recv, bytes per rank) -> 0
-# include/lasso_prover.h lasso_transcript_vtbl: merlin::Transcript as append_message / challenge_bytes callbacks (labels are pointer + length)
-APPEND_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t)
-CHALLENGE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t)
-
-
-class TranscriptVtbl(C.Structure):
-    _fields_ = [("append_message", APPEND_FN), ("challenge_bytes", CHALLENGE_FN)]
 
 
 def declare_prover(lib):
@@ -104,6 +98,22 @@ class HostProver:
     def _chk(self, rc):
         if rc != 0:
             raise LassoError(f"lasso_host error {rc}: " + self.lib.lasso_host_last_error().decode())
+
+    def _ext(self, name):
+        """the library with the optional prover header `name` (_abi.PROVER_EXTENSIONS) declared on first use; LassoError when the library does not export it"""
+        return _abi.declared_ext(self, name, _abi.PROVER_EXTENSIONS, "prover", LassoError)
+
+    def _values_fns(self):
+        return self._ext("values")
+
+    def _poly_fns(self):
+        return self._ext("poly")
+
+    def _stats(self, fn, reset, *keys):
+        """one lasso_host_*_stats call as a dict: `keys` name its counters and, last, whether the device library has the entry"""
+        counts, avail = [C.c_uint64() for _ in keys[:-1]], C.c_int32()
+        self._chk(fn(self.h, *map(C.byref, counts), C.byref(avail), 1 if reset else 0))
+        return {**{k: v.value for k, v in zip(keys, counts)}, keys[-1]: bool(avail.value)}
 
     def gen_indices(self, s, m, c):
         one = np.empty(s, dtype=np.uint64)
@@ -196,9 +206,7 @@ class HostProver:
     def densify_stats(self, reset=False):
         """{"operand_dims_on_device": dimensions this host densified through lasso_densify_dim_operands so far, "available": whether the device library has that entry}
         (lasso_host_densify_stats)"""
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(self.lib.lasso_host_densify_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"operand_dims_on_device": k.value, "available": bool(a.value)}
+        return self._stats(self.lib.lasso_host_densify_stats, reset, "operand_dims_on_device", "available")
 
     def dense_info(self, dense):
         """device bytes a densified representation holds, and whether dim / read are in capacity mode's compact form"""
@@ -261,9 +269,7 @@ class HostProver:
 
     def wire_stats(self, reset=False):
         """{"device_points": compressed points this host decoded on the device so far, "device_available": whether the device decoder exists} (lasso_host_wire_stats)"""
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(self.lib.lasso_host_wire_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"device_points": k.value, "device_available": bool(a.value)}
+        return self._stats(self.lib.lasso_host_wire_stats, reset, "device_points", "device_available")
 
     def msm_points(self, points, scalars):
         """VariableBaseMSM::msm over the caller's own points, nothing prepared (lasso_host_msm_points): `points` = (n, 8) uint64 affine Montgomery limbs (an all-zero row
@@ -280,9 +286,7 @@ class HostProver:
     def msm_stats(self, reset=False):
         """{"points_calls": the verifier's MSMs over commitment rows that ran table-free on this host so far, "available": whether the device library has
         lasso_msm_points} (lasso_host_msm_stats)"""
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(self.lib.lasso_host_msm_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"points_calls": k.value, "available": bool(a.value)}
+        return self._stats(self.lib.lasso_host_msm_stats, reset, "points_calls", "available")
 
     def points_from_candidates(self, limbs, greatest, where=0):
         """candidates of a label's generator stream -> (affine (n, 8) uint64, status (n,) uint8), on the host (where=0: one after the other) or on the device (where=1:
@@ -300,26 +304,13 @@ class HostProver:
     def gens_stats(self, reset=False):
         """{"device_candidates": generator candidates this host handed to the device so far, "available": whether the device library has
         lasso_points_from_candidates} (lasso_host_gens_stats)"""
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(self.lib.lasso_host_gens_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"device_candidates": k.value, "available": bool(a.value)}
-
-    def _mle_fns(self):
-        """include/lasso_prover_mle.h, declared on first use (a prover library built before that header existed does not export it)"""
-        if not hasattr(self, "_mle_ok"):
-            try:
-                self.lib.lasso_host_tables_mle.argtypes = [C.c_void_p, C.POINTER(_abi.Strategy), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
-                self.lib.lasso_host_mle_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_int32]
-            except AttributeError:
-                raise LassoError("this prover library does not export lasso_host_tables_mle (include/lasso_prover_mle.h)")
-            self._mle_ok = True
-        return self.lib
+        return self._stats(self.lib.lasso_host_gens_stats, reset, "device_candidates", "available")
 
     def tables_mle(self, strategy, point, where=0):
         """SubtableStrategy::evaluate_subtable_mle for every subtable of `strategy` (any kind) at `point` = (log_m, 4) uint64: (num_subtables, 4) uint64, fully reduced.
         Built-in kinds and Spark: their closed forms.  A CustomStrategy: where=0 the host loop, where=1 one lasso_tables_mle call on the device (LassoError when the device
         library has no such entry) — lasso_host_tables_mle"""
-        lib = self._mle_fns()
+        lib = self._ext("mle")
         point = np.ascontiguousarray(point, dtype=np.uint64).reshape(-1, 4)
         kind = strategy.desc.base.kind if hasattr(strategy, "desc") else strategy.kind
         c = strategy.c
@@ -331,26 +322,7 @@ class HostProver:
     def mle_stats(self, reset=False):
         """{"device_tables": caller-defined tables this host evaluated on the device so far, "available": whether the device library has lasso_tables_mle}
         (lasso_host_mle_stats)"""
-        lib = self._mle_fns()
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(lib.lasso_host_mle_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"device_tables": k.value, "available": bool(a.value)}
-
-    def _values_fns(self):
-        """include/lasso_prover_values.h, declared on first use (a prover library built before that header existed does not export it)"""
-        if not hasattr(self, "_values_ok"):
-            vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
-            try:
-                self.lib.lasso_host_lookup_values_ref.argtypes = [C.POINTER(_abi.Strategy), vp, sz, i32, vp, sz, C.POINTER(sz)]
-                self.lib.lasso_host_lookup_values.argtypes = [vp, vp, C.POINTER(_abi.Strategy), i32, i32, vp]
-                self.lib.lasso_host_values_evaluate.argtypes = [vp, vp, i32, sz, vp, sz, vp]
-                self.lib.lasso_host_proof_claimed_evaluation.argtypes = [C.c_char_p, sz, vp]
-                self.lib.lasso_host_values_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(i32), i32]
-                self.lib.lasso_host_dense_len.argtypes = [vp, C.POINTER(sz)]
-            except AttributeError:
-                raise LassoError("this prover library does not export lasso_host_lookup_values (include/lasso_prover_values.h)")
-            self._values_ok = True
-        return self.lib
+        return self._stats(self._ext("mle").lasso_host_mle_stats, reset, "device_tables", "available")
 
     @staticmethod
     def _values_form(form):
@@ -362,7 +334,7 @@ class HostProver:
         """the lookup results v[k] = combine_lookups(T[dim(k)]) of the (n, c) uint64 `indices`, on the CPU (lasso_host_lookup_values_ref: the normative statement):
         s = next_pow2(n) elements — (s, 4) uint64 fully reduced memory words, or (s,) uint64 for form="u64" (LassoError where that form is not offered) — the rows
         behind n being the rows densify pads with (address 0)"""
-        lib = self._values_fns()
+        lib = self._ext("values")
         indices = np.ascontiguousarray(indices, dtype=np.uint64)
         f = self._values_form(form)
         n = indices.shape[0]
@@ -376,7 +348,7 @@ class HostProver:
         """the same vector for a densified representation, written by the device from the representation's own address columns (lasso_host_lookup_values).  out=None: a
         numpy array as lookup_values_ref returns it.  `out`: a torch tensor ALREADY ON THE GPU of this host's context — contiguous int64 (reinterpreted as unsigned), shape
         (s,) for form="u64" or (s, 4) for "field", s the representation's padded number of lookups — which receives the vector and is returned."""
-        lib = self._values_fns()
+        lib = self._ext("values")
         f = self._values_form(form)
         n = C.c_size_t()
         self._chk(lib.lasso_host_dense_len(dense, C.byref(n)))
@@ -396,7 +368,7 @@ class HostProver:
     def values_evaluate(self, values, r):
         """DensePolynomial::evaluate of `values` — (s, 4) uint64 memory words as a numpy array, or an (s, 4) contiguous int64 torch tensor on this host's GPU — at
         r = (log2 s, 4) uint64: (4,) uint64, fully reduced (lasso_host_values_evaluate: one lasso_tables_mle call, no eq table)"""
-        lib = self._values_fns()
+        lib = self._ext("values")
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         out = np.zeros(4, dtype=np.uint64)
         if hasattr(values, "data_ptr") and hasattr(values, "is_cuda"):
@@ -413,44 +385,20 @@ class HostProver:
     def claimed_evaluation(self, proof):
         """claimed_evaluation inside the proof bytes as (4,) uint64 memory words, fully reduced (lasso_host_proof_claimed_evaluation); LassoError on bytes that do not
         deserialize that far"""
-        lib = self._values_fns()
+        lib = self._ext("values")
         out = np.zeros(4, dtype=np.uint64)
         self._chk(lib.lasso_host_proof_claimed_evaluation(bytes(proof), len(proof), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def values_stats(self, reset=False):
         """{"device_lookups": elements lasso_lookup_values wrote for this host so far, "available": whether the device library has that entry} (lasso_host_values_stats)"""
-        lib = self._values_fns()
-        k, a = C.c_uint64(), C.c_int32()
-        self._chk(lib.lasso_host_values_stats(self.h, C.byref(k), C.byref(a), 1 if reset else 0))
-        return {"device_lookups": k.value, "available": bool(a.value)}
+        return self._stats(self._ext("values").lasso_host_values_stats, reset, "device_lookups", "available")
 
     # ---- include/lasso_prover_poly.h: a commitment to the caller's vector and its opening at a point
-    def _poly_fns(self):
-        """include/lasso_prover_poly.h, declared on first use (a prover library built before that header existed does not export it)"""
-        if not hasattr(self, "_poly_ok"):
-            vp, sz, i32 = C.c_void_p, C.c_size_t, C.c_int32
-            vt = C.POINTER(TranscriptVtbl)
-            try:
-                self.lib.lasso_host_poly_gens_new.argtypes = [vp, C.c_char_p, sz, C.POINTER(vp)]
-                self.lib.lasso_host_poly_gens_from_points.argtypes = [vp, sz, vp, sz, C.POINTER(vp)]
-                self.lib.lasso_host_poly_gens_free.argtypes = [vp]
-                self.lib.lasso_host_poly_commit.argtypes = [vp, vp, vp, i32, i32, sz, vp, sz, C.POINTER(sz)]
-                self.lib.lasso_host_poly_commitment_append.argtypes = [vt, vp, C.c_char_p, C.c_char_p, sz]
-                self.lib.lasso_host_poly_open.argtypes = [vp, vp, vp, i32, i32, sz, vp, sz, vt, vp, vt, vp, vp, vp, sz, C.POINTER(sz)]
-                self.lib.lasso_host_poly_verify.argtypes = [vp, vp, vp, sz, vp, vt, vp, C.c_char_p, sz, C.c_char_p, sz, C.POINTER(i32)]
-                self.lib.lasso_host_poly_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(i32), i32]
-                self.lib.lasso_alloc.argtypes = [vp, sz, C.POINTER(vp)]       # the device library's, reached through the prover library that is linked against it
-                self.lib.lasso_free.argtypes = [vp, vp]
-            except AttributeError:
-                raise LassoError("this prover library does not export lasso_host_poly_commit (include/lasso_prover_poly.h)")
-            self._poly_ok = True
-        return self.lib
-
     def poly_gens(self, num_vars, label=b"gens_poly", points=None):
         """PolyCommitmentGens::new(num_vars, label) (lasso_host_poly_gens_new), or with `points` — an (n + 2, 8) uint64 array [G[0..n), gens_1.G[0], h],
         n = 2^(num_vars - num_vars // 2) — the caller's own generators (lasso_host_poly_gens_from_points).  Release with free(poly_gens=...)."""
-        lib = self._poly_fns()
+        lib = self._ext("poly")
         g = C.c_void_p()
         if points is None:
             self._chk(lib.lasso_host_poly_gens_new(self.h, label, num_vars, C.byref(g)))
@@ -483,18 +431,18 @@ class HostProver:
     def poly_commit(self, pgens, values, form=None):
         """DensePolynomial::commit of `values` (see _poly_values for what they may be) over `pgens`: the bytes [u64 L][L x 32 B] (lasso_host_poly_commit).  The 64-bit
         form is read as it is on the device where the device library has include/lasso_hip_poly.h"""
-        lib = self._poly_fns()
+        lib = self._ext("poly")
         ptr, f, on_dev, s, keep = self._poly_values(values, form)
         return self._bytes_call(lib.lasso_host_poly_commit, self.h, pgens, ptr, f, on_dev, s)
 
     def poly_commitment_append(self, transcript, label, commitment):
         """PolyCommitment::append_to_transcript(label) against a live transcript (a (vtbl, user) pair as Transcript.pair() makes it)"""
-        self._chk(self._poly_fns().lasso_host_poly_commitment_append(transcript[0], transcript[1], label, bytes(commitment), len(commitment)))
+        self._chk(self._ext("poly").lasso_host_poly_commitment_append(transcript[0], transcript[1], label, bytes(commitment), len(commitment)))
 
     def poly_open(self, pgens, values, r, transcript, tape, form=None):
         """PolyEvalProof::prove of `values` at r = (num_vars, 4) uint64 against live transcript and tape pairs: (proof bytes, Zr as (4,) uint64 memory words, fully
         reduced) — Zr = the polynomial's evaluation at r, computed on the way (lasso_host_poly_open)"""
-        lib = self._poly_fns()
+        lib = self._ext("poly")
         ptr, f, on_dev, s, keep = self._poly_values(values, form)
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         zr = np.zeros(4, dtype=np.uint64)
@@ -505,7 +453,7 @@ class HostProver:
     def poly_verify(self, pgens, r, zr, proof, commitment, transcript):
         """PolyEvalProof::verify_plain over the wire bytes against a live transcript pair: True = Ok(()), False = Err; LassoError on bytes that do not deserialize
         (lasso_host_poly_verify)"""
-        lib = self._poly_fns()
+        lib = self._ext("poly")
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         zr = np.ascontiguousarray(zr, dtype=np.uint64).reshape(4)
         ok = C.c_int32(-1)
@@ -515,7 +463,7 @@ class HostProver:
 
     def values_vector(self, dense, strategy):
         """the lookup results of `dense` left ON THE DEVICE as a DeviceVector: 64-bit integers where lasso_lookup_values offers that form, field elements otherwise"""
-        lib = self._poly_fns(); self._values_fns()
+        lib = self._ext("poly"); self._ext("values")
         n = C.c_size_t()
         self._chk(lib.lasso_host_dense_len(dense, C.byref(n)))
         for form in ("u64", "field"):
@@ -541,10 +489,7 @@ class HostProver:
     def poly_stats(self, reset=False):
         """{"u64_commit_elements", "u64_open_elements": 64-bit elements this host committed to / opened through the device entries of include/lasso_hip_poly.h so far,
         "available": whether the device library has them} (lasso_host_poly_stats)"""
-        lib = self._poly_fns()
-        a, b, av = C.c_uint64(), C.c_uint64(), C.c_int32()
-        self._chk(lib.lasso_host_poly_stats(self.h, C.byref(a), C.byref(b), C.byref(av), 1 if reset else 0))
-        return {"u64_commit_elements": a.value, "u64_open_elements": b.value, "available": bool(av.value)}
+        return self._stats(self._ext("poly").lasso_host_poly_stats, reset, "u64_commit_elements", "u64_open_elements", "available")
 
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
@@ -566,7 +511,7 @@ class HostProver:
         if gens:
             self.lib.lasso_host_gens_free(gens)
         if poly_gens:
-            self._poly_fns().lasso_host_poly_gens_free(poly_gens)
+            self._ext("poly").lasso_host_poly_gens_free(poly_gens)
 
     def close(self):
         if self.h:
@@ -596,7 +541,9 @@ class DeviceVector:
     HostProver.values_vector returns and poly_commit / poly_open take without a download"""
 
     def __init__(self, host, form, s):
-        lib = host._poly_fns()
+        lib = host._ext("poly")
+        lib.lasso_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]       # the device library's, reached through the prover library that is linked against it
+        lib.lasso_free.argtypes = [C.c_void_p, C.c_void_p]
         p = C.c_void_p()
         if lib.lasso_alloc(C.c_void_p(host.ctx()), s * (8 if form == "u64" else 32), C.byref(p)) != 0:
             raise LassoError("DeviceVector: lasso_alloc failed")

@@ -1,11 +1,6 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited) with the two entry points that take a strategy on a caller-defined strategy's path —
-// lasso_sumcheck_combine_round and lasso_combine_claim — wrapped: for kind = LASSO_CUSTOM a literal loop over the descriptor's term list (sumcheck.rs:179-218 and
-// subtables/mod.rs:197-213 with comb_func = the caller's g), everything else forwarded to the mock.  Linked with lasso_amd/host/prover_capi.cpp by tests/customutil.py.
-#define lasso_sumcheck_combine_round mock_builtin_combine_round
-#define lasso_combine_claim mock_builtin_combine_claim
-#include "../../oracle/mock_hip.cpp"
-#undef lasso_sumcheck_combine_round
-#undef lasso_combine_claim
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_CUSTOM), which compiles the mock's lasso_sumcheck_combine_round and lasso_combine_claim — the two entry points that take a
+// strategy on a caller-defined strategy's path — as mock_builtin_*: here they are wrapped.  For kind = LASSO_CUSTOM a literal loop over the descriptor's term list
+// (sumcheck.rs:179-218 and subtables/mod.rs:197-213 with comb_func = the caller's g), everything else forwarded to the mock.
 #include "../../include/lasso_custom_check.h"
 
 static Fr custom_g(const lasso_strategy_custom* s, const Fr* v) {

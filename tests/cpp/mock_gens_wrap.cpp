@@ -1,7 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited) plus the one entry point of include/lasso_hip_gens.h, implemented with the PRODUCT's
-// pt_from_candidate (lasso_amd/csrc/fe29.cuh / bn254_fe29.cuh — the function k_points_from_candidates runs per lane) compiled for the host.  Linked with
-// lasso_amd/host/prover_capi.cpp by tests/gensutil.py: the weak reference there resolves, so lasso_host_gens_new takes the device route on the CPU.
-#include "../../oracle/mock_hip.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_GENS): the one entry point of include/lasso_hip_gens.h, implemented with the PRODUCT's pt_from_candidate
+// (lasso_amd/csrc/fe29.cuh / bn254_fe29.cuh — the function k_points_from_candidates runs per lane) compiled for the host.  lasso_host_gens_new takes the device route on the CPU.
 #include "../../lasso_amd/csrc/fe29.cuh"
 
 extern "C" int32_t lasso_points_from_candidates(lasso_ctx* c, const uint64_t* limbs, const uint8_t* greatest, size_t n, lasso_affine* out, uint8_t* status) {

@@ -1,8 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited; through tests/cpp/mock_custom_wrap.cpp, so that caller-defined strategies can be PROVED
-// on the CPU) plus the entry points of include/lasso_hip_mle.h as a literal statement over the oracle's field type: the whole eq table by the oracle's
-// EqPolynomial(point).evals(), then one serial dot product per table.  Linked with lasso_amd/host/prover_capi.cpp by tests/mleutil.py: the weak reference to
-// lasso_tables_mle there resolves, so the verifier takes its device route on the CPU.
-#include "mock_custom_wrap.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_MLE): the entry points of include/lasso_hip_mle.h as a literal statement over the oracle's field type: the whole eq table
+// by the oracle's EqPolynomial(point).evals(), then one serial dot product per table.  The verifier takes its device route on the CPU.
 #include "../../include/lasso_hip_mle.h"
 
 extern "C" int32_t lasso_tables_mle(lasso_ctx* c, const uint32_t* const* tables_u32, const lasso_fr* const* tables_fr, uint32_t num_tables, uint32_t log_m, const lasso_fr* point, lasso_fr* out) {

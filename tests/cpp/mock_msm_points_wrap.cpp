@@ -1,7 +1,6 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited) plus the entry points of include/lasso_hip_msm.h, implemented on the mock's own
-// literal MSM (oracle/lasso_oracle.hpp msm, the function its lasso_msm runs).  Linked with lasso_amd/host/prover_capi.cpp by tests/msmutil.py: the weak reference to
-// lasso_msm_points there resolves, so the verifier takes its table-free path on the CPU.  An all-zero affine entry is the identity and is skipped, as the header says.
-#include "../../oracle/mock_hip.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_MSM_POINTS): the entry points of include/lasso_hip_msm.h, implemented on the mock's own literal MSM
+// (oracle/lasso_oracle.hpp msm, the function its lasso_msm runs).  The verifier takes its table-free path on the CPU.  An all-zero affine entry is the identity and is
+// skipped, as the header says.
 #include "../../include/lasso_hip_msm.h"
 
 extern "C" int32_t lasso_msm_points(lasso_ctx* c, const lasso_affine* points, const lasso_fr* scalars, size_t n, lasso_point* out) {

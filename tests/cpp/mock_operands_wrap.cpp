@@ -1,8 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited; taken through tests/cpp/mock_custom_wrap.cpp, which adds nothing but the two wrapped
-// entry points a caller-defined strategy is proved through, so that one can be proved from operands too) plus the entry point of include/lasso_hip_operands.h, implemented as expand (the shared
-// lasso_amd/csrc/operand_layout.cuh) then the mock's own lasso_densify_dim_slab — the reference's serial loop.  Linked with lasso_amd/host/prover_capi.cpp by
-// tests/operandutil.py: the weak reference to lasso_densify_dim_operands there resolves, so lasso_host_densify_operands takes its device path on the CPU.
-#include "mock_custom_wrap.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_OPERANDS): the entry point of include/lasso_hip_operands.h, implemented as expand (the shared
+// lasso_amd/csrc/operand_layout.cuh) then the mock's own lasso_densify_dim_slab — the reference's serial loop.  lasso_host_densify_operands takes its device path on the CPU.
 #include "../../lasso_amd/csrc/operand_layout.cuh"
 
 static size_t g_operand_calls = 0;

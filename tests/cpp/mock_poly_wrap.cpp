@@ -1,8 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited; through tests/cpp/mock_values_wrap.cpp, so that caller-defined strategies can be proved,
-// lasso_tables_mle and lasso_lookup_values exist on the CPU) plus the three entry points of include/lasso_hip_poly.h as literal loops over the oracle's field type and MSM.
-// "Device" pointers are host pointers here.  Linked with lasso_amd/host/prover_capi.cpp by tests/polyutil.py: the weak references there resolve, so lasso_host_poly_commit
-// and lasso_host_poly_open take the 64-bit route on the CPU; the library built WITHOUT this file (tests/valuesutil.py) takes the host lift.
-#include "mock_values_wrap.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_POLY): the three entry points of include/lasso_hip_poly.h as literal loops over the oracle's field type and MSM, so that
+// lasso_host_poly_commit and lasso_host_poly_open take the 64-bit route on the CPU; a library built without this fragment takes the host lift.
 #include "../../include/lasso_hip_poly.h"
 
 extern "C" int32_t lasso_u64_or(lasso_ctx* c, const uint64_t* v, size_t n, uint64_t* out) {

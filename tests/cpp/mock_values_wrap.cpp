@@ -1,8 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited; through tests/cpp/mock_custom_wrap.cpp and mock_mle_wrap.cpp, so that caller-defined
-// strategies can be proved and lasso_tables_mle exists on the CPU) plus the entry point of include/lasso_hip_values.h as a literal statement over the oracle's field type:
-// per lookup the NUM_MEMORIES table entries, then combine_lookups as subtables/*.rs state it.  "Device" pointers are host pointers here.  Linked with
-// lasso_amd/host/prover_capi.cpp by tests/valuesutil.py: the weak reference to lasso_lookup_values there resolves.
-#include "mock_mle_wrap.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_VALUES; requires custom, for custom_g): the entry point of include/lasso_hip_values.h as a literal statement over the
+// oracle's field type: per lookup the NUM_MEMORIES table entries, then combine_lookups as subtables/*.rs state it.
 #include "../../include/lasso_hip_values.h"
 #include "../../lasso_amd/csrc/values_combine.cuh"   // the refusal's rule and text only; the arithmetic below is the mock's own
 

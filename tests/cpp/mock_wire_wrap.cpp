@@ -1,7 +1,5 @@
-// Test-only: the oracle's mock of the device ABI (oracle/mock_hip.cpp, not edited) plus the one entry point of include/lasso_hip_wire.h, implemented with the PRODUCT's
-// pt_decompress (lasso_amd/csrc/fe29.cuh / bn254_fe29.cuh — the function k_points_decompress runs per lane) compiled for the host.  Linked with
-// lasso_amd/host/prover_capi.cpp by tests/wireutil.py: the weak reference there resolves, so the verifier takes its batched path on the CPU.
-#include "../../oracle/mock_hip.cpp"
+// Fragment of tests/cpp/mock_device.cpp (-DMOCK_EXT_WIRE): the one entry point of include/lasso_hip_wire.h, implemented with the PRODUCT's pt_decompress
+// (lasso_amd/csrc/fe29.cuh / bn254_fe29.cuh — the function k_points_decompress runs per lane) compiled for the host.  The verifier takes its batched path on the CPU.
 #include "../../lasso_amd/csrc/fe29.cuh"
 
 extern "C" int32_t lasso_points_decompress(lasso_ctx* c, const uint8_t* wire32, size_t n, lasso_affine* out, uint8_t* canon32, uint8_t* status) {

@@ -1,35 +1,19 @@
 """Helpers of the caller-defined-strategy tests: the built-in strategies re-expressed as descriptors (lasso_amd.CustomStrategy), two strategies the reference does
 not ship, a big-integer evaluation of a term list, and the CPU build of the host prover against the wrapped mock (tests/cpp/mock_custom_wrap.cpp)."""
 import os
-import subprocess
 
 import numpy as np
 
 from lasso_amd import CustomStrategy, _abi, fr_words
 from lasso_amd.custom import FR_MODULUS
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_mock_prover_custom(curve="curve25519"):
-    """tests/proverutil.py build_mock_prover with the wrapped mock in place of oracle/mock_hip.cpp: custom strategies can be PROVED on the CPU"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_custom_bn254.so" if bn else "liblasso_prover_mock_custom.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_prover.h", "lasso_custom_check.h")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_custom_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """the host prover over the mock with the two strategy-taking entry points wrapped (tests/cpp/mock_custom_wrap.cpp): custom strategies can be PROVED on the CPU"""
+    return build_mock_prover(curve, ext=("custom",))
 
 
 # ---- the built-in strategies as descriptors (materialize_subtables of and.rs / or.rs / xor.rs / lt.rs / range_check.rs, restated)

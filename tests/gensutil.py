@@ -11,6 +11,7 @@ import sys
 import numpy as np
 
 import wireutil as W
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, NONCANONICAL, NO_POINT = range(3)
@@ -190,25 +191,9 @@ def oracle_gens(oracle, count, label=LABEL):
 # ---------------------------------------------------------------- builds and child processes
 
 def build_mock_prover_gens(curve="curve25519"):
-    """tests/proverutil.py build_mock_prover with tests/cpp/mock_gens_wrap.cpp in place of oracle/mock_hip.cpp: lasso_points_from_candidates exists (the product's
-    pt_from_candidate on the host), so lasso_host_gens_new takes the device route on the CPU"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_gens_bn254.so" if bn else "liblasso_prover_mock_gens.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "fe29.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "bn254_fe29.cuh", "mont29.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_gens.h", "lasso_prover.h", "lasso_custom_check.h")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_gens_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """the host prover over the mock with lasso_points_from_candidates (tests/cpp/mock_gens_wrap.cpp: the product's pt_from_candidate on the host), so
+    lasso_host_gens_new takes the device route on the CPU"""
+    return build_mock_prover(curve, ext=("gens",))
 
 
 # Generator sets (and optionally one proof) in a FRESH process: the LASSO_GENS_* switches are read once per process.  argv: repository root, library ("" = the product

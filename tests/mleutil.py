@@ -6,31 +6,15 @@ import subprocess
 import sys
 
 import numpy as np
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_mock_prover_mle(curve="curve25519"):
-    """tests/customutil.py build_mock_prover_custom with tests/cpp/mock_mle_wrap.cpp on top: caller-defined strategies can be proved on the CPU, and lasso_tables_mle
-    exists (the mock's literal eq table and dot products), so the verifier takes its device route"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_mle_bn254.so" if bn else "liblasso_prover_mock_mle.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_mle.h", "lasso_prover.h", "lasso_prover_mle.h", "lasso_custom_check.h")]
-    srcs.append(os.path.join(ROOT, "tests", "cpp", "mock_custom_wrap.cpp"))
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_mle_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """the host prover over the mock with lasso_tables_mle (tests/cpp/mock_mle_wrap.cpp: the mock's literal eq table and dot products), so the verifier takes its
+    device route, and with caller-defined strategies provable on the CPU"""
+    return build_mock_prover(curve, ext=("custom", "mle"))
 
 
 # ---- big-integer references (memory words are value * 2^256 mod p)

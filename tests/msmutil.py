@@ -4,29 +4,14 @@ import json
 import os
 import subprocess
 import sys
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_mock_prover_msm(curve="curve25519"):
-    """tests/proverutil.py build_mock_prover with tests/cpp/mock_msm_points_wrap.cpp in place of oracle/mock_hip.cpp: lasso_msm_points exists (the mock's literal MSM)"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_msm_bn254.so" if bn else "liblasso_prover_mock_msm.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_hip_msm.h", "lasso_prover.h")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_msm_points_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """the host prover over the mock with lasso_msm_points (tests/cpp/mock_msm_points_wrap.cpp: the mock's literal MSM)"""
+    return build_mock_prover(curve, ext=("msm_points",))
 
 
 # A verify in a FRESH process: LASSO_VERIFY_MSM_POINTS is read once per process.  argv: library ("" = the product library of `curve`), curve, kind, c, log_m, log_r, lookups.

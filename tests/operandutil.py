@@ -7,6 +7,7 @@ import subprocess
 import sys
 
 import numpy as np
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -54,39 +55,14 @@ def operands_for(layout, c, n, rng, mode="rand"):
 
 # ---- builds
 
-def _build(so_name, sources, deps, curve, extra=()):
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, so_name + ("_bn254.so" if bn else ".so"))
-    srcs = sources + deps
-    srcs += [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("operand_layout.cuh", "mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_operands.h", "lasso_prover.h", "lasso_custom_check.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *extra, *flags, "-o", tmp, *sources])
-        os.replace(tmp, so)
-    return so
-
-
-WRAP = os.path.join(ROOT, "tests", "cpp", "mock_operands_wrap.cpp")
-CAPI = os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp")
-
-
 def build_mock_prover_operands(curve="curve25519"):
     """the host prover over the mock WITH lasso_densify_dim_operands (and the custom-strategy wrappers): lasso_host_densify_operands takes its device path"""
-    return _build("liblasso_prover_mock_operands", [CAPI, WRAP], [os.path.join(ROOT, "tests", "cpp", "mock_custom_wrap.cpp")], curve)
+    return build_mock_prover(curve, ext=("operands",))
 
 
 def build_slab_lib_operands(curve="curve25519", with_entry=True):
-    """tests/cpp/slab_threads_operands.cpp over the wrapped mock (with_entry) or the plain one (the fallback)"""
-    harness = [os.path.join(ROOT, "tests", "cpp", "slab_threads_operands.cpp")]
-    mock = WRAP if with_entry else os.path.join(ROOT, "oracle", "mock_hip.cpp")
-    deps = [os.path.join(ROOT, "tests", "cpp", "slab_threads.cpp"), os.path.join(ROOT, "tests", "cpp", "mock_custom_wrap.cpp")]
-    return _build("libslab_threads_operands" if with_entry else "libslab_threads_operands_plain", harness + [CAPI, mock], deps, curve, extra=["-pthread"])
+    """tests/cpp/slab_threads_operands.cpp over the mock with the entry (with_entry) or the plain one (the fallback)"""
+    return build_mock_prover(curve, ext=("operands",) if with_entry else (), harness=["slab_threads_operands.cpp"], extra_flags=["-pthread"])
 
 
 # ---- LASSO_DENSIFY_OPERANDS in a fresh process.  argv: repository root, library ("" = the product library of `curve`), curve, JSON list of cases

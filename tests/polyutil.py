@@ -1,12 +1,12 @@
 """Helpers of the vector-commitment tests (tests/test_poly_commit_cpu.py, tests/test_gpu_poly_commit.py): the CPU build of the host prover against the mock with the three
 entries of include/lasso_hip_poly.h added (tests/cpp/mock_poly_wrap.cpp), Python big-integer references, and the shapes and children the GPU tests run."""
 import os
-import subprocess
 
 import numpy as np
 
 import valuesutil as V
 from lasso_amd.custom import FR_MODULUS
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CURVES = ["curve25519", "bn254"]
@@ -15,26 +15,9 @@ M64 = (1 << 64) - 1
 
 
 def build_mock_prover_poly(curve="curve25519"):
-    """tests/valuesutil.py build_mock_prover_values with tests/cpp/mock_poly_wrap.cpp on top: lasso_u64_or, lasso_hyrax_commit_compressed_u64 and
-    lasso_matvec_left_u64_dev exist as literal loops, so lasso_host_poly_commit / lasso_host_poly_open take the 64-bit route on the CPU"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_poly_bn254.so" if bn else "liblasso_prover_mock_poly.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "values_combine.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in os.listdir(os.path.join(ROOT, "include"))]
-    srcs += [os.path.join(ROOT, "tests", "cpp", f) for f in ("mock_custom_wrap.cpp", "mock_mle_wrap.cpp", "mock_values_wrap.cpp")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_poly_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """build_mock_prover_values' library with lasso_u64_or, lasso_hyrax_commit_compressed_u64 and lasso_matvec_left_u64_dev on top (tests/cpp/mock_poly_wrap.cpp:
+    literal loops), so lasso_host_poly_commit / lasso_host_poly_open take the 64-bit route on the CPU"""
+    return build_mock_prover(curve, ext=("custom", "mle", "values", "poly"))
 
 
 # ---- Python integers

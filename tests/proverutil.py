@@ -2,7 +2,6 @@
 or the test-only build of the same host sources against the oracle's mock of the device ABI."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
@@ -11,25 +10,7 @@ from lasso_amd import _abi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build_mock_prover(curve="curve25519"):
-    """The host prover sources linked against the oracle's mock of the device ABI; curve = "bn254" builds both with -DLASSO_BN254 / -DORC_BN254."""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_bn254.so" if bn else "liblasso_prover_mock.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "device_switches.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_prover.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"    # several test processes (pytest -n) may find the library stale at once: each links its own file, the rename is atomic
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,   # see oracle/Makefile
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), os.path.join(ROOT, "oracle", "mock_hip.cpp")])
-        os.replace(tmp, so)
-    return so
-
-
+from mockbuild import build_mock_prover  # noqa: E402,F401  (curve, ext=()): the host prover sources linked against the oracle's mock of the device ABI
 from lasso_amd.prover import HostProver, declare_prover  # noqa: E402,F401
 
 

@@ -246,19 +246,7 @@ def test_custom_as_builtin_proves_the_builtin_bytes(hosts, curve, kind, c, log_m
 
 def _slab_lib():
     """tests/cpp/slab_threads.cpp (the ranks of one proof as threads) over the wrapped mock"""
-    import os
-    import subprocess
-    out_dir = os.path.join(U.ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libslab_threads_custom.so")
-    srcs = [os.path.join(U.ROOT, "tests", "cpp", "slab_threads.cpp"), os.path.join(U.ROOT, "lasso_amd", "host", "prover_capi.cpp"), os.path.join(U.ROOT, "tests", "cpp", "mock_custom_wrap.cpp")]
-    deps = srcs + [os.path.join(U.ROOT, "lasso_amd", "host", f) for f in ("prover.hpp", "verifier.hpp", "field_host.hpp", "hashes.hpp")] + [os.path.join(U.ROOT, "oracle", f) for f in ("lasso_oracle.hpp", "mock_hip.cpp")]
-    deps += [os.path.join(U.ROOT, "include", f) for f in ("lasso_hip.h", "lasso_prover.h", "lasso_custom_check.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(x) > os.path.getmtime(so) for x in deps):
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", "-o", tmp] + srcs)
-        os.replace(tmp, so)
-    return C.CDLL(so)
+    return C.CDLL(build_mock_prover(ext=("custom",), harness=["slab_threads.cpp"], extra_flags=["-pthread"]))
 
 
 def _slab_prove(lib, world, sptr, num_memories, idx, r, capacity=False):

@@ -16,19 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def build_slab_lib(curve="curve25519"):
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "libslab_threads_bn254.so" if bn else "libslab_threads.so")
-    srcs = [os.path.join(ROOT, "tests", "cpp", "slab_threads.cpp"), os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), os.path.join(ROOT, "oracle", "mock_hip.cpp")]
-    deps = srcs + [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover.hpp", "field_host.hpp", "hashes.hpp")] + [os.path.join(ROOT, "oracle", "lasso_oracle.hpp")]
-    deps += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "device_switches.cuh")] + [os.path.join(ROOT, "oracle", "bn254.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in deps):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"      # atomic replace: other test processes (pytest -n, the capacity-mode children) may be building or loading the same library
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp] + srcs)   # see oracle/Makefile
-        os.replace(tmp, so)
-    return C.CDLL(so)
+    return C.CDLL(build_mock_prover(curve, harness=["slab_threads.cpp"], extra_flags=["-pthread"]))
 
 
 @pytest.fixture(scope="module")

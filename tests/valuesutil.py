@@ -2,7 +2,6 @@
 lasso_lookup_values added (tests/cpp/mock_values_wrap.cpp), every strategy kind as (strategy, its descriptor restatement), Python big-integer values, the shapes the GPU
 tests run (here so that the CPU test can hold them against the launch plan without importing a GPU module)."""
 import os
-import subprocess
 
 import numpy as np
 
@@ -10,6 +9,7 @@ import customutil as U
 import mleutil as M
 from lasso_amd import _abi
 from lasso_amd.custom import FR_MODULUS
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CURVES = ["curve25519", "bn254"]
@@ -18,26 +18,9 @@ U64_TEXT = "the 64-bit form is offered over integer tables for LT"      # the st
 
 
 def build_mock_prover_values(curve="curve25519"):
-    """tests/mleutil.py build_mock_prover_mle with tests/cpp/mock_values_wrap.cpp on top: lasso_lookup_values exists as a literal loop, so lasso_host_lookup_values takes
-    its device route on the CPU"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_values_bn254.so" if bn else "liblasso_prover_mock_values.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "switches.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "values_combine.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_mle.h", "lasso_hip_values.h", "lasso_prover.h", "lasso_prover_mle.h", "lasso_prover_values.h", "lasso_custom_check.h")]
-    srcs += [os.path.join(ROOT, "tests", "cpp", f) for f in ("mock_custom_wrap.cpp", "mock_mle_wrap.cpp")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_values_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """build_mock_prover_mle's library with lasso_lookup_values on top (tests/cpp/mock_values_wrap.cpp: a literal loop), so lasso_host_lookup_values takes its
+    device route on the CPU; include/lasso_hip_poly.h stays absent"""
+    return build_mock_prover(curve, ext=("custom", "mle", "values"))
 
 
 # ---- every strategy kind: (name, what the C ABI takes, the same strategy as a descriptor whose tables and term list Python can read)

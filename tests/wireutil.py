@@ -2,9 +2,9 @@
 from ark-ec's rules (NOT from the product's C++), crafted encodings for both curves, a walker of the proof's wire format that finds every point and scalar, and the CPU
 build of the host prover against the mock with the device decoder added (tests/cpp/mock_wire_wrap.cpp)."""
 import os
-import subprocess
 
 import numpy as np
+from mockbuild import build_mock_prover
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -287,21 +287,5 @@ def commitment_points(comm):
 
 
 def build_mock_prover_wire(curve="curve25519"):
-    """tests/proverutil.py build_mock_prover with tests/cpp/mock_wire_wrap.cpp in place of oracle/mock_hip.cpp: the device decoder exists (the product's pt_decompress on the host)"""
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    bn = curve == "bn254"
-    so = os.path.join(out_dir, "liblasso_prover_mock_wire_bn254.so" if bn else "liblasso_prover_mock_wire.so")
-    srcs = [os.path.join(ROOT, "lasso_amd", "host", f) for f in ("prover_capi.cpp", "prover.hpp", "verifier.hpp", "field_host.hpp", "hashes.hpp", "modinv.hpp")]
-    srcs += [os.path.join(ROOT, "lasso_amd", "csrc", f) for f in ("mont32.cuh", "fr.cuh", "fq.cuh", "fe29.cuh", "bn254_fr.cuh", "bn254_fq.cuh", "bn254_fe29.cuh", "mont29.cuh")]
-    srcs += [os.path.join(ROOT, "oracle", f) for f in ("mock_hip.cpp", "lasso_oracle.hpp", "ff.hpp", "ed25519.hpp", "bn254.hpp", "hashes.hpp")]
-    srcs += [os.path.join(ROOT, "include", f) for f in ("lasso_hip.h", "lasso_hip_wire.h", "lasso_prover.h", "lasso_custom_check.h")]
-    wrap = os.path.join(ROOT, "tests", "cpp", "mock_wire_wrap.cpp")
-    srcs.append(wrap)
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        flags = ["-DLASSO_BN254", "-DORC_BN254"] if bn else []
-        tmp = f"{so}.{os.getpid()}.tmp"
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-fno-gnu-unique", "-Wl,-Bsymbolic", *flags, "-o", tmp,
-                               os.path.join(ROOT, "lasso_amd", "host", "prover_capi.cpp"), wrap])
-        os.replace(tmp, so)
-    return so
+    """the host prover over the mock with the device decoder (tests/cpp/mock_wire_wrap.cpp: the product's pt_decompress on the host)"""
+    return build_mock_prover(curve, ext=("wire",))
