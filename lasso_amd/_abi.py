@@ -27,6 +27,11 @@ class OperandLayout(C.Structure):
         return f"OperandLayout({self.operands}, {self.chunk_bits}, {self.msb_first})"
 
 
+class PolyVec(C.Structure):
+    """include/lasso_prover_polys.h lasso_host_poly_vec: one vector of a call that takes several"""
+    _fields_ = [("values", vp), ("form", i32), ("on_device", i32)]
+
+
 KINDS = {"and": 0, "or": 1, "xor": 2, "lt": 3, "range": 4, "spark": 5, "custom": 6}   # "spark" = LASSO_SPARK_UNCONFIRMED (include/lasso_hip.h): not in the reference snapshot
 CUSTOM_MAX_TERMS, CUSTOM_MAX_FACTORS, CUSTOM_MAX_DEGREE = 256, 2048, 17
 K_BIND, K_CUBIC, K_COMBINE, K_EQ, K_GP, K_FINGERPRINT, K_DOT, K_MATVEC, K_MSM, K_MISC, K_MSM_DIRECT, K_COUNT = range(12)
@@ -195,6 +200,10 @@ PROVER_EXTENSIONS = {
                                      "lasso_host_poly_open": [vp, vp, vp, i32, i32, sz, vp, sz, _vt, vp, _vt, vp, vp, vp, sz, _P(sz)],
                                      "lasso_host_poly_verify": [vp, vp, vp, sz, vp, _vt, vp, C.c_char_p, sz, C.c_char_p, sz, _P(i32)],
                                      "lasso_host_poly_stats": [vp, _P(u64), _P(u64), _P(i32), i32]}),
+    "polys": ("lasso_prover_polys.h", {"lasso_host_polys_commit": [vp, vp, _P(PolyVec), sz, sz, vp, sz, _P(sz)],
+                                       "lasso_host_polys_open": [vp, vp, _P(PolyVec), sz, sz, vp, sz, _vt, vp, _vt, vp, vp, vp, sz, _P(sz)],
+                                       "lasso_host_polys_verify": [vp, vp, vp, sz, vp, sz, _vt, vp, C.c_char_p, sz, C.c_char_p, sz, _P(i32)],
+                                       "lasso_host_polys_evaluate": [vp, _P(PolyVec), sz, sz, vp, sz, vp], "lasso_host_polys_stats": [vp, _P(u64), _P(u64), i32]}),
 }
 
 

@@ -1689,6 +1689,57 @@ class Prover {
     if (Zr_out) *Zr_out = y;
     return dot_product_log_prove(d, t, tape, g, d_LZ, d_R, a_bytes, y);
   }
+  // ---- CombinedTableEvalProof::prove (subtables/mod.rs:285-313) of DensePolynomial::merge (dense_mlpoly.rs:251-261) of a caller's k vectors of 2^nv values each, the
+  // merge never made: vector b is block b of the merged matrix (2^(left - kappa) whole rows, kappa = log2 next_pow2(k)), so prep_open's factorisation below applies with
+  // the blocks read where they lie, each in its own form (a 64-bit block through matvec_u64).  polys_pass is everything that depends on r alone: the M_b, the right-half
+  // table and evals[b] = <M_b, R> (k * 2^right products on the host); polys_eval_prove draws the challenges afterwards and ends where every opening does.
+  struct PolyBlock { const void* d; bool u64; };
+  struct PolysPass { DBuf M, R; ScVec evals; size_t kappa = 0, right = 0; };
+  static PolysPass polys_pass(const Dev& d, const std::vector<PolyBlock>& blocks, MatvecU64 matvec_u64, size_t nv, const ScVec& r) {
+    PolysPass ps; const size_t k = blocks.size();
+    ps.kappa = ceil_log2(k);
+    const size_t left = (nv + ps.kappa) / 2; ps.right = nv + ps.kappa - left;
+    LASSO_REQUIRE(k >= 1 && r.size() == nv && left >= ps.kappa);   // left >= kappa: no row of the merged matrix spans two vectors
+    const size_t lrows = (size_t)1 << (left - ps.kappa), Rn = (size_t)1 << ps.right;
+    ps.M = DBuf(d, k * Rn); ps.R = DBuf(d, Rn);
+    DBuf Lp(d, lrows);
+    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i + ps.kappa < left; i++) rl.push_back(r[i].abi()); for (size_t i = left - ps.kappa; i < nv; i++) rr.push_back(r[i].abi());
+    d.chk(lasso_eq_evals(d.ctx, rl.data(), (uint32_t)rl.size(), Lp.p), "lasso_eq_evals");
+    d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), ps.R.p), "lasso_eq_evals");
+    for (size_t b = 0; b < k; b++) {
+      LASSO_REQUIRE(blocks[b].d && (!blocks[b].u64 || matvec_u64));
+      if (blocks[b].u64) d.chk(matvec_u64(d.ctx, (const uint64_t*)blocks[b].d, Lp.p, lrows, Rn, ps.M.p + b * Rn), "lasso_matvec_left_u64_dev");
+      else d.chk(lasso_matvec_left_dev(d.ctx, (const lasso_fr*)blocks[b].d, Lp.p, lrows, Rn, ps.M.p + b * Rn), "lasso_matvec_left_dev");
+    }
+    std::vector<lasso_fr> m(k * Rn); d.chk(lasso_download(d.ctx, m.data(), ps.M.p, k * Rn * sizeof(lasso_fr)), "lasso_download");
+    const ScVec R = eq_evals_host(r.data() + (left - ps.kappa), ps.right);
+    for (size_t b = 0; b < k; b++) { Sc y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(m[b * Rn + i]) * R[i]; ps.evals.push_back(y); }
+    return ps;
+  }
+  static DotProductProofLog polys_eval_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, PolysPass& ps, const PolyCommitmentGens& g) {
+    const size_t k = ps.evals.size(), K = (size_t)1 << ps.kappa, Rn = (size_t)1 << ps.right;
+    t.append_protocol_name("Lasso CombinedTableEvalProof");
+    ScVec evals = ps.evals; evals.resize(K, Sc::zero());
+    t.append_scalars("evals_ops_val", evals);
+    const ScVec ch = t.challenge_vector("challenge_combine_n_to_one", ps.kappa);
+    size_t len = K;
+    for (size_t i = ch.size(); i-- > 0;) { len /= 2; for (size_t j = 0; j < len; j++) evals[j] = evals[2 * j] + ch[i] * (evals[2 * j + 1] - evals[2 * j]); }   // bound_poly_var_bot
+    const Sc joint = evals[0];
+    t.append_scalar("joint_claim_eval", joint);
+    Trace tr("DensePolyEval.prove", d.ctx);
+    t.append_protocol_name("polynomial evaluation proof");   // PolyEvalProof::prove at ch || r: L * Z = sum_b eq(ch)[b] * M_b, the zero blocks behind k contribute nothing
+    DBuf d_LZ;
+    if (ps.kappa == 0) d_LZ = std::move(ps.M);
+    else {
+      DBuf w(d, K); d_LZ = DBuf(d, Rn);
+      std::vector<lasso_fr> cc; for (auto& c : ch) cc.push_back(c.abi());
+      d.chk(lasso_eq_evals(d.ctx, cc.data(), (uint32_t)cc.size(), w.p), "lasso_eq_evals");
+      d.chk(lasso_matvec_left_dev(d.ctx, ps.M.p, w.p, k, Rn, d_LZ.p), "lasso_matvec_left_dev");
+    }
+    std::vector<uint8_t> a_bytes(32 * Rn);
+    d.chk(lasso_fr_to_bytes(d.ctx, ps.R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
+    return dot_product_log_prove(d, t, tape, g, d_LZ, ps.R, a_bytes, joint);
+  }
   DotProductProofLog poly_eval_prove(const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const Sc& Zr, const PolyCommitmentGens& g) {
     if (this->P == 1 && d_poly) return poly_eval_prove_resident(d, t, tape, d_poly, nullptr, num_vars, r, &Zr, nullptr, g);
     Trace tr("DensePolyEval.prove", d.ctx);

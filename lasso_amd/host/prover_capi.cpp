@@ -15,6 +15,7 @@
 #include "../csrc/values_combine.cuh"
 #include "../../include/lasso_hip_poly.h"
 #include "../../include/lasso_prover_poly.h"
+#include "../../include/lasso_prover_polys.h"
 
 using namespace lasso;
 
@@ -63,6 +64,7 @@ struct lasso_host {
   Dev dev; std::atomic<int> refs{1};
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
   uint64_t ext_count[EXT_COUNT][2] = {};   // the counters of EXTS' rows, for this host
+  uint64_t polys_count[2] = {};            // lasso_host_polys_stats: vectors committed to / opened (no device entry of their own, so no row of EXTS)
   TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = ext_count[EXT_MLE]; } return m; }
   GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = ext_count[EXT_GENS]; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = ext_count[EXT_MSM_POINTS]; } return m; }
@@ -563,16 +565,21 @@ struct PolyOperand {
   PolyOperand(const PolyOperand&) = delete; PolyOperand& operator=(const PolyOperand&) = delete;
   ~PolyOperand() { try { if (own && dev) dev->free(own); } catch (...) {} }
 };
-static void poly_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s) {
-  const std::string w(who);
-  if (!h || !g || !g->g || !values) throw Error(w + ": null argument");
-  if (g->owner != h) throw Error(w + ": the generators belong to another host");
+// what is refused of one vector, whoever takes it: `w` names the call and, where the call takes several (include/lasso_prover_polys.h), the vector
+static void poly_vec_check(const std::string& w, const void* values, int32_t form, int32_t on_device) {
+  if (!values) throw Error(w + ": null argument");
   if (form != LASSO_VALUES_FR && form != LASSO_VALUES_U64) throw Error(w + ": form is neither LASSO_VALUES_FR (0) nor LASSO_VALUES_U64 (1)");
   if (on_device != 0 && on_device != 1) throw Error(w + ": `on_device` is neither 0 (host) nor 1 (device)");
+  if ((uintptr_t)values & (on_device ? 15 : 7)) throw Error(w + ": the values pointer is misaligned for its form (host memory: 8 bytes, device memory: 16 bytes)");
+}
+static void poly_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s) {
+  const std::string w(who);
+  if (!h || !g || !g->g) throw Error(w + ": null argument");
+  if (g->owner != h) throw Error(w + ": the generators belong to another host");
+  poly_vec_check(w, values, form, on_device);
   if (h->dev.comm.sharded()) throw Error(w + ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
   if (s == 0 || (s & (s - 1))) throw Error(w + ": the number of values must be a power of two");
   if (s != ((size_t)1 << g->num_vars)) throw Error(w + ": the generators were made for 2^" + std::to_string(g->num_vars) + " values, got " + std::to_string(s));
-  if ((uintptr_t)values & (on_device ? 15 : 7)) throw Error(w + ": the values pointer is misaligned for its form (host memory: 8 bytes, device memory: 16 bytes)");
 }
 static void poly_operand(lasso_host* h, const void* values, int32_t form, int32_t on_device, size_t s, PolyOperand& o) {
   const Dev& d = h->dev; o.dev = &d;
@@ -676,6 +683,115 @@ int32_t lasso_host_poly_verify(lasso_host* h, lasso_host_poly_gens* g, const las
     return 0;)
 }
 int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint64_t* u64_open_elements, int32_t* available, int32_t reset) { return ext_stats("lasso_host_poly_stats", h, EXT_POLY, u64_commit_elements, u64_open_elements, available, reset); }
+// ---- include/lasso_prover_polys.h: k vectors under one commitment, opened at r in one proof
+}  // extern "C"
+// The merge of k vectors of s = 2^nv values as a matrix: 2^left rows of 2^right values, vector b in the rows [b * rows_per, (b + 1) * rows_per)
+struct PolysShape { size_t nv = 0, kappa = 0, left = 0, right = 0, rows_per = 0; };
+static const char* const POLYS_SLAB = ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vectors are not offered there";
+// every refusal of the calls that take vectors, before anything is uploaded or launched.  g == null: a call without generators; r_len == SIZE_MAX: a call without a point
+static PolysShape polys_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, size_t r_len) {
+  const std::string w(who);
+  if (!h || (!vecs && k)) throw Error(w + ": null argument");
+  if (g && g->owner != h) throw Error(w + ": the generators belong to another host");
+  if (h->dev.comm.sharded()) throw Error(w + POLYS_SLAB);
+  if (k == 0) throw Error(w + ": no vectors (k = 0)");
+  if (s == 0 || (s & (s - 1))) throw Error(w + ": the number of values per vector must be a power of two");
+  PolysShape sh; while (((size_t)1 << sh.nv) < s) sh.nv++;
+  sh.kappa = ceil_log2(k);
+  const std::string merge = std::to_string(k) + " vectors of 2^" + std::to_string(sh.nv) + " values merge into a polynomial of " + std::to_string(sh.nv + sh.kappa) + " variables";
+  if (sh.nv + sh.kappa > 30) throw Error(w + ": " + merge + "; at most 30 are offered");
+  if (g && g->num_vars != sh.nv + sh.kappa) throw Error(w + ": the generators were made for " + std::to_string(g->num_vars) + " variables, but " + merge);
+  if (r_len != SIZE_MAX && r_len != sh.nv) throw Error(w + ": the point must have log2(s) = " + std::to_string(sh.nv) + " coordinates (the " + std::to_string(sh.kappa) + " above them are challenges), got " + std::to_string(r_len));
+  sh.left = (sh.nv + sh.kappa) / 2; sh.right = sh.nv + sh.kappa - sh.left;
+  if (sh.right > sh.nv) throw Error(w + ": a row of the merged matrix (2^" + std::to_string(sh.right) + " values) would span several vectors of " + std::to_string(s) + " values; " + merge);
+  sh.rows_per = (size_t)1 << (sh.left - sh.kappa);
+  for (size_t b = 0; b < k; b++) poly_vec_check(w + ": vector " + std::to_string(b), vecs[b].values, vecs[b].form, vecs[b].on_device);
+  return sh;
+}
+// the M_b pass over the k vectors where the device reads them; host vectors are uploaded for its duration
+static Prover::PolysPass polys_pass(lasso_host* h, const lasso_host_poly_vec* vecs, size_t k, size_t s, const PolysShape& sh, const ScVec& rv, size_t* u64_vectors) {
+  std::vector<PolyOperand> ops(k); std::vector<Prover::PolyBlock> blocks(k);
+  size_t wide = 0;
+  for (size_t b = 0; b < k; b++) { poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, ops[b]); blocks[b] = {ops[b].d, ops[b].u64}; wide += ops[b].u64 ? 1 : 0; }
+  if (u64_vectors) *u64_vectors = wide;
+  try { return Prover::polys_pass(h->dev, blocks, lasso_matvec_left_u64_dev, sh.nv, rv); } catch (...) { h->dev.abort_all(); throw; }
+}
+extern "C" {
+int32_t lasso_host_polys_commit(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, uint8_t* out, size_t cap, size_t* len) {
+  GUARD(
+    if (!g || !g->g) throw Error("lasso_host_polys_commit: null argument");
+    const PolysShape sh = polys_check("lasso_host_polys_commit", h, g, vecs, k, s, SIZE_MAX);
+    const Dev& d = h->dev; const size_t L = (size_t)1 << sh.left, R = (size_t)1 << sh.right;
+    std::vector<uint8_t> rows(32 * L);
+    for (size_t b = 0; b < k; b++) {   // one vector at a time: an uploaded one is released before the next
+      PolyOperand o; poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, o);
+      uint8_t* at = rows.data() + 32 * b * sh.rows_per;
+      if (o.u64) {
+        uint64_t bits = 0;
+        d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
+        d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, sh.rows_per, R, g->g->bases, at), "lasso_hyrax_commit_compressed_u64");
+        h->ext_count[EXT_POLY][0] += s;
+      } else { const PolyCommitment c = hyrax_commit_rows(d, (const lasso_fr*)o.d, sh.rows_per, R, *g->g); memcpy(at, c.compressed.data(), 32 * sh.rows_per); }
+    }
+    uint8_t id[32]; compress_one(Pt::identity(), id);   // the zero blocks behind k commit to the identity, row by row
+    for (size_t i = k * sh.rows_per; i < L; i++) memcpy(rows.data() + 32 * i, id, 32);
+    h->polys_count[0] += k;
+    ProofWriter w; w.pts_vec(rows);
+    return emit(w.b, out, cap, len);)
+}
+int32_t lasso_host_polys_open(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len,
+                              const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, lasso_fr* evals, uint8_t* proof, size_t cap, size_t* len) {
+  GUARD(
+    if (!g || !g->g || !r || !tv || !pv || !evals) throw Error("lasso_host_polys_open: null argument");
+    const PolysShape sh = polys_check("lasso_host_polys_open", h, g, vecs, k, s, r_len);
+    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    size_t wide = 0;
+    Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, &wide);
+    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
+    DotProductProofLog P;
+    try { P = Prover::polys_eval_prove(h->dev, t, tape, ps, *g->g); } catch (...) { h->dev.abort_all(); throw; }
+    h->ext_count[EXT_POLY][1] += wide * s; h->polys_count[1] += k;
+    ProofWriter w; P.write(w);
+    return emit(w.b, proof, cap, len);)
+}
+int32_t lasso_host_polys_verify(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const lasso_fr* evals, size_t k, const lasso_transcript_vtbl* tv, void* tu,
+                                const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
+  GUARD(
+    if (!h || !g || !g->g || (!r && r_len) || !evals || !tv || !proof || !commitment || !ok) throw Error("lasso_host_polys_verify: null argument");
+    if (g->owner != h) throw Error("lasso_host_polys_verify: the generators belong to another host");
+    if (h->dev.comm.sharded()) throw Error(std::string("lasso_host_polys_verify") + POLYS_SLAB);
+    if (k == 0) throw Error("lasso_host_polys_verify: no vectors (k = 0)");
+    if (r_len + ceil_log2(k) != g->num_vars) throw Error("lasso_host_polys_verify: the generators were made for " + std::to_string(g->num_vars) + " variables, but " + std::to_string(k) + " evaluations at a point of " +
+                                                         std::to_string(r_len) + " coordinates are an opening in " + std::to_string(r_len + ceil_log2(k)));
+    ProofReader pr(proof, proof_len);
+    const WireDotProductProofLog P = read_dpl(pr);
+    if (!pr.done()) throw Error("proof bytes: trailing data");
+    ProofReader cr(commitment, commitment_len);
+    const std::vector<WirePoint> comm = cr.pts_vec();
+    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    ProofTranscript t(tv, tu);
+    ScVec rv, ev; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i])); for (size_t b = 0; b < k; b++) ev.push_back(Sc::from_abi(evals[b]));
+    *ok = Verifier::combined_table_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, rv, ev, comm) ? 1 : 0;
+    return 0;)
+}
+int32_t lasso_host_polys_evaluate(lasso_host* h, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len, lasso_fr* evals) {
+  GUARD(
+    if ((!r && r_len) || !evals) throw Error("lasso_host_polys_evaluate: null argument");
+    const PolysShape sh = polys_check("lasso_host_polys_evaluate", h, nullptr, vecs, k, s, r_len);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    const Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, nullptr);
+    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
+    return 0;)
+}
+int32_t lasso_host_polys_stats(lasso_host* h, uint64_t* vectors_committed, uint64_t* vectors_opened, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_polys_stats: null host");
+    if (vectors_committed) *vectors_committed = h->polys_count[0];
+    if (vectors_opened) *vectors_opened = h->polys_count[1];
+    if (reset) h->polys_count[0] = h->polys_count[1] = 0;
+    return 0;)
+}
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {
   GUARD(const Strategy S = Strategy::from_abi(st); (void)S; return 0;)
 }

@@ -361,6 +361,18 @@ class Verifier {
     const Pt rhs = (G_hat + g.Qmul.mul(a_hat)) * p.z1 + g.hmul.mul(p.z2);
     return ed_eq(lhs.p, rhs.p);
   }
+  // CombinedTableEvalProof::verify (subtables/mod.rs:315-375) over a caller's generators and transcript: the counterpart of Prover::polys_eval_prove
+  static bool combined_table_eval_verify_plain(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& proof, const PolyCommitmentGens& g, const ScVec& r,
+                                               const ScVec& evals_in, const std::vector<WirePoint>& comm) {
+    t.append_protocol_name("Lasso CombinedTableEvalProof");
+    ScVec evals = evals_in; evals.resize(next_pow2(evals.size()), Sc::zero());
+    t.append_scalars("evals_ops_val", evals);
+    const ScVec ch = t.challenge_vector("challenge_combine_n_to_one", ceil_log2(evals.size()));
+    const Sc joint = bound_bot_all(evals, ch);
+    ScVec r_joint = ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
+    t.append_scalar("joint_claim_eval", joint);
+    return poly_eval_verify_plain(d, t, points_msm, proof, g, r_joint, joint, comm);
+  }
  private:
   // subtables/mod.rs:315-375
   bool combined_table_eval_verify(const WireDotProductProofLog& proof, const ScVec& r, const ScVec& evals_in, const std::vector<WirePoint>& comm) {

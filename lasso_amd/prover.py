@@ -491,6 +491,70 @@ class HostProver:
         "available": whether the device library has them} (lasso_host_poly_stats)"""
         return self._stats(self._ext("poly").lasso_host_poly_stats, reset, "u64_commit_elements", "u64_open_elements", "available")
 
+    # ---- include/lasso_prover_polys.h: several vectors under one commitment, opened at r in one proof
+    def _polys_vecs(self, vectors, s):
+        """(lasso_host_poly_vec array, k, s, what must stay alive).  A vector is whatever _poly_values takes — a (s,) uint64 array ("u64"), a (s, 4) uint64 array
+        ("field"), a tensor on this host's GPU, a DeviceVector — or a pair (device pointer, "u64" / "field"): s elements of that form in device memory of this host's
+        context, 16-byte aligned.  All have the same length; `s` is needed only where every vector is such a pair."""
+        vectors = list(vectors)
+        arr, keep, lens = (_abi.PolyVec * max(len(vectors), 1))(), [], set() if s is None else {int(s)}
+        for i, v in enumerate(vectors):
+            if isinstance(v, tuple) and len(v) == 2 and isinstance(v[1], str):
+                arr[i] = _abi.PolyVec(C.c_void_p(int(v[0])), self._values_form(v[1]), 1)
+                continue
+            ptr, f, on_dev, n, alive = self._poly_values(v, None)
+            arr[i] = _abi.PolyVec(ptr, f, on_dev); keep.append(alive); lens.add(n)
+        if len(lens) > 1:
+            raise LassoError(f"polys: the vectors must have one length, got {sorted(lens)}")
+        if not lens and vectors:
+            raise LassoError("polys: `s` is needed where every vector is a (device pointer, form) pair")
+        return arr, len(vectors), (lens.pop() if lens else 0), keep
+
+    def polys_commit(self, pgens, vectors, s=None):
+        """DensePolynomial::merge(vectors).commit over `pgens` — a poly_gens for log2(s) + log2(next_pow2(k)) variables: the bytes [u64 L'][L' x 32 B]
+        (lasso_host_polys_commit; see _polys_vecs for what a vector may be).  The merge is never made: every vector is read where it lies."""
+        lib = self._ext("polys")
+        arr, k, s, keep = self._polys_vecs(vectors, s)
+        return self._bytes_call(lib.lasso_host_polys_commit, self.h, pgens, arr, k, s)
+
+    def polys_open(self, pgens, vectors, r, transcript, tape, s=None):
+        """CombinedTableEvalProof::prove of the merged `vectors` at r = (log2 s, 4) uint64 against live transcript and tape pairs: (proof bytes, evals as (k, 4) uint64
+        memory words, fully reduced), evals[b] = MLE(vectors[b])(r) (lasso_host_polys_open)"""
+        lib = self._ext("polys")
+        arr, k, s, keep = self._polys_vecs(vectors, s)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        evals = np.zeros((max(k, 1), 4), dtype=np.uint64)
+        proof = self._bytes_call(lambda *a: lib.lasso_host_polys_open(self.h, pgens, arr, k, s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1],
+                                                                       evals.ctypes.data_as(C.c_void_p), *a))
+        return proof, evals[:k]
+
+    def polys_verify(self, pgens, r, evals, proof, commitment, transcript):
+        """CombinedTableEvalProof::verify over the wire bytes against a live transcript pair; evals = (k, 4) uint64: True = Ok(()), False = Err; LassoError on bytes
+        that do not deserialize (lasso_host_polys_verify)"""
+        lib = self._ext("polys")
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        evals = np.ascontiguousarray(evals, dtype=np.uint64).reshape(-1, 4)
+        ok = C.c_int32(-1)
+        self._chk(lib.lasso_host_polys_verify(self.h, pgens, r.ctypes.data_as(C.c_void_p), r.shape[0], evals.ctypes.data_as(C.c_void_p), evals.shape[0], transcript[0], transcript[1],
+                                              bytes(proof), len(proof), bytes(commitment), len(commitment), C.byref(ok)))
+        return ok.value == 1
+
+    def polys_evaluate(self, vectors, r, s=None):
+        """evals[b] = MLE(vectors[b])(r) as (k, 4) uint64, by the opening's own pass over the vectors, without generators or transcript (lasso_host_polys_evaluate):
+        what a verifier computes of the public columns"""
+        lib = self._ext("polys")
+        arr, k, s, keep = self._polys_vecs(vectors, s)
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        evals = np.zeros((max(k, 1), 4), dtype=np.uint64)
+        self._chk(lib.lasso_host_polys_evaluate(self.h, arr, k, s, r.ctypes.data_as(C.c_void_p), r.shape[0], evals.ctypes.data_as(C.c_void_p)))
+        return evals[:k]
+
+    def polys_stats(self, reset=False):
+        """{"vectors_committed", "vectors_opened"}: vectors this host took through polys_commit / polys_open so far (lasso_host_polys_stats)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self._ext("polys").lasso_host_polys_stats(self.h, C.byref(a), C.byref(b), 1 if reset else 0))
+        return {"vectors_committed": a.value, "vectors_opened": b.value}
+
     def strategy_check(self, strategy):
         """validate a strategy descriptor without proving (lasso_host_strategy_check): raises LassoError with the reason"""
         self._chk(self.lib.lasso_host_strategy_check(strategy_ptr(strategy)))
