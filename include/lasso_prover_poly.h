@@ -8,7 +8,7 @@
  * Vectors come as field elements or as 64-bit integers (enum lasso_values_form, lasso_hip_values.h), from host memory or from device memory of this host's context.  The
  * 64-bit form is read as it is on the device (include/lasso_hip_poly.h: 8 bytes per element in the commitment's MSM and in the opening's L * Z).  Those device entries are
  * weak references of the library: linked against an implementation of lasso_hip.h alone, the integers are lifted to field elements on the host and the 32-byte entries
- * serve — the bytes are the same.  Not offered: blinded commitments, slab mode (world > 1).  Several vectors under one commitment
+ * serve — the bytes are the same.  Blinded (hiding) commitments and openings: include/lasso_prover_blind.h.  Not offered: slab mode (world > 1).  Several vectors under one commitment
  * and in one opening: include/lasso_prover_polys.h.
  * The evaluation of a 64-bit vector at r is Zr of lasso_host_poly_open (the opening computes <L * Z, R> anyway); lasso_host_values_evaluate keeps taking field elements only.
  * Separate from lasso_prover.h for the reason lasso_prover_values.h is.  Exported by liblasso_prover.so and liblasso_prover_bn254.so. */

@@ -14,7 +14,7 @@
  * lasso_host_poly_commitment_append; the proof bytes are the serialized DotProductProofLog as for lasso_host_poly_open.
  * Refused, -1 with a message, before anything is launched: k = 0; nv + kappa > 30; generators for another number of variables; r_len != nv; a row of the merged matrix that
  * would span several vectors (2^(nv + kappa - left) > s: only where k is large against s, e.g. five vectors of two values); per vector what lasso_host_poly_commit refuses,
- * with the vector's index; a slab-mode host.  Not offered: blinded commitments, vectors of different lengths.
+ * with the vector's index; a slab-mode host.  Blinded (hiding) commitments: include/lasso_prover_blind.h.  Not offered: vectors of different lengths.
  * Separate from lasso_prover.h for the reason lasso_prover_values.h is.  Exported by liblasso_prover.so and liblasso_prover_bn254.so. */
 #ifndef LASSO_PROVER_POLYS_H
 #define LASSO_PROVER_POLYS_H

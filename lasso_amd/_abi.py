@@ -204,6 +204,12 @@ PROVER_EXTENSIONS = {
                                        "lasso_host_polys_open": [vp, vp, _P(PolyVec), sz, sz, vp, sz, _vt, vp, _vt, vp, vp, vp, sz, _P(sz)],
                                        "lasso_host_polys_verify": [vp, vp, vp, sz, vp, sz, _vt, vp, C.c_char_p, sz, C.c_char_p, sz, _P(i32)],
                                        "lasso_host_polys_evaluate": [vp, _P(PolyVec), sz, sz, vp, sz, vp], "lasso_host_polys_stats": [vp, _P(u64), _P(u64), i32]}),
+    "blind": ("lasso_prover_blind.h", {"lasso_host_poly_commit_blinded": [vp, vp, vp, i32, i32, sz, _vt, vp, vp, vp, sz, _P(sz)],
+                                       "lasso_host_poly_open_blinded": [vp, vp, vp, i32, i32, sz, vp, sz, vp, vp, _vt, vp, _vt, vp, vp, vp, vp, sz, _P(sz)],
+                                       "lasso_host_poly_verify_committed": [vp, vp, vp, sz, C.c_char_p, _vt, vp, C.c_char_p, sz, C.c_char_p, sz, _P(i32)],
+                                       "lasso_host_polys_commit_blinded": [vp, vp, _P(PolyVec), sz, sz, _vt, vp, vp, vp, sz, _P(sz)],
+                                       "lasso_host_polys_open_blinded": [vp, vp, _P(PolyVec), sz, sz, vp, sz, vp, _vt, vp, _vt, vp, vp, vp, sz, _P(sz)],
+                                       "lasso_host_blind_stats": [vp, _P(u64), _P(u64), i32]}),
 }
 
 

@@ -1502,7 +1502,7 @@ class Prover {
     rand_out = rand; return out;
   }
 
-  // ---- BulletReductionProof::prove + DotProductProofLog::prove (bullet.rs:40-154, dot_product.rs:167-249), blinds of x and y are zero on this path.
+  // ---- BulletReductionProof::prove + DotProductProofLog::prove (bullet.rs:40-154, dot_product.rs:167-249); the blinds of x and y are zero unless the caller names them.
   // The generator vector is never folded: G^(k)_i = sum_b w_b G_{b*n_k+i} with w the running tensor of u^{+-1}, so every L_k / R_k / g_hat is one
   // MSM over the ORIGINAL (precomputed) generators with scalars a (x) w — same group elements as the reference's fold-then-MSM.
   Pt msm_dev(const PolyCommitmentGens& g, const lasso_fr* d_scalars, size_t n) {
@@ -1512,8 +1512,11 @@ class Prover {
   // d_a0 = x (here L*Z), d_b0 = a (here the R half of the eq table), both of length n and resident on the device; a_bytes = serialize(a)
   // Static over (device, transcript, tape): a Lasso proof's three openings call it through the member form below, the opening of a caller's own vector
   // (include/lasso_prover_poly.h lasso_host_poly_open) with its own transcript and no Prover at all — one text.
+  // blind_x / blind_y (null = zero; include/lasso_prover_blind.h): Cx = <x, G> + blind_x * h and Cy = y * G_1 + blind_y * h, the h terms added on the host under the MSM;
+  // blind_fin starts at their sum (dot_product.rs:206-212).  cy_out receives Cy's 32 wire bytes.  Null pointers issue the launches and write the bytes they always did.
   DotProductProofLog dot_product_log_prove(const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y) { return dot_product_log_prove(d, t, tape, g, d_a0, d_b0, a_bytes, y); }
-  static DotProductProofLog dot_product_log_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y) {
+  static DotProductProofLog dot_product_log_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, const PolyCommitmentGens& g, DBuf& d_a0, DBuf& d_b0, const std::vector<uint8_t>& a_bytes, const Sc& y,
+                                                  const Sc* blind_x = nullptr, const Sc* blind_y = nullptr, uint8_t* cy_out = nullptr) {
     static_assert(sizeof(Sc) == sizeof(lasso_fr), "ScVec is uploaded as an array of lasso_fr");
     Trace tr("DotProductProofLog.prove", d.ctx);
     t.append_protocol_name("dot product proof (log)");
@@ -1546,15 +1549,20 @@ class Prover {
       d.chk(lasso_defer_next(d.ctx), "lasso_defer_next");
       if (shard) d.chk(lasso_msm_dev_slab(d.ctx, g.bases_slab, d_a0.p, n, cw, cr, nullptr, nullptr, &cx), "lasso_msm_dev_slab");
       else d.chk(lasso_msm_dev(d.ctx, g.bases, d_a0.p, n, &cx), "lasso_msm_dev");
-      uint8_t cy[32]; compress_one(g.Qmul.mul(y), cy);
+      uint8_t cy[32]; compress_one(blind_y ? g.Qmul.mul(y) + g.hmul.mul(*blind_y) : g.Qmul.mul(y), cy);
+      Pt hx; if (blind_x) hx = g.hmul.mul(*blind_x);
       d.chk(lasso_result_wait(d.ctx, (lasso_fr*)&cx, 4), "lasso_result_wait");
       Pt cxp = Pt::from_abi(cx); if (shard) sum_points(&cx, 1, &cxp);
+      if (blind_x) cxp = cxp + hx;
       compress_one(cxp, buf); t.append_point_bytes("Cx", buf);
       t.append_point_bytes("Cy", cy);
+      if (cy_out) memcpy(cy_out, cy, 32);
     }
-    // bullet reduction (bullet.rs:40-154), blind = blind_x + blind_y = 0
+    // bullet reduction (bullet.rs:40-154), blind = blind_x + blind_y
     lasso_fr *a_cur = d_a0.p, *a_nxt = d_a1.p, *b_cur = d_b0.p, *b_nxt = d_b1.p, *w_cur = d_w0.p, *w_nxt = d_w1.p;
     Sc blind_fin = Sc::zero(); size_t nk = n, nw = 1, round = 0;
+    if (blind_x) blind_fin += *blind_x;
+    if (blind_y) blind_fin += *blind_y;
     bool have_u = false; lasso_fr ua, uia;
     // Rounds launched AHEAD (one GPU): the kernel of round k+1 is enqueued behind round k before round k's L, R are back; it waits on the device for the challenge the host posts
     // (lasso_bullet_post) — the host turn between two rounds is ~4 us of work, the launch and its dispatch were 27 us more (include/lasso_hip.h).  `queued`: this round's kernel is
@@ -1657,14 +1665,15 @@ class Prover {
     P.z2 = a_hat * (c * blind_fin + r_beta) + r_delta;
     return P;
   }
-  // ---- PolyEvalProof::prove (dense_mlpoly.rs:302-359), blinds None
+  // ---- PolyEvalProof::prove (dense_mlpoly.rs:302-359); blinds None unless named
   // One GPU, the whole polynomial resident: everything stays on the device — the two halves of the eq table (eq_poly.rs:44-52), L*Z (dense_mlpoly.rs:184-207); only
   // serialize(R) comes back.  Static for the reason dot_product_log_prove is.  matvec_u64 != null: d_poly holds 64-bit integers, Z[i] = F::from(d_poly[i]), and L*Z reads
   // them as they are (include/lasso_hip_poly.h lasso_matvec_left_u64_dev).  Zr == null: the evaluation is not known yet — it is <L*Z, R>, taken from the vector just
-  // computed (2^right products on the host); *Zr_out receives what the proof is about either way.
+  // computed (2^right products on the host); *Zr_out receives what the proof is about either way.  blinds (2^left row blinds of the commitment) / blind_Zr, each null
+  // = None: LZ_blind = <L, blinds> on the host (:325-344); C_Zr_out receives Zr * G_1 + blind_Zr * h in wire form, the C_Zr' of :358.
   typedef int32_t (*MatvecU64)(lasso_ctx*, const uint64_t*, const lasso_fr*, size_t, size_t, lasso_fr*);
   static DotProductProofLog poly_eval_prove_resident(const Dev& d, ProofTranscript& t, RandomTape& tape, const void* d_poly, MatvecU64 matvec_u64, size_t num_vars, const ScVec& r, const Sc* Zr, Sc* Zr_out,
-                                                     const PolyCommitmentGens& g) {
+                                                     const PolyCommitmentGens& g, const ScVec* blinds = nullptr, const Sc* blind_Zr = nullptr, uint8_t* C_Zr_out = nullptr) {
     Trace tr("DensePolyEval.prove", d.ctx);
     t.append_protocol_name("polynomial evaluation proof");
     LASSO_REQUIRE(r.size() == num_vars && d_poly);
@@ -1687,19 +1696,29 @@ class Prover {
       y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(lz[i]) * R[i];
     }
     if (Zr_out) *Zr_out = y;
-    return dot_product_log_prove(d, t, tape, g, d_LZ, d_R, a_bytes, y);
+    Sc LZ_blind;
+    if (blinds) LZ_blind = left_blind(*blinds, r.data(), left);
+    return dot_product_log_prove(d, t, tape, g, d_LZ, d_R, a_bytes, y, blinds ? &LZ_blind : nullptr, blind_Zr, C_Zr_out);
+  }
+  // <EqPolynomial(point[0 .. left)).evals(), blinds>: the blind of L * Z under row blinds (dense_mlpoly.rs:330-333)
+  static Sc left_blind(const ScVec& blinds, const Sc* point, size_t left) {
+    const ScVec L = eq_evals_host(point, left);
+    LASSO_REQUIRE(blinds.size() == L.size());
+    Sc acc = Sc::zero(); for (size_t i = 0; i < L.size(); i++) acc += L[i] * blinds[i];
+    return acc;
   }
   // ---- CombinedTableEvalProof::prove (subtables/mod.rs:285-313) of DensePolynomial::merge (dense_mlpoly.rs:251-261) of a caller's k vectors of 2^nv values each, the
   // merge never made: vector b is block b of the merged matrix (2^(left - kappa) whole rows, kappa = log2 next_pow2(k)), so prep_open's factorisation below applies with
   // the blocks read where they lie, each in its own form (a 64-bit block through matvec_u64).  polys_pass is everything that depends on r alone: the M_b, the right-half
   // table and evals[b] = <M_b, R> (k * 2^right products on the host); polys_eval_prove draws the challenges afterwards and ends where every opening does.
   struct PolyBlock { const void* d; bool u64; };
-  struct PolysPass { DBuf M, R; ScVec evals; size_t kappa = 0, right = 0; };
+  struct PolysPass { DBuf M, R; ScVec evals, r_left; size_t kappa = 0, right = 0; };   // r_left: r[0 .. left - kappa), the point's share of the row index
   static PolysPass polys_pass(const Dev& d, const std::vector<PolyBlock>& blocks, MatvecU64 matvec_u64, size_t nv, const ScVec& r) {
     PolysPass ps; const size_t k = blocks.size();
     ps.kappa = ceil_log2(k);
     const size_t left = (nv + ps.kappa) / 2; ps.right = nv + ps.kappa - left;
     LASSO_REQUIRE(k >= 1 && r.size() == nv && left >= ps.kappa);   // left >= kappa: no row of the merged matrix spans two vectors
+    ps.r_left.assign(r.begin(), r.begin() + (left - ps.kappa));
     const size_t lrows = (size_t)1 << (left - ps.kappa), Rn = (size_t)1 << ps.right;
     ps.M = DBuf(d, k * Rn); ps.R = DBuf(d, Rn);
     DBuf Lp(d, lrows);
@@ -1716,7 +1735,8 @@ class Prover {
     for (size_t b = 0; b < k; b++) { Sc y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(m[b * Rn + i]) * R[i]; ps.evals.push_back(y); }
     return ps;
   }
-  static DotProductProofLog polys_eval_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, PolysPass& ps, const PolyCommitmentGens& g) {
+  // blinds (null = None): the 2^left row blinds of the merged commitment, zero blocks included; the left half of ch || r is eq(ch) (x) eq(r[0 .. left - kappa))
+  static DotProductProofLog polys_eval_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, PolysPass& ps, const PolyCommitmentGens& g, const ScVec* blinds = nullptr) {
     const size_t k = ps.evals.size(), K = (size_t)1 << ps.kappa, Rn = (size_t)1 << ps.right;
     t.append_protocol_name("Lasso CombinedTableEvalProof");
     ScVec evals = ps.evals; evals.resize(K, Sc::zero());
@@ -1738,7 +1758,9 @@ class Prover {
     }
     std::vector<uint8_t> a_bytes(32 * Rn);
     d.chk(lasso_fr_to_bytes(d.ctx, ps.R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    return dot_product_log_prove(d, t, tape, g, d_LZ, ps.R, a_bytes, joint);
+    Sc LZ_blind;
+    if (blinds) { ScVec pt = ch; pt.insert(pt.end(), ps.r_left.begin(), ps.r_left.end()); LZ_blind = left_blind(*blinds, pt.data(), pt.size()); }
+    return dot_product_log_prove(d, t, tape, g, d_LZ, ps.R, a_bytes, joint, blinds ? &LZ_blind : nullptr);
   }
   DotProductProofLog poly_eval_prove(const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const Sc& Zr, const PolyCommitmentGens& g) {
     if (this->P == 1 && d_poly) return poly_eval_prove_resident(d, t, tape, d_poly, nullptr, num_vars, r, &Zr, nullptr, g);

@@ -16,6 +16,7 @@
 #include "../../include/lasso_hip_poly.h"
 #include "../../include/lasso_prover_poly.h"
 #include "../../include/lasso_prover_polys.h"
+#include "../../include/lasso_prover_blind.h"
 
 using namespace lasso;
 
@@ -65,6 +66,7 @@ struct lasso_host {
   std::unique_ptr<ShmComm> shm;   // slab mode's native intra-node exchange (lasso_host_set_comm_shm); outlives every proof of this host
   uint64_t ext_count[EXT_COUNT][2] = {};   // the counters of EXTS' rows, for this host
   uint64_t polys_count[2] = {};            // lasso_host_polys_stats: vectors committed to / opened (no device entry of their own, so no row of EXTS)
+  uint64_t blind_count[2] = {};            // lasso_host_blind_stats: rows blinded on the device / on the host (likewise)
   TablesMle tables_mle() { TablesMle m; if (lasso_tables_mle && sw::verify_device_mle()) { m.fn = &lasso_tables_mle; m.min_entries = sw::mle_device_min(); m.counter = ext_count[EXT_MLE]; } return m; }
   GensDevice gens_device() { GensDevice g; if (lasso_points_from_candidates && sw::gens_device()) { g.fn = &lasso_points_from_candidates; g.min_points = sw::gens_device_min(); g.batch = sw::gens_device_batch(); g.counter = ext_count[EXT_GENS]; } return g; }
   PointsMsm points_msm() { PointsMsm m; if (lasso_msm_points && sw::verify_msm_points()) { m.fn = &lasso_msm_points; m.counter = ext_count[EXT_MSM_POINTS]; } return m; }
@@ -790,6 +792,176 @@ int32_t lasso_host_polys_stats(lasso_host* h, uint64_t* vectors_committed, uint6
     if (vectors_committed) *vectors_committed = h->polys_count[0];
     if (vectors_opened) *vectors_opened = h->polys_count[1];
     if (reset) h->polys_count[0] = h->polys_count[1] = 0;
+    return 0;)
+}
+// ---- include/lasso_prover_blind.h: the hiding form of the two headers above, composed of the device entries they use and of slab mode's two
+}  // extern "C"
+// `count` scalars of the caller's, memory form, any representative -> Sc; and back, fully reduced
+static ScVec blinds_in(const lasso_fr* b, size_t count) { ScVec v; v.reserve(count); for (size_t i = 0; i < count; i++) v.push_back(Sc::from_abi(b[i])); return v; }
+static void blinds_check(const std::string& w, const void* blinds) {
+  if ((uintptr_t)blinds & 7) throw Error(w + ": the blinds pointer is misaligned (host memory: 8 bytes)");
+}
+// tape.random_vector("poly_blinds", count) (dense_mlpoly.rs:166-170) into the caller's array
+static ScVec blinds_draw(const lasso_transcript_vtbl* pv, void* pu, size_t count, lasso_fr* out) {
+  RandomTape tape(pv, pu);
+  const ScVec b = tape.random_vector("poly_blinds", count);
+  for (size_t i = 0; i < count; i++) out[i] = (b[i] * Sc::one()).abi();
+  return b;
+}
+// rows[i] += blinds[i] * h on the host: `rows` wire rows are decoded as the verifier would decode them, the sums compressed in one batch
+static void blind_rows_host(lasso_host* h, const PolyCommitmentGens& g, const Sc* blinds, size_t rows, uint8_t* wire) {
+  const std::vector<WirePoint> pts = decode_points(h->dev, h->wire_decoder(), wire, rows, "commitment rows");
+  std::vector<Pt> sum(rows);
+  for (size_t i = 0; i < rows; i++) { const Pt b = g.hmul.mul(blinds[i]); sum[i] = pts[i].infinity ? b : pts[i].p + b; }
+  std::vector<uint8_t> out; compress_batch(sum, out);
+  memcpy(wire, out.data(), 32 * rows);
+  h->blind_count[1] += rows;
+}
+// `rows` whole rows of R values of one vector, blinded, as wire bytes at `wire`: row i = <Z_i, G> + blinds[i] * h (commitments.rs:84-93).  hb: the one-point base [h], made by
+// the first vector that takes the device route and destroyed by the caller
+static void blind_commit_rows(lasso_host* h, const PolyCommitmentGens& g, const PolyOperand& o, size_t s, size_t rows, size_t R, const Sc* blinds, lasso_bases** hb, uint8_t* wire) {
+  const Dev& d = h->dev;
+  if (o.u64) {   // read as 8-byte integers; the rows come back in wire form
+    uint64_t bits = 0;
+    d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
+    d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed_u64");
+    h->ext_count[EXT_POLY][0] += s;
+    blind_rows_host(h, g, blinds, rows, wire);
+    return;
+  }
+  // field elements: data rows and blind rows as the kernels' own points, side by side, added and compressed by slab mode's reduction
+  const size_t rb = lasso_point_row_bytes();
+  struct Bytes { const Dev& d; void* p; ~Bytes() { try { if (p) d.free(p); } catch (...) {} } } parts{d, d.alloc_bytes(2 * rows * rb)};
+  int32_t rc = lasso_hyrax_commit_rows_dev(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, parts.p);
+  if (rc == LASSO_ERR_UNSUPPORTED) {   // a device library without row sums on the device: wire rows, blinded on the host
+    d.chk(lasso_hyrax_commit_compressed(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed");
+    blind_rows_host(h, g, blinds, rows, wire);
+    return;
+  }
+  d.chk(rc, "lasso_hyrax_commit_rows_dev");
+  if (!*hb) d.chk(lasso_bases_create(d.ctx, &g.affine[g.n + 1], 1, hb), "lasso_bases_create");
+  DBuf d_bl(d, rows);
+  std::vector<lasso_fr> bl(rows); for (size_t i = 0; i < rows; i++) bl[i] = blinds[i].abi();
+  d.chk(lasso_upload(d.ctx, d_bl.p, bl.data(), rows * sizeof(lasso_fr)), "lasso_upload");
+  d.chk(lasso_hyrax_commit_rows_dev(d.ctx, d_bl.p, rows, 1, *hb, (uint8_t*)parts.p + rows * rb), "lasso_hyrax_commit_rows_dev");
+  d.chk(lasso_points_reduce_compress(d.ctx, parts.p, 2, rows, wire), "lasso_points_reduce_compress");
+  h->blind_count[0] += rows;
+}
+struct BlindBase { const Dev& d; lasso_bases* b = nullptr; explicit BlindBase(const Dev& d_) : d(d_) {} ~BlindBase() { if (b) lasso_bases_destroy(d.ctx, b); } };
+extern "C" {
+int32_t lasso_host_poly_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s,
+                                       const lasso_transcript_vtbl* pv, void* pu, lasso_fr* blinds_out, uint8_t* out, size_t cap, size_t* len) {
+  GUARD(
+    poly_check("lasso_host_poly_commit_blinded", h, g, values, form, on_device, s);
+    if (!pv || !blinds_out) throw Error("lasso_host_poly_commit_blinded: null argument");
+    blinds_check("lasso_host_poly_commit_blinded", blinds_out);
+    const size_t nv = g->num_vars, L = (size_t)1 << (nv / 2), R = (size_t)1 << (nv - nv / 2);
+    const ScVec blinds = blinds_draw(pv, pu, L, blinds_out);
+    std::vector<uint8_t> rows(32 * L);
+    {
+      PolyOperand o; poly_operand(h, values, form, on_device, s, o);
+      BlindBase hb(h->dev);
+      try { blind_commit_rows(h, *g->g, o, s, L, R, blinds.data(), &hb.b, rows.data()); } catch (...) { h->dev.abort_all(); throw; }
+    }
+    ProofWriter w; w.pts_vec(rows);
+    return emit(w.b, out, cap, len);)
+}
+int32_t lasso_host_poly_open_blinded(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len,
+                                     const lasso_fr* blinds, const lasso_fr* blind_Zr, const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu,
+                                     lasso_fr* Zr, uint8_t C_Zr[32], uint8_t* proof, size_t cap, size_t* len) {
+  GUARD(
+    poly_check("lasso_host_poly_open_blinded", h, g, values, form, on_device, s);
+    if (!r || !tv || !pv) throw Error("lasso_host_poly_open_blinded: null argument");
+    if (r_len != g->num_vars) throw Error("lasso_host_poly_open_blinded: the point must have num_vars coordinates");
+    blinds_check("lasso_host_poly_open_blinded", blinds); blinds_check("lasso_host_poly_open_blinded", blind_Zr);
+    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    ScVec bl; Sc bz;
+    if (blinds) bl = blinds_in(blinds, (size_t)1 << (g->num_vars / 2));
+    if (blind_Zr) bz = Sc::from_abi(*blind_Zr);
+    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
+    Sc y; DotProductProofLog P; uint8_t cy[32];
+    try {
+      P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g, blinds ? &bl : nullptr, blind_Zr ? &bz : nullptr, cy);
+    } catch (...) { h->dev.abort_all(); throw; }
+    if (o.u64) h->ext_count[EXT_POLY][1] += s;
+    if (Zr) *Zr = (y * Sc::one()).abi();
+    if (C_Zr) memcpy(C_Zr, cy, 32);
+    ProofWriter w; P.write(w);
+    return emit(w.b, proof, cap, len);)
+}
+int32_t lasso_host_poly_verify_committed(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const uint8_t C_Zr[32], const lasso_transcript_vtbl* tv, void* tu,
+                                         const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
+  GUARD(
+    if (!h || !g || !g->g || !r || !C_Zr || !tv || !proof || !commitment || !ok) throw Error("lasso_host_poly_verify_committed: null argument");
+    if (g->owner != h) throw Error("lasso_host_poly_verify_committed: the generators belong to another host");
+    if (h->dev.comm.sharded()) throw Error("lasso_host_poly_verify_committed: a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+    if (r_len != g->num_vars) throw Error("lasso_host_poly_verify_committed: the point must have num_vars coordinates");
+    ProofReader pr(proof, proof_len);
+    const WireDotProductProofLog P = read_dpl(pr);
+    if (!pr.done()) throw Error("proof bytes: trailing data");
+    ProofReader cr(commitment, commitment_len);
+    const std::vector<WirePoint> comm = cr.pts_vec();
+    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    WirePoint cz;
+    if (!decompress_point(C_Zr, cz.p, cz.infinity)) throw Error("C_Zr bytes: invalid point encoding");
+    if (cz.infinity) cz.p = Pt::identity();
+    compress_affine_pt(cz.p, cz.infinity, cz.bytes);
+    ProofTranscript t(tv, tu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    *ok = Verifier::poly_eval_verify(h->dev, t, h->points_msm(), P, *g->g, rv, cz, comm) ? 1 : 0;
+    return 0;)
+}
+int32_t lasso_host_polys_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s,
+                                        const lasso_transcript_vtbl* pv, void* pu, lasso_fr* blinds_out, uint8_t* out, size_t cap, size_t* len) {
+  GUARD(
+    if (!g || !g->g) throw Error("lasso_host_polys_commit_blinded: null argument");
+    const PolysShape sh = polys_check("lasso_host_polys_commit_blinded", h, g, vecs, k, s, SIZE_MAX);
+    if (!pv || !blinds_out) throw Error("lasso_host_polys_commit_blinded: null argument");
+    blinds_check("lasso_host_polys_commit_blinded", blinds_out);
+    const size_t L = (size_t)1 << sh.left, R = (size_t)1 << sh.right;
+    const ScVec blinds = blinds_draw(pv, pu, L, blinds_out);   // one draw for the whole merge, as merge(polys).commit(gens, Some(tape)) makes it
+    std::vector<uint8_t> rows(32 * L);
+    BlindBase hb(h->dev);
+    for (size_t b = 0; b < k; b++) {   // one vector at a time: an uploaded one is released before the next
+      PolyOperand o; poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, o);
+      try { blind_commit_rows(h, *g->g, o, s, sh.rows_per, R, blinds.data() + b * sh.rows_per, &hb.b, rows.data() + 32 * b * sh.rows_per); } catch (...) { h->dev.abort_all(); throw; }
+    }
+    if (k * sh.rows_per < L) {   // the zero blocks behind k commit to blinds[i] * h, row by row
+      std::vector<Pt> tail; for (size_t i = k * sh.rows_per; i < L; i++) tail.push_back(g->g->hmul.mul(blinds[i]));
+      std::vector<uint8_t> tb; compress_batch(tail, tb);
+      memcpy(rows.data() + 32 * k * sh.rows_per, tb.data(), tb.size());
+      h->blind_count[1] += tail.size();
+    }
+    h->polys_count[0] += k;
+    ProofWriter w; w.pts_vec(rows);
+    return emit(w.b, out, cap, len);)
+}
+int32_t lasso_host_polys_open_blinded(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len,
+                                      const lasso_fr* blinds, const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu,
+                                      lasso_fr* evals, uint8_t* proof, size_t cap, size_t* len) {
+  GUARD(
+    if (!g || !g->g || !r || !tv || !pv || !evals) throw Error("lasso_host_polys_open_blinded: null argument");
+    const PolysShape sh = polys_check("lasso_host_polys_open_blinded", h, g, vecs, k, s, r_len);
+    blinds_check("lasso_host_polys_open_blinded", blinds);
+    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
+    ScVec bl; if (blinds) bl = blinds_in(blinds, (size_t)1 << sh.left);
+    size_t wide = 0;
+    Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, &wide);
+    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
+    DotProductProofLog P;
+    try { P = Prover::polys_eval_prove(h->dev, t, tape, ps, *g->g, blinds ? &bl : nullptr); } catch (...) { h->dev.abort_all(); throw; }
+    h->ext_count[EXT_POLY][1] += wide * s; h->polys_count[1] += k;
+    ProofWriter w; P.write(w);
+    return emit(w.b, proof, cap, len);)
+}
+int32_t lasso_host_blind_stats(lasso_host* h, uint64_t* rows_device, uint64_t* rows_host, int32_t reset) {
+  GUARD(
+    if (!h) throw Error("lasso_host_blind_stats: null host");
+    if (rows_device) *rows_device = h->blind_count[0];
+    if (rows_host) *rows_host = h->blind_count[1];
+    if (reset) h->blind_count[0] = h->blind_count[1] = 0;
     return 0;)
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {

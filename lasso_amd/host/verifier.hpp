@@ -104,6 +104,24 @@ struct WireDecoder {
   uint64_t* counter = nullptr;    // points decoded on the device, per host (lasso_host_wire_stats)
 };
 
+// k encodings in one batch by the decoder the verifier would take for them: the device decoder where there is one and the batch reaches its threshold, the host decoder
+// otherwise.  A rejected encoding throws in ProofReader::pt's words (`what` names the bytes).
+inline std::vector<WirePoint> decode_points(const Dev& d, const WireDecoder& dec, const uint8_t* enc, size_t k, const char* what) {
+  std::vector<WirePoint> pts(k);
+  if (dec.fn && k && k >= dec.min_points) {
+    std::vector<uint8_t> canon(32 * k), status(k); std::vector<lasso_affine> aff(k);
+    d.chk(dec.fn(d.ctx, enc, k, aff.data(), canon.data(), status.data()), "lasso_points_decompress");
+    if (dec.counter) *dec.counter += k;
+    for (size_t i = 0; i < k; i++) { if (status[i] > LASSO_WIRE_OK_IDENTITY) throw Error(std::string(what) + ": invalid point encoding"); pts[i] = wire_point_from_abi(aff[i], &canon[32 * i], status[i]); }
+    return pts;
+  }
+  for (size_t i = 0; i < k; i++) {
+    if (!decompress_point(enc + 32 * i, pts[i].p, pts[i].infinity)) throw Error(std::string(what) + ": invalid point encoding");
+    compress_affine_pt(pts[i].p, pts[i].infinity, pts[i].bytes);
+  }
+  return pts;
+}
+
 // The table-free MSM over caller points as the verifier sees it (prover_capi.cpp fills it in: lasso_msm_points is a weak reference too, include/lasso_hip_msm.h)
 struct PointsMsm {
   int32_t (*fn)(lasso_ctx*, const lasso_affine*, const lasso_fr*, size_t, lasso_point*) = nullptr;
@@ -322,7 +340,12 @@ class Verifier {
   bool poly_eval_verify_plain(const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) { return poly_eval_verify_plain(d, t, points_msm, p, g, r, Zr, comm); }
  public:
   static bool poly_eval_verify_plain(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) {
-    const Pt C_Zr = g.Qmul.mul(Zr);   // Zr.commit(&0, &gens.gens.gens_1) = Zr * G[0] + 0 * h
+    WirePoint C_Zr; C_Zr.p = g.Qmul.mul(Zr);   // Zr.commit(&0, &gens.gens.gens_1) = Zr * G[0] + 0 * h
+    wire(C_Zr.p, C_Zr.bytes);
+    return poly_eval_verify(d, t, points_msm, p, g, r, C_Zr, comm);
+  }
+  // PolyEvalProof::verify (dense_mlpoly.rs:361-386): the evaluation comes as a commitment C_Zr = Zr * G_1 + blind_Zr * h, decoded from its wire bytes by the caller
+  static bool poly_eval_verify(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const WirePoint& C_Zr, const std::vector<WirePoint>& comm) {
     t.append_protocol_name("polynomial evaluation proof");
     const size_t left = r.size() / 2;   // EqPolynomial::compute_factored_evals eq_poly.rs:44-52
     const ScVec L = eq_evals_host(r.data(), left), R = eq_evals_host(r.data() + left, r.size() - left);
@@ -334,9 +357,9 @@ class Verifier {
     t.append_protocol_name("dot product proof (log)");
     uint8_t buf[32];
     wire(C_LZ, buf); t.append_point_bytes("Cx", buf);
-    wire(C_Zr, buf); t.append_point_bytes("Cy", buf);
+    t.append_point_bytes("Cy", C_Zr.bytes);
     t.append_scalars("a", R);
-    const Pt Gamma = C_LZ + C_Zr;
+    const Pt Gamma = C_LZ + C_Zr.p;
     // verification_scalars
     const size_t lg_n = p.L_vec.size();
     if (lg_n >= 32 || p.R_vec.size() != lg_n) return false;            // InputTooLarge

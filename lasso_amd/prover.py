@@ -428,24 +428,48 @@ class HostProver:
             raise LassoError("poly: an array has shape (s,) (u64) or (s, 4) (field)")
         return a.ctypes.data_as(C.c_void_p), f, 0, a.shape[0], a
 
-    def poly_commit(self, pgens, values, form=None):
+    def poly_commit(self, pgens, values, form=None, tape=None):
         """DensePolynomial::commit of `values` (see _poly_values for what they may be) over `pgens`: the bytes [u64 L][L x 32 B] (lasso_host_poly_commit).  The 64-bit
-        form is read as it is on the device where the device library has include/lasso_hip_poly.h"""
+        form is read as it is on the device where the device library has include/lasso_hip_poly.h.  With `tape` (a live tape pair): the hiding form, commit(gens,
+        Some(tape)) — (commitment, the row blinds drawn from the tape as (L, 4) uint64 memory words) (lasso_host_poly_commit_blinded)"""
         lib = self._ext("poly")
         ptr, f, on_dev, s, keep = self._poly_values(values, form)
-        return self._bytes_call(lib.lasso_host_poly_commit, self.h, pgens, ptr, f, on_dev, s)
+        if tape is None:
+            return self._bytes_call(lib.lasso_host_poly_commit, self.h, pgens, ptr, f, on_dev, s)
+        blinds = np.zeros((1 << ((s.bit_length() - 1) // 2) if s else 1, 4), dtype=np.uint64)
+        c = self._bytes_call(self._ext("blind").lasso_host_poly_commit_blinded, self.h, pgens, ptr, f, on_dev, s, tape[0], tape[1], blinds.ctypes.data_as(C.c_void_p))
+        return c, blinds
 
     def poly_commitment_append(self, transcript, label, commitment):
         """PolyCommitment::append_to_transcript(label) against a live transcript (a (vtbl, user) pair as Transcript.pair() makes it)"""
         self._chk(self._ext("poly").lasso_host_poly_commitment_append(transcript[0], transcript[1], label, bytes(commitment), len(commitment)))
 
-    def poly_open(self, pgens, values, r, transcript, tape, form=None):
+    @staticmethod
+    def _blinds_arg(blinds, rows=None):
+        """row blinds / one blind as the C calls take them: (pointer or None, what must stay alive)"""
+        if blinds is None:
+            return None, None
+        a = np.ascontiguousarray(blinds, dtype=np.uint64).reshape(-1, 4)
+        if rows is not None and a.shape[0] != rows:
+            raise LassoError(f"blinds: {rows} row blinds of 4 words each are needed, got {a.shape[0]}")
+        return a.ctypes.data_as(C.c_void_p), a
+
+    def poly_open(self, pgens, values, r, transcript, tape, form=None, blinds=None, blind_Zr=None, committed=False):
         """PolyEvalProof::prove of `values` at r = (num_vars, 4) uint64 against live transcript and tape pairs: (proof bytes, Zr as (4,) uint64 memory words, fully
-        reduced) — Zr = the polynomial's evaluation at r, computed on the way (lasso_host_poly_open)"""
+        reduced) — Zr = the polynomial's evaluation at r, computed on the way (lasso_host_poly_open).  With `blinds` (the row blinds poly_commit returned), `blind_Zr`
+        ((4,) uint64) or committed=True: (proof, Zr, C_Zr) — C_Zr = Zr * G_1 + blind_Zr * h as 32 wire bytes, what poly_verify_committed takes
+        (lasso_host_poly_open_blinded; a keyword left out is None: zero)"""
         lib = self._ext("poly")
         ptr, f, on_dev, s, keep = self._poly_values(values, form)
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         zr = np.zeros(4, dtype=np.uint64)
+        if blinds is not None or blind_Zr is not None or committed:
+            bl, keep_b = self._blinds_arg(blinds, 1 << ((s.bit_length() - 1) // 2) if s else None)
+            bz, keep_z = self._blinds_arg(blind_Zr, 1)
+            c_zr = (C.c_uint8 * 32)()
+            proof = self._bytes_call(lambda *a: self._ext("blind").lasso_host_poly_open_blinded(self.h, pgens, ptr, f, on_dev, s, r.ctypes.data_as(C.c_void_p), r.shape[0], bl, bz, transcript[0],
+                                                                                                 transcript[1], tape[0], tape[1], zr.ctypes.data_as(C.c_void_p), c_zr, *a))
+            return proof, zr, bytes(c_zr)
         proof = self._bytes_call(lambda *a: lib.lasso_host_poly_open(self.h, pgens, ptr, f, on_dev, s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1],
                                                                       zr.ctypes.data_as(C.c_void_p), *a))
         return proof, zr
@@ -460,6 +484,24 @@ class HostProver:
         self._chk(lib.lasso_host_poly_verify(self.h, pgens, r.ctypes.data_as(C.c_void_p), r.shape[0], zr.ctypes.data_as(C.c_void_p), transcript[0], transcript[1],
                                              bytes(proof), len(proof), bytes(commitment), len(commitment), C.byref(ok)))
         return ok.value == 1
+
+    def poly_verify_committed(self, pgens, r, c_zr, proof, commitment, transcript):
+        """PolyEvalProof::verify: as poly_verify, the evaluation given as its commitment C_Zr (32 wire bytes, poly_open's third result) (lasso_host_poly_verify_committed)"""
+        lib = self._ext("blind")
+        r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
+        if len(c_zr) != 32:
+            raise LassoError("poly_verify_committed: C_Zr is 32 bytes")
+        ok = C.c_int32(-1)
+        self._chk(lib.lasso_host_poly_verify_committed(self.h, pgens, r.ctypes.data_as(C.c_void_p), r.shape[0], bytes(c_zr), transcript[0], transcript[1],
+                                                       bytes(proof), len(proof), bytes(commitment), len(commitment), C.byref(ok)))
+        return ok.value == 1
+
+    def blind_stats(self, reset=False):
+        """{"rows_device": rows this host blinded on the device (lasso_points_reduce_compress), "rows_host": rows blinded on the host (the decode route, a merge's zero
+        blocks)} (lasso_host_blind_stats)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self._ext("blind").lasso_host_blind_stats(self.h, C.byref(a), C.byref(b), 1 if reset else 0))
+        return {"rows_device": a.value, "rows_host": b.value}
 
     def values_vector(self, dense, strategy):
         """the lookup results of `dense` left ON THE DEVICE as a DeviceVector: 64-bit integers where lasso_lookup_values offers that form, field elements otherwise"""
@@ -476,11 +518,14 @@ class HostProver:
                 if form == "field" or "64-bit form" not in str(e):
                     raise
 
-    def values_commit(self, dense, strategy, pgens):
+    def values_commit(self, dense, strategy, pgens, tape=None):
         """(commitment bytes, DeviceVector): the lookup results of `dense` written by the device (values_vector), never downloaded, and their commitment over `pgens`;
-        pass the vector on to poly_open and free() it afterwards"""
+        pass the vector on to poly_open and free() it afterwards.  With `tape`: the hiding commitment, (commitment, DeviceVector, row blinds) (see poly_commit)"""
         vec = self.values_vector(dense, strategy)
         try:
+            if tape is not None:
+                c, blinds = self.poly_commit(pgens, vec, tape=tape)
+                return c, vec, blinds
             return self.poly_commit(pgens, vec), vec
         except Exception:
             vec.free()
@@ -510,20 +555,36 @@ class HostProver:
             raise LassoError("polys: `s` is needed where every vector is a (device pointer, form) pair")
         return arr, len(vectors), (lens.pop() if lens else 0), keep
 
-    def polys_commit(self, pgens, vectors, s=None):
+    @staticmethod
+    def _polys_rows(k, s):
+        """rows of the merged matrix of k vectors of s values: 2^((log2 s + kappa) / 2)"""
+        return 1 << (((max(s, 1).bit_length() - 1) + (max(k, 1) - 1).bit_length()) // 2)
+
+    def polys_commit(self, pgens, vectors, s=None, tape=None):
         """DensePolynomial::merge(vectors).commit over `pgens` — a poly_gens for log2(s) + log2(next_pow2(k)) variables: the bytes [u64 L'][L' x 32 B]
-        (lasso_host_polys_commit; see _polys_vecs for what a vector may be).  The merge is never made: every vector is read where it lies."""
+        (lasso_host_polys_commit; see _polys_vecs for what a vector may be).  The merge is never made: every vector is read where it lies.  With `tape` (a live tape
+        pair): the hiding form, (commitment, the L' row blinds of one draw as (L', 4) uint64) — every row blinded, the zero blocks' too (lasso_host_polys_commit_blinded)"""
         lib = self._ext("polys")
         arr, k, s, keep = self._polys_vecs(vectors, s)
-        return self._bytes_call(lib.lasso_host_polys_commit, self.h, pgens, arr, k, s)
+        if tape is None:
+            return self._bytes_call(lib.lasso_host_polys_commit, self.h, pgens, arr, k, s)
+        blinds = np.zeros((self._polys_rows(k, s), 4), dtype=np.uint64)
+        c = self._bytes_call(self._ext("blind").lasso_host_polys_commit_blinded, self.h, pgens, arr, k, s, tape[0], tape[1], blinds.ctypes.data_as(C.c_void_p))
+        return c, blinds
 
-    def polys_open(self, pgens, vectors, r, transcript, tape, s=None):
+    def polys_open(self, pgens, vectors, r, transcript, tape, s=None, blinds=None):
         """CombinedTableEvalProof::prove of the merged `vectors` at r = (log2 s, 4) uint64 against live transcript and tape pairs: (proof bytes, evals as (k, 4) uint64
-        memory words, fully reduced), evals[b] = MLE(vectors[b])(r) (lasso_host_polys_open)"""
+        memory words, fully reduced), evals[b] = MLE(vectors[b])(r) (lasso_host_polys_open).  `blinds`: the row blinds polys_commit returned with a tape
+        (lasso_host_polys_open_blinded); the evaluations stay in the clear and polys_verify takes the opening as it stands"""
         lib = self._ext("polys")
         arr, k, s, keep = self._polys_vecs(vectors, s)
         r = np.ascontiguousarray(r, dtype=np.uint64).reshape(-1, 4)
         evals = np.zeros((max(k, 1), 4), dtype=np.uint64)
+        if blinds is not None:
+            bl, keep_b = self._blinds_arg(blinds, self._polys_rows(k, s))
+            proof = self._bytes_call(lambda *a: self._ext("blind").lasso_host_polys_open_blinded(self.h, pgens, arr, k, s, r.ctypes.data_as(C.c_void_p), r.shape[0], bl, transcript[0], transcript[1],
+                                                                                                  tape[0], tape[1], evals.ctypes.data_as(C.c_void_p), *a))
+            return proof, evals[:k]
         proof = self._bytes_call(lambda *a: lib.lasso_host_polys_open(self.h, pgens, arr, k, s, r.ctypes.data_as(C.c_void_p), r.shape[0], transcript[0], transcript[1], tape[0], tape[1],
                                                                        evals.ctypes.data_as(C.c_void_p), *a))
         return proof, evals[:k]
