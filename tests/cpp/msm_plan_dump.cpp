@@ -1,11 +1,12 @@
 // Which MSM kernel serves a call of the device library, as lasso_hip.hip decides it: the plan functions of lasso_amd/csrc/launch_plan.cuh over the switches of
 // lasso_amd/csrc/device_switches.cuh, both included as they are (as tests/cpp/test_launch_plan_host.cpp includes them).  tests/msmvariants.py runs this program once per switch
 // setting, as a child process with that environment (the switches are read once per process), and tests/test_msm_reach_cpu.py holds every row of its table to the plan printed here.
-// stdin, one call per line:   <id> <entry> <rows> <cols> <bps> <W> <ngens>
-//   entry: hyrax_commit | hyrax_commit_compressed | hyrax_commit_compressed_u32 | hyrax_commit_rows_dev | msm | msm_dev_scaled | bullet_round
-//   rows x cols: the matrix of a commitment; msm / msm_dev_scaled: rows = 1, cols = n; bullet_round: rows = n, cols = nk
+// stdin, one call per line:   <id> <entry> <rows> <cols> <bps> <W> <ngens> <world>
+//   entry: hyrax_commit | hyrax_commit_compressed | hyrax_commit_compressed_u32 | hyrax_commit_rows_dev | msm | msm_dev_scaled | bullet_round | bullet_round_slab | msm_dev_slab
+//   rows x cols: the matrix of a commitment; msm / msm_dev_scaled / msm_dev_slab: rows = 1, cols = n; bullet_round(_slab): rows = n, cols = nk
 //   bps, W: bytes per scalar and populated nibbles as hyrax_commit_impl finds them in the data (4 and (bits + 3) / 4, or 32 and 64); ignored by the last three entries
-//   ngens: points the bases object was created from (lasso_bases_create)
+//   ngens: points the bases object was created from (lasso_bases_create); the slab entries: the rank's n / world generators, then Q and H
+//   world: ranks of slab mode (the two slab entries; 1 everywhere else)
 // stdout, one JSON object per line: {"id", "msm": MsmPlan | null, "direct": MsmDirectPlan | null, "bullet": BulletPlan | null} — the plans the call goes through.
 #include <cstdio>
 #include <cstring>
@@ -37,6 +38,11 @@ static MsmHave have_of(size_t ngens) {
   return MsmHave{ngens, mult, mult8, true, true};
 }
 
+static void print_bullet(const BulletPlan& b, size_t nk, size_t world) {   // wide: both rows get n_loc / 2 local columns (half >= P); else one row of the rank gets all n_loc, the other none
+  const bool wide = nk / 2 >= world;
+  printf("{\"w8\": %s, \"windows\": %zu, \"n_loc\": %zu, \"K\": %zu, \"ipc\": %u, \"ipc_cap\": %zu, \"world\": %zu, \"half\": %zu, \"wide\": %s, \"cols\": %zu, \"weights\": %zu}", b.w8 ? "true" : "false", b.windows, b.n_loc, b.K,
+         b.ipc, b.windows * 128, world, nk / 2, wide ? "true" : "false", wide ? b.n_loc / 2 : b.n_loc, b.n_loc * world / nk);
+}
 static void print_direct(const MsmDirectPlan& d) {
   printf("{\"w8\": %s, \"windows\": %zu, \"K\": %zu, \"ipc\": %u, \"ipc_cap\": %zu}", d.w8 ? "true" : "false", d.windows, d.K, d.ipc, d.windows * 128);
 }
@@ -55,8 +61,8 @@ static void print_run_msm(const MsmShape& s, const MsmHave& have) {
 
 int main() {
   char id[128], entry[64];
-  size_t rows, cols, ngens; unsigned bps, W;
-  while (scanf("%127s %63s %zu %zu %u %u %zu", id, entry, &rows, &cols, &bps, &W, &ngens) == 7) {
+  size_t rows, cols, ngens, world; unsigned bps, W;
+  while (scanf("%127s %63s %zu %zu %u %u %zu %zu", id, entry, &rows, &cols, &bps, &W, &ngens, &world) == 8) {
     const MsmHave have = have_of(ngens);
     const bool direct = have.mult && dsw::msm_direct();   // the entry points that choose the latency-shaped launch themselves ask this
     printf("{\"id\": \"%s\", ", id);
@@ -71,10 +77,15 @@ int main() {
     } else if (!strcmp(entry, "bullet_round")) {   // lasso_bullet_round (n = rows, nk = cols): the fused launch, else k_bullet_step + two compact rows by k_msm_direct, else two whole rows by run_msm
       const size_t n = rows, nk = cols;
       if (direct && dsw::msm_fused()) {
-        const BulletPlan b = bullet_plan(n, nk, 1, have.mult8, dsw::msm_direct_wgs());
-        printf("\"msm\": null, \"direct\": null, \"bullet\": {\"w8\": %s, \"windows\": %zu, \"n_loc\": %zu, \"K\": %zu, \"ipc\": %u, \"ipc_cap\": %zu}", b.w8 ? "true" : "false", b.windows, b.n_loc, b.K, b.ipc, b.windows * 128);
+        printf("\"msm\": null, \"direct\": null, \"bullet\": "); print_bullet(bullet_plan(n, nk, 1, have.mult8, dsw::msm_direct_wgs()), nk, 1);
       } else if (direct) { printf("\"msm\": null, \"direct\": "); print_direct(msm_direct_plan(2, n / 2 + 2, have.mult8, dsw::msm_direct_wgs())); printf(", \"bullet\": null"); }
       else print_run_msm(MsmShape{32, MSM_WINDOWS, 2, n + 2, false, false}, have);
+    } else if (!strcmp(entry, "bullet_round_slab")) {   // lasso_bullet_round_slab: always the fused launch (no switch takes it elsewhere), chunked over the rank's local columns
+      if (!have.mult || world < 1 || rows % world) { fprintf(stderr, "%s: lasso_bullet_round_slab refuses this call\n", id); return 2; }
+      printf("\"msm\": null, \"direct\": null, \"bullet\": "); print_bullet(bullet_plan(rows, cols, (uint32_t)world, have.mult8, dsw::msm_direct_wgs()), cols, world);
+    } else if (!strcmp(entry, "msm_dev_slab")) {   // lasso_msm_dev_slab: always run_msm_direct, one row of the rank's n / world columns and the two tail columns
+      if (!have.mult || world < 1 || cols % world) { fprintf(stderr, "%s: lasso_msm_dev_slab refuses this call\n", id); return 2; }
+      printf("\"msm\": null, \"direct\": "); print_direct(msm_direct_plan(1, cols / world + 2, have.mult8, dsw::msm_direct_wgs())); printf(", \"bullet\": null");
     } else { fprintf(stderr, "unknown entry %s\n", entry); return 2; }
     printf("}\n");
   }

@@ -17,6 +17,7 @@ struct Shared {
   int world; std::mutex mu; std::condition_variable cv;
   std::vector<const void*> ptrs; int arrived = 0; long gen = 0; int left = 0; long gen2 = 0;
   size_t calls = 0, bytes = 0;
+  int finished = 0;   // ranks that are through with their proofs (or have failed)
 };
 struct RankCtx { Shared* sh; int rank; };
 int32_t allgather(void* user, const void* send, void* recv, size_t bytes) {
@@ -76,6 +77,12 @@ extern "C" int slab_prove_threads_ex(int world, const lasso_strategy* st, size_t
         if (peak_bytes) peak_bytes[rk] = peak; if (prover_peak_bytes) prover_peak_bytes[rk] = used;
       }
     } while (0);
+    {   // Nobody frees while another rank still proves.  The ranks share ONE device here, and a free waits for the whole device — the other ranks' kernels included, among them a
+        // gate that waits for its own host thread's challenge.  Where the opening has no collective (LASSO_SLAB_OPEN=0: every rank runs it whole, its rounds launched ahead) the
+        // ranks drift apart, and a rank that had finished was seen to stall another one's proof until its gate gave up ("a result was not delivered by the device").
+      std::unique_lock<std::mutex> lk(sh.mu);
+      if (++sh.finished == world) sh.cv.notify_all(); else sh.cv.wait(lk, [&] { return sh.finished == world; });
+    }
     if (d) lasso_host_dense_free(d);
     if (g) lasso_host_gens_free(g);
     if (h) lasso_host_destroy(h);

@@ -44,7 +44,10 @@ Row = namedtuple("Row", "id env entry shape expect")
 # Scalar classes: ("below", maxv) — integers in [0, maxv) with 0 and maxv - 1 present; "cycle4" — the values 0..3 in turn; the full-width ones: "random", "byte_edges" (canonical
 # values built from the signed-BYTE digit edges of msm_recode<8>: bytes 0x7f / 0x80 / 0x81 / 0xff in every window, the all-0x80 and all-0xff carry chains, 0, 1, p - 1, p - 2,
 # 2^252 - 1), "equal" (every scalar of a row the same), "sparse" (97 % zeros).
-Shape = namedtuple("Shape", "rows cols scalars ngens")
+# Slab mode (one proof over `world` ranks, include/lasso_hip.h): bullet_round_slab is rows = n, cols = nk, msm_dev_slab one row of n columns, both over the WHOLE generator vector;
+# ngens is what ONE rank's bases object holds (its n / world generators, then Q and H).  A row runs every rank 0 .. world - 1 in turn, so `rank` stays 0 in the table.  form:
+# bullet_round_slab "fold" (a folding round) or "first" (u == NULL: the inputs are the state); msm_dev_slab runs its three forms (SLAB_MSM_FORMS) in the one row.
+Shape = namedtuple("Shape", "rows cols scalars ngens world rank form", defaults=(1, 0, ""))
 
 
 def _rows(env, entries):
@@ -61,6 +64,17 @@ def _msm3(w8, k1, k33, k301, cap301):
 def _bullet(w8, shapes):
     """lasso_bullet_round as one k_bullet_msm launch: (n, nk, chunks per row, items per chunk at the cap)"""
     return [(f"bullet{n}_{nk}", "bullet_round", (n, nk, "random", n + 2), {"bullet.w8": w8, "bullet.K": k, **({"bullet.ipc": "cap"} if cap else {})}) for n, nk, k, cap in shapes]
+
+
+def _bullet_slab(w8, shapes):
+    """lasso_bullet_round_slab, every rank: (n, nk, world, folding round, wide mapping (nk / 2 >= world), chunks per row, items per chunk at the cap)"""
+    return [(f"slab_bullet{n}_{nk}_w{world}" + ("" if fold else "_first"), "bullet_round_slab", (n, nk, "random", n // world + 2, world, 0, "fold" if fold else "first"),
+             {"bullet.w8": w8, "bullet.wide": wide, "bullet.K": k, **({"bullet.ipc": "cap"} if cap else {})}) for n, nk, world, fold, wide, k, cap in shapes]
+
+
+def _msm_slab(w8, shapes):
+    """lasso_msm_dev_slab, every rank, in its three forms: (n, world, chunks of the row of n / world + 2 columns, items per chunk at the cap)"""
+    return [(f"slab_msm{n}_w{world}", "msm_dev_slab", (1, n, "random", n // world + 2, world), {"direct.w8": w8, "direct.K": k, **({"direct.ipc": "cap"} if cap else {})}) for n, world, k, cap in shapes]
 
 
 FULL8 = {"LASSO_MSM_FULL8": "1"}
@@ -114,6 +128,18 @@ TABLE = (
     # k_msm_pip_*: the 12-bit-window kernels at the fewest rows and columns that reach them, in one group of rows and in several (the last one partly filled)
     + _rows({"LASSO_MSM_PIP_MIN_COLS": "32"}, [("256x40", "hyrax_commit_compressed", (256, 40, "random", NGENS_300), {"kernel": "PIP", "pip_group": 256})])
     + _rows({"LASSO_MSM_PIP_MIN_COLS": "32", "LASSO_MSM_PIP_SCRATCH_MB": "16"}, [("300x33", "hyrax_commit", (300, 33, "byte_edges", NGENS_300), {"kernel": "PIP", "pip_group": 64})])
+    # slab mode of the opening (k_bullet_msm with P > 1, k_msm_direct through sstride / soffset), every rank of each shape.  The narrow mapping (nk / 2 < world: one row of a rank gets
+    # all n / world columns, the other none) with one row of every rank empty, at half = 2 < 4 and at world == n (one generator per rank); the boundary half == world (hl == 1) at 2 and
+    # at 8 ranks; a first round (the inputs are the state); the wide mapping in several chunks, folding and first round; the narrow mapping in several chunks (the empty row's eight
+    # chunk workgroups accumulate nothing); 1024 fold weights, which the two extra workgroups write in two passes of their stride loop
+    + _rows({}, _bullet_slab(True, [(8, 2, 2, True, False, 1, False), (8, 4, 4, True, False, 1, False), (8, 2, 8, True, False, 1, False), (8, 4, 2, True, True, 1, False),
+                                    (8, 8, 2, False, True, 1, False), (64, 16, 8, True, True, 1, False), (256, 128, 2, True, True, 8, False), (256, 128, 4, False, True, 4, False),
+                                    (256, 2, 4, True, False, 8, False), (4096, 4, 8, True, False, 64, False)])
+            + _msm_slab(True, [(2, 2, 1, False), (8, 8, 1, False), (64, 4, 3, False), (296, 8, 5, False), (298, 2, 19, False)]))
+    + _rows({"LASSO_MSM_DIRECT8": "0"}, _bullet_slab(False, [(8, 2, 2, True, False, 1, False), (256, 128, 2, True, True, 16, False)]) + _msm_slab(False, [(296, 8, 10, False)]))
+    + _rows({"LASSO_MSM_DIRECT_WGS": "1"}, _msm_slab(True, [(298, 2, 2, True)]))
+    + _rows({"LASSO_MSM_DIRECT_WGS": "7"}, _bullet_slab(True, [(256, 128, 2, True, True, 2, False), (4096, 2, 4, True, False, 8, True)]))
+    + _rows({"LASSO_MSM_DIRECT_WGS": "4096"}, _bullet_slab(True, [(256, 2, 4, True, False, 8, False)]))
 )
 ENVS = []
 for _r in TABLE:
@@ -165,7 +191,7 @@ def plans(env, calls, curve):
     lines = []
     for cid, entry, shape in calls:
         bps, w = scalar_width(shape.scalars)
-        lines.append(f"{cid} {entry} {shape.rows} {shape.cols} {bps} {w} {shape.ngens}")
+        lines.append(f"{cid} {entry} {shape.rows} {shape.cols} {bps} {w} {shape.ngens} {shape.world}")
     e = {k: v for k, v in os.environ.items() if not k.startswith("LASSO_")}
     e.update(env)
     res = subprocess.run([plan_program(curve)], input="\n".join(lines) + "\n", env=e, capture_output=True, text=True, timeout=60)
@@ -256,11 +282,105 @@ def gens_of(mock_lib, ngens):
     return _GENS[ngens]
 
 
+# ---- slab mode: the two calls (lasso_amd.Device has no method for them: the host prover is their one caller) and the bases object of a rank
+
+def _vp(a):
+    import ctypes as C
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def slab_gens(mock_lib, n, world, rank):
+    """what PolyCommitmentGens::init (lasso_amd/host/prover.hpp) hands lasso_bases_create for a rank of slab mode: G[rank::world][: n / world], then Q, then H"""
+    g = gens_of(mock_lib, n + 2)      # G_0 .. G_{n-1}, Q, H
+    return np.concatenate([g[rank:n:world][: n // world], g[n:n + 2]])
+
+
+def bullet_round_slab(d, bases, n, world, rank, pa, pb, pw, pa2, pb2, pw2, nk, u, ui, blinds):
+    """lasso_bullet_round_slab on Device `d` (u None: a first round) -> the rank's partial L and R, (2, 16)"""
+    import ctypes as C
+    blinds = np.ascontiguousarray(blinds, dtype=np.uint64).reshape(2, 4)
+    u = None if u is None else np.ascontiguousarray(u, dtype=np.uint64); ui = None if u is None else np.ascontiguousarray(ui, dtype=np.uint64)
+    out = np.empty((2, 16), dtype=np.uint64)
+    d._chk(d.lib.lasso_bullet_round_slab(d.ctx, C.c_void_p(bases), n, world, rank, C.c_void_p(pa), C.c_void_p(pb), C.c_void_p(pw), C.c_void_p(pa2), C.c_void_p(pb2), C.c_void_p(pw2), nk,
+                                         _vp(u), _vp(ui), _vp(blinds), _vp(out)))
+    return out
+
+
+def msm_dev_slab(d, bases, p_scalars, n, world, rank, scale, tail):
+    """lasso_msm_dev_slab on Device `d` (scale / tail None: NULL) -> the rank's partial point, (1, 16)"""
+    import ctypes as C
+    scale = None if scale is None else np.ascontiguousarray(scale, dtype=np.uint64); tail = None if tail is None else np.ascontiguousarray(tail, dtype=np.uint64).reshape(2, 4)
+    out = np.empty((1, 16), dtype=np.uint64)
+    d._chk(d.lib.lasso_msm_dev_slab(d.ctx, C.c_void_p(bases), C.c_void_p(p_scalars), n, world, rank, _vp(scale), _vp(tail), _vp(out)))
+    return out
+
+
+# the forms of lasso_msm_dev_slab: (name, scalar class, scale given, tail given).  Without a scale or without a tail the scalars reach the recoder as they are, hence the edge classes
+SLAB_MSM_FORMS = (("full", "random", True, True), ("noscale", "byte_edges", False, True), ("notail", "sparse", True, False))
+
+
+def bullet_inputs(s, fold=True):
+    """the state a bullet-round row starts from: a, b (2 nk entries before a fold, nk in a first round), the fold weights, blinds, u, u^-1"""
+    from gpuutil import rand_fr
+    n, nk = s.rows, s.cols
+    rng = np.random.default_rng([s.rows, s.cols, 77])
+    length = 2 * nk if fold else nk
+    nw = n // length
+    a, bb, w = scalars_of(s, length)[0], rand_fr(rng, length, edge=False), rand_fr(rng, nw, edge=False)
+    blinds = rand_fr(rng, 2, edge=False); u, ui = rand_fr(rng, 2, edge=False)
+    return a, bb, w, blinds, u, ui
+
+
+def _run_slab_row(d, row, mock_lib):
+    """every rank of a slab row on Device `d`, each over a bases object of its own: outputs named `<name>_r<rank>`"""
+    s = row.shape
+    out = {}
+    if row.entry == "bullet_round_slab":
+        n, nk, fold = s.rows, s.cols, s.form == "fold"
+        a, bb, w, blinds, u, ui = bullet_inputs(s, fold)
+        nw = len(w)
+        for rank in range(s.world):
+            b = d.bases_create(slab_gens(mock_lib, n, s.world, rank))
+            pa = d.upload(a); pb = d.upload(bb); pw = d.upload(w)
+            try:
+                if fold:
+                    pa2 = d.alloc(32 * nk); pb2 = d.alloc(32 * nk); pw2 = d.alloc(32 * 2 * nw)
+                    out[f"points_r{rank}"] = bullet_round_slab(d, b, n, s.world, rank, pa, pb, pw, pa2, pb2, pw2, nk, u, ui, blinds)
+                    out.update({f"a_r{rank}": d.download(pa2, (nk, 4)), f"b_r{rank}": d.download(pb2, (nk, 4)), f"w_r{rank}": d.download(pw2, (2 * nw, 4))})
+                    for p in (pa2, pb2, pw2):
+                        d.free(p)
+                else:
+                    out[f"points_r{rank}"] = bullet_round_slab(d, b, n, s.world, rank, pa, pb, pw, 0, 0, 0, nk, None, None, blinds)
+            finally:
+                for p in (pa, pb, pw):
+                    d.free(p)
+                d.bases_destroy(b)
+        return out
+    assert row.entry == "msm_dev_slab"
+    from gpuutil import rand_fr
+    n = s.cols
+    rng = np.random.default_rng([s.rows, s.cols, 77])
+    scale, tail = rand_fr(rng, 1, edge=False), rand_fr(rng, 2, edge=False)
+    ptrs = {name: d.upload(scalars_of(s._replace(scalars=cls))[0]) for name, cls, _, _ in SLAB_MSM_FORMS}
+    for rank in range(s.world):
+        b = d.bases_create(slab_gens(mock_lib, n, s.world, rank))
+        try:
+            for name, _, with_scale, with_tail in SLAB_MSM_FORMS:
+                out[f"points_{name}_r{rank}"] = msm_dev_slab(d, b, ptrs[name], n, s.world, rank, scale if with_scale else None, tail if with_tail else None)
+        finally:
+            d.bases_destroy(b)
+    for p in ptrs.values():
+        d.free(p)
+    return out
+
+
 def run_row(d, row, mock_lib):
-    """the row's call on Device `d` -> {name: array}.  "points": projective points, compared as wire bytes; everything else is compared as it is"""
+    """the row's call on Device `d` -> {name: array}.  "points...": projective points, compared as wire bytes; everything else is compared as it is"""
     import ctypes as C
     from gpuutil import rand_fr
     s = row.shape
+    if row.entry in ("bullet_round_slab", "msm_dev_slab"):
+        return _run_slab_row(d, row, mock_lib)
     b = d.bases_create(gens_of(mock_lib, s.ngens))
     try:
         if row.entry.startswith("hyrax_commit"):
@@ -323,21 +443,24 @@ def reference(mock, row):
             mock.free(p); mock.bases_destroy(b)
             return {"wire": four[scalars_of(s)[1].astype(np.int64)]}
         return {"wire": run_row(mock, row._replace(entry="hyrax_commit_compressed"), mock.lib)["wire"]}
-    out = run_row(mock, row, mock.lib)
-    out["wire"] = np.frombuffer(b"".join(compress_points(mock.lib, out.pop("points"))), dtype=np.uint8).reshape(-1, 32)
-    return out
+    return as_wire(mock.lib, run_row(mock, row, mock.lib))
 
 
 def as_wire(mock_lib, out):
     """a run's outputs in the form `reference` gives"""
     from gpuutil import compress_points
     out = dict(out)
-    if "points" in out:
-        out["wire"] = np.frombuffer(b"".join(compress_points(mock_lib, np.asarray(out.pop("points")).reshape(-1, 16))), dtype=np.uint8).reshape(-1, 32)
+    for name in [k for k in out if k.startswith("points")]:      # "points", and a slab row's "points_r<rank>", "points_<form>_r<rank>"
+        out["wire" + name[len("points"):]] = np.frombuffer(b"".join(compress_points(mock_lib, np.asarray(out.pop(name)).reshape(-1, 16))), dtype=np.uint8).reshape(-1, 32)
     return out
 
 
 DTYPES = {"points": np.uint64, "wire": np.uint8, "a": np.uint64, "b": np.uint64, "w": np.uint64}
+
+
+def dtype_of(name):
+    """the element type of an output: a slab row's names carry a form and a rank behind the plain name"""
+    return DTYPES[name.split("_")[0]]
 
 
 def child_main(index):
@@ -350,7 +473,7 @@ def child_main(index):
     d = Device(0, curve=CURVE)
     for row in rows_of(ENVS[index]):
         for name, arr in run_row(d, row, mock_lib).items():
-            print("ROW", row.id, name, np.ascontiguousarray(arr, dtype=DTYPES[name]).tobytes().hex(), flush=True)
+            print("ROW", row.id, name, np.ascontiguousarray(arr, dtype=dtype_of(name)).tobytes().hex(), flush=True)
     d.close()
     print("DONE", len(rows_of(ENVS[index])))
 

@@ -9,6 +9,7 @@ import pytest
 from fieldref import L as FR_P, limbs, to_mont
 from gpuutil import compress_points, gens, load_mock, rand_fr, small_fr
 from lasso_amd import _abi
+import msmvariants as MV
 from msmvariants import FULL_WIDTH_WIDE_SHAPES, HYRAX_COMMIT_SHAPES, HYRAX_COMMIT_U32_SHAPES
 from roundvariants import CUBIC_EQW2_SHAPES, CUBIC_EQW_ROUND_FUSED_SHAPES, CUBIC_EQW_ROUND_SHAPES, CUBIC_ROUND0_EQ_SHAPES, CUBIC_ROUND_AHEAD_SHAPES, LAYER_AHEAD_SHAPES
 
@@ -1415,6 +1416,214 @@ def test_msm_dev_scaled(devs, gens_300, n):
         return out
     a, b = both(devs, run)
     assert compress_points(devs[1].lib, a) == compress_points(devs[1].lib, b)
+
+
+# ---- slab mode (one proof over `world` ranks by residue class, include/lasso_hip.h): the four entry points of their own, every rank run.  tests/msmvariants.py TABLE holds each
+# rank's partial points to the mock's lasso_bullet_round_slab / lasso_msm_dev_slab, which restate the split the kernel implements; here the split itself is checked: the ranks'
+# results put together again are what the SINGLE-rank call gives, which knows nothing of ranks.
+
+SLAB_BULLET_SHAPES = sorted({(r.shape.rows, r.shape.cols, r.shape.world, r.shape.form == "fold") for r in MV.TABLE if r.entry == "bullet_round_slab" and not r.env})
+SLAB_MSM_SHAPES = sorted({(r.shape.cols, r.shape.world) for r in MV.TABLE if r.entry == "msm_dev_slab" and not r.env})
+_SLAB_REF = {}
+
+
+def sum_points(oracle, wires):
+    """the sum of compressed points, compressed again: the oracle's group law, as test_msm_linearity_large adds.  The oracle's C interface holds points as affine pairs, which the
+    identity of BN254's group does not have: a term whose encoding is the identity's (an empty row of a rank) is left out of the sum on both curves"""
+    from blindutil import IDENTITY
+    from fieldref import CURVE
+    U8 = C.c_uint64 * 8
+    acc = None
+    for wire in wires:
+        if bytes(wire) == IDENTITY[CURVE]:
+            continue
+        x = U8()
+        assert oracle.orc_pt_decompress(bytes(wire), x) == 0
+        if acc is None:
+            acc = x
+        else:
+            o = U8(); oracle.orc_pt_add(acc, x, o); acc = o
+    if acc is None:
+        return IDENTITY[CURVE]
+    buf = (C.c_uint8 * 32)()
+    oracle.orc_pt_compress(acc, buf)
+    return bytes(buf)
+
+
+def _single_rank_round(mock, n, nk, fold):
+    """lasso_bullet_round over the unsplit generators on the mock: (wire bytes of L and R, (a', b', w') of a folding round)"""
+    if (n, nk, fold) not in _SLAB_REF:
+        s = MV.Shape(n, nk, "random", n + 2)
+        a, b, w, blinds, u, ui = MV.bullet_inputs(s, fold)
+        bases = mock.bases_create(MV.gens_of(mock.lib, n + 2))
+        pa = mock.upload(a); pb = mock.upload(b); pw = mock.upload(w); pa2 = mock.alloc(32 * nk); pb2 = mock.alloc(32 * nk); pw2 = mock.alloc(32 * 2 * len(w))
+        if fold:
+            lr = mock.bullet_round(bases, n, pa, pb, pw, pa2, pb2, pw2, nk, u, ui, blinds)
+            state = (mock.download(pa2, (nk, 4)), mock.download(pb2, (nk, 4)), mock.download(pw2, (2 * len(w), 4)))
+        else:
+            lr = mock.bullet_round(bases, n, pa, pb, pw, 0, 0, 0, nk, None, None, blinds)
+            state = ()
+        for p in (pa, pb, pw, pa2, pb2, pw2):
+            mock.free(p)
+        mock.bases_destroy(bases)
+        _SLAB_REF[n, nk, fold] = (compress_points(mock.lib, lr), state)
+    return _SLAB_REF[n, nk, fold]
+
+
+@pytest.mark.parametrize("n,nk,world,fold", SLAB_BULLET_SHAPES)
+def test_bullet_round_slab_recomposes(devs, oracle, n, nk, world, fold):
+    """the ranks' partial L (and R) of lasso_bullet_round_slab add up to the L (R) of lasso_bullet_round over the unsplit generators, and every rank leaves the state a', b', w' of
+    that single-rank round, word for word.  In the narrow mapping (nk / 2 < world) generator j = jl * world + rank sits at position rank mod nk of its weight block, so all of a
+    rank's generators feed ONE row — L where that position is in the upper half, else R — and a rank other than 0 (rank 0 adds c * Q + blind * H to both rows) returns the group's
+    identity for the other one."""
+    from blindutil import IDENTITY
+    from fieldref import CURVE
+    real, mock = devs
+    form = "fold" if fold else "first"
+    got = MV.run_row(real, MV.Row("recompose", {}, "bullet_round_slab", MV.Shape(n, nk, "random", n // world + 2, world, 0, form), {}), mock.lib)
+    want_lr, want_state = _single_rank_round(mock, n, nk, fold)
+    parts = [compress_points(mock.lib, got[f"points_r{rank}"]) for rank in range(world)]
+    for row, name in enumerate("LR"):
+        assert sum_points(oracle, [p[row] for p in parts]) == want_lr[row], f"the {world} partial {name} do not add up to the single-rank {name}"
+    for rank in range(world):
+        for name, want in zip("abw", want_state):
+            assert np.array_equal(got[f"{name}_r{rank}"], want), f"rank {rank}: {name}' differs from the single-rank round's"
+    if nk // 2 < world:
+        for rank in range(1, world):
+            empty = 1 if (rank & (nk - 1)) >= nk // 2 else 0      # all of the rank's generators feed L: R is empty, and the other way round
+            assert parts[rank][empty] == IDENTITY[CURVE], f"rank {rank}: its empty row is not the identity"
+
+
+@pytest.mark.parametrize("n,world", SLAB_MSM_SHAPES)
+def test_msm_dev_slab_recomposes(devs, oracle, n, world):
+    """the ranks' lasso_msm_dev_slab results add up to the mock's lasso_msm_dev_scaled over the unsplit generators (rank 0 alone passes the tail, as the host prover does), with a
+    scale and a tail, with scale == NULL (the scale 1), with tail == NULL (a zero tail), and to lasso_msm_dev where both are NULL"""
+    real, mock = devs
+    rng = np.random.default_rng([n, world, 5])
+    scale, tail = rand_fr(rng, 1, edge=False), rand_fr(rng, 2, edge=False)
+    one, zeros = small_fr([1]), np.zeros((2, 4), dtype=np.uint64)
+    forms = [("random", scale, tail), ("byte_edges", None, tail), ("sparse", scale, None), ("byte_edges", None, None)]
+    sc = {cls: MV.scalars_of(MV.Shape(1, n, cls, n + 2))[0] for cls in ("random", "byte_edges", "sparse")}
+    full = mock.bases_create(MV.gens_of(mock.lib, n + 2))
+    pm = {cls: mock.upload(z) for cls, z in sc.items()}
+    want = [compress_points(mock.lib, mock.msm_dev(full, pm[cls], n) if sc_ is None and tl is None else mock.msm_dev_scaled(full, pm[cls], n, one if sc_ is None else sc_, zeros if tl is None else tl))[0]
+            for cls, sc_, tl in forms]
+    for p in pm.values():
+        mock.free(p)
+    mock.bases_destroy(full)
+    pr = {cls: real.upload(z) for cls, z in sc.items()}
+    parts = [[] for _ in forms]
+    for rank in range(world):
+        b = real.bases_create(MV.slab_gens(mock.lib, n, world, rank))
+        for k, (cls, sc_, tl) in enumerate(forms):
+            parts[k].append(compress_points(mock.lib, MV.msm_dev_slab(real, b, pr[cls], n, world, rank, sc_, tl if rank == 0 else None))[0])
+        real.bases_destroy(b)
+    for p in pr.values():
+        real.free(p)
+    for k, (cls, sc_, tl) in enumerate(forms):
+        assert sum_points(oracle, parts[k]) == want[k], f"scalars {cls}, scale {'given' if sc_ is not None else 'NULL'}, tail {'given' if tl is not None else 'NULL'}"
+
+
+def _fingerprint_mem_slab(d, p_table, p_final, m, world, rank, gamma, tau, p_io, p_fo):
+    g = np.ascontiguousarray(gamma, dtype=np.uint64); t = np.ascontiguousarray(tau, dtype=np.uint64)
+    d._chk(d.lib.lasso_fingerprint_mem_slab(d.ctx, C.c_void_p(p_table), C.c_void_p(p_final), m, world, rank, g.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p),
+                                            C.c_void_p(p_io), C.c_void_p(p_fo)))
+
+
+@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("m", [1, 2, 64, 4100])
+def test_fingerprint_mem_slab(devs, m, world):
+    """init / final fingerprints of a rank's m local entries (local i stands for address i * world + rank of the whole subtable): every rank against the mock, and the ranks'
+    outputs interleaved against the device's own lasso_fingerprint_mem over the whole arrays, which knows nothing of ranks"""
+    rng = np.random.default_rng(m * 16 + world)
+    table = rand_fr(rng, m * world); final = rand_fr(rng, m * world)      # whole arrays; rank r holds final[r::world]
+    gamma, tau = rand_fr(rng, 2, edge=False)
+
+    def run(d):
+        pt = d.upload(table)
+        res = []
+        for rank in range(world):
+            pf = d.upload(final[rank::world]); pio = d.alloc(32 * m); pfo = d.alloc(32 * m)
+            _fingerprint_mem_slab(d, pt, pf, m, world, rank, gamma, tau, pio, pfo)
+            res.append((d.download(pio, (m, 4)), d.download(pfo, (m, 4))))
+            for p in (pf, pio, pfo):
+                d.free(p)
+        pf = d.upload(final); pio = d.alloc(32 * m * world); pfo = d.alloc(32 * m * world)
+        d.fingerprint_mem(pt, pf, m * world, gamma, tau, pio, pfo)
+        whole = (d.download(pio, (m * world, 4)), d.download(pfo, (m * world, 4)))
+        for p in (pt, pf, pio, pfo):
+            d.free(p)
+        return res, whole
+    (ra, wa), (rb, wb) = both(devs, run)
+    for rank in range(world):
+        for k, name in enumerate(("init", "final")):
+            assert np.array_equal(ra[rank][k], rb[rank][k]), f"rank {rank}: {name} fingerprints differ from the mock's"
+            assert np.array_equal(ra[rank][k], wa[k][rank::world]), f"rank {rank}: {name} fingerprints differ from the device's own at addresses i * {world} + {rank}"
+    assert np.array_equal(wa[0], wb[0]) and np.array_equal(wa[1], wb[1])
+
+
+def _densify_dim_slab(d, p_idx, n_lookups, c, dim, s, log_m, world, rank, p_u32, p_dim, p_read, p_fin):
+    d._chk(d.lib.lasso_densify_dim_slab(d.ctx, C.c_void_p(p_idx), n_lookups, c, dim, s, log_m, world, rank, C.c_void_p(p_u32), C.c_void_p(p_dim), C.c_void_p(p_read), C.c_void_p(p_fin)))
+
+
+@pytest.mark.parametrize("mode", ["rand", "same", "sorted"])
+@pytest.mark.parametrize("n_lookups,c,log_m,world", [(2, 1, 1, 2), (5, 2, 4, 2), (8, 1, 3, 8), (1000, 3, 8, 8), (4096, 1, 16, 4), (5000, 2, 12, 2)])
+def test_densify_dim_slab(devs, n_lookups, c, log_m, world, mode):
+    """every rank sorts the whole access sequence and keeps its residue class (global index k -> local k / world, address a -> a / world): all four outputs of every rank and
+    dimension against the mock, and interleaved against the device's own lasso_densify_dim.  s == world and m == world (one entry per rank), a ragged n_lookups whose padded tail
+    counts as address 0, one hot address, sorted addresses"""
+    rng = np.random.default_rng(n_lookups * 31 + c * 7 + log_m + world)
+    m = 1 << log_m
+    s = 1 << max((n_lookups - 1).bit_length(), 0)
+    sl, ml = s // world, m // world
+    if mode == "same":
+        idx = np.full((n_lookups, c), m - 1, dtype=np.uint64)
+    else:
+        idx = rng.integers(0, m, size=(n_lookups, c), dtype=np.uint64)
+        if mode == "sorted":
+            idx = np.sort(idx, axis=0)
+
+    def run(d):
+        p_idx = d.upload(idx)
+        res = []
+        for dim in range(c):
+            per_rank = []
+            for rank in range(world):
+                p_u32 = d.alloc(4 * sl); p_dim = d.alloc(32 * sl); p_read = d.alloc(32 * sl); p_fin = d.alloc(32 * ml)
+                _densify_dim_slab(d, p_idx, n_lookups, c, dim, s, log_m, world, rank, p_u32, p_dim, p_read, p_fin)
+                per_rank.append((d.download(p_u32, (sl,), dtype=np.uint32), d.download(p_dim, (sl, 4)), d.download(p_read, (sl, 4)), d.download(p_fin, (ml, 4))))
+                for p in (p_u32, p_dim, p_read, p_fin):
+                    d.free(p)
+            p_u32 = d.alloc(4 * s); p_dim = d.alloc(32 * s); p_read = d.alloc(32 * s); p_fin = d.alloc(32 * m)
+            d.densify_dim(p_idx, n_lookups, c, dim, s, log_m, p_u32, p_dim, p_read, p_fin)
+            whole = (d.download(p_u32, (s,), dtype=np.uint32), d.download(p_dim, (s, 4)), d.download(p_read, (s, 4)), d.download(p_fin, (m, 4)))
+            for p in (p_u32, p_dim, p_read, p_fin):
+                d.free(p)
+            res.append((per_rank, whole))
+        d.free(p_idx)
+        return res
+    a, b = both(devs, run)
+    names = ("dim_u32", "dim", "read", "final")
+    for dim, ((ranks_a, whole_a), (ranks_b, whole_b)) in enumerate(zip(a, b)):
+        for rank in range(world):
+            for name, x, y, w in zip(names, ranks_a[rank], ranks_b[rank], whole_a):
+                assert np.array_equal(x, y), f"dimension {dim}, rank {rank}: `{name}` differs from the mock's"
+                assert np.array_equal(x, w[rank::world]), f"dimension {dim}, rank {rank}: `{name}` is not the rank's residue class of the device's own lasso_densify_dim"
+        for x, y in zip(whole_a, whole_b):
+            assert np.array_equal(x, y)
+
+
+def test_densify_slab_rejects_out_of_range_on_every_rank(devs):
+    """test_densify_rejects_out_of_range in slab mode: the bad index belongs to one rank's residue class, and every rank refuses the sequence"""
+    d = devs[0]
+    idx = np.array([[3], [16]], dtype=np.uint64)
+    world = 2
+    p_idx = d.upload(idx); p_u32 = d.alloc(4); p_dim = d.alloc(32); p_read = d.alloc(32); p_fin = d.alloc(32 * 16 // world)
+    for rank in range(world):
+        with pytest.raises(Exception):
+            _densify_dim_slab(d, p_idx, 2, 1, 0, 2, 4, world, rank, p_u32, p_dim, p_read, p_fin)
+    for p in (p_idx, p_u32, p_dim, p_read, p_fin):
+        d.free(p)
 
 
 @pytest.mark.parametrize("n,alpha", [(2, 1), (4, 2), (64, 1), (1 << 12, 3), (1 << 15, 8)])

@@ -5,7 +5,9 @@ The runtime switches that select an MSM kernel are read once per process, so tes
 process that runs the setting's rows at the shapes tests/test_msm_reach_cpu.py has shown to reach the kernel: k_msm_rows_full<8> (LASSO_MSM_FULL8=1: signed-byte recoding, LDS
 batches of 128 columns, chunked rows, ragged last batch), k_msm_rows8w with rpw > 1 (LASSO_MSM_ROWS8W_WAVES), k_msm_rows8 at >= 1024 rows (LASSO_MSM_ROWS8W=0), the bucket
 kernel in place of each of them, k_msm_direct / k_bullet_msm over both multiple tables at every chunking LASSO_MSM_DIRECT_WGS gives, the 12-bit-window kernels in one group and
-several, wire bytes by hipMemcpy (more than 2^16 rows) and row sums left on the device.
+several, wire bytes by hipMemcpy (more than 2^16 rows) and row sums left on the device; and slab mode (lasso_bullet_round_slab, lasso_msm_dev_slab: world > 1), every rank of
+each shape, under the default switches, both multiple tables and the chunkings LASSO_MSM_DIRECT_WGS gives (tests/test_gpu_kernels.py holds the ranks' results, put together
+again, to the single-rank calls).
 
 The expected bytes come from the mock Device, once per module: they do not depend on the setting, which is the point.  Runs on the build LASSO_TEST_CURVE selects
 (tests/test_gpu_bn254.py re-runs the module on the BN254 build)."""
@@ -66,7 +68,7 @@ def test_every_row_of_the_setting_gives_the_mocks_bytes(expected, index):
     assert set(got) == {r.id for r in rows}
     bad = []
     for r in rows:
-        out = V.as_wire(mock_lib, {name: np.frombuffer(raw, dtype=V.DTYPES[name]) for name, raw in got[r.id].items()})
+        out = V.as_wire(mock_lib, {name: np.frombuffer(raw, dtype=V.dtype_of(name)) for name, raw in got[r.id].items()})
         assert set(out) == set(want[r.id]), r.id
         for name, w in want[r.id].items():
             g = out[name].reshape(w.shape)

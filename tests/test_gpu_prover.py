@@ -225,7 +225,12 @@ def test_gpu_ab_switches_do_not_change_the_bytes(host, env):
     wait on hundreds of workgroups, the grids on both sides of LASSO_DIRECT_NX and at the cap LASSO_CUBIC_NX sets, the plain loop behind k_eq_outer, EqGlobal behind the gate, the
     pointer tables of more than 8 circuits under each of them, the profiled round launched ahead — run at kernel level in tests/test_gpu_round_variants.py, one child process per
     setting, at the shapes of tests/roundvariants.py; tests/test_round_reach_cpu.py shows on the CPU that each shape reaches its instantiation.
-    Still untested anywhere: LASSO_SLAB_OPEN and LASSO_SLAB_RCCL (slab mode: they need several contexts side by side) and LASSO_THROUGHPUT_AHEAD."""
+    The switches of slab mode need several contexts side by side, and LASSO_THROUGHPUT_AHEAD a host in throughput mode: tests/test_gpu_slab_switches.py runs slab proofs over 2 and 8
+    ranks under LASSO_SLAB_OPEN=0 (with and without LASSO_BULLET_AHEAD=0), LASSO_SLAB_HOST_TAIL=0, LASSO_SLAB_HOST_TOPS=0 and all three at once, slab proofs on the BN254 build,
+    and throughput mode (lasso_host_set_throughput_mode: one host, and four proving at once) with and without LASSO_THROUGHPUT_AHEAD=1, one child process per setting, against the
+    oracle's bytes.  Out of reach on one device: LASSO_SLAB_AHEAD (ranks_share_a_device() switches it off; held over the mock, in tests/test_slab_sharding_cpu.py) and
+    LASSO_SLAB_RCCL (RCCL declines ranks that share a device, tests/test_gpu_kernels.py test_rccl_two_ranks_on_one_device, so the exchange takes the shared-memory route
+    whatever the switch says; the mock has no RCCL, so no test holds the RCCL route of lasso_host_set_comm_shm)."""
     import hashlib, os, subprocess, sys
     env, inst = env if isinstance(env, tuple) else (env, "and")
     kind, c, log_m, log_s = _SWITCH_INSTANCES[inst]

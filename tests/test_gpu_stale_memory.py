@@ -6,7 +6,7 @@ reads what its own call did not store fails them.  tests/test_gpu_write_contract
 
 One child pytest per group, smallest shapes only, each with its own time limit; a child that does not finish in it, or is ended by a signal, is the last one started (the
 groups after it fail at once), and nothing is retried.  Runs on the build LASSO_TEST_CURVE selects: tests/test_gpu_bn254.py re-runs the module on the BN254 build, where the
-groups are the BN254 proofs and the verifier and set-up modules (the slab, soak and switch tests of tests/test_gpu_prover.py exist for the curve25519 build only).
+groups are the BN254 proofs and the verifier and set-up modules (the slab, soak and switch tests of tests/test_gpu_prover.py exist for the curve25519 build only; slab proofs on the BN254 build are in tests/test_gpu_slab_switches.py).
 
   proofs     tests/test_gpu_prover.py: test_gpu_proof_bit_exact_vs_oracle (all CASES), test_gpu_cubic_batched_scripted_eq_points, test_gpu_soak_alternating_shapes_on_one_prover
              (240 proofs of four shapes on one prover: the pool and the scratch as another shape left them)

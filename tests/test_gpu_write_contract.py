@@ -13,10 +13,10 @@ the call did not store then computes with the word instead of with zeros or with
 is asserted for it.  The last two sensitivity cases read fresh lasso_alloc memory back and require the word everywhere, the second after the scratch has grown beyond its floor
 with live data and been trimmed, twice.
 
-Measured on an MI355X with both switches on: 816 cases in 22 children, 131 to 134 s for the module on the curve25519 build and 116 to 122 s on the BN254 build (131 s before the fill
-was added: the memsets do not show); the longest child is the curve group (73 cases, 38 s / 33 s: the commitments' reference runs on the mock), then LASSO_REDUCE_NX=3 (77 rows,
-19 s) and the round group (120 cases, 14 s); every other child takes 2 to 9 s.  Cases per group: sensitivity 13, kernels 184 + 73 + 120, field edges 66 + 77, operands 65, MSM
-over caller points 22, wire points 8, candidates 8, table rows 60 / 5 / 8 / 4 / 77 / 8 / 7 / 1 / 1 / 9 in the order of SETTINGS.  No stray write, no damaged guard and no
+Measured on an MI355X with both switches on: 873 cases in 22 children, 130 s for the module on the curve25519 build and 124 s on the BN254 build (131 s before the fill was
+added: the memsets do not show); the longest child is the curve group (88 cases, 40 s: the commitments' reference runs on the mock), then the round group (120 cases, 14 s) and
+LASSO_REDUCE_NX=3 (77 rows, 12 s); every other child takes 2 to 9 s.  Cases per group: sensitivity 13, kernels 211 + 88 + 120, field edges 66 + 77, operands 65, MSM over caller
+points 22, wire points 8, candidates 8, table rows 75 / 5 / 8 / 4 / 77 / 8 / 7 / 1 / 1 / 9 in the order of SETTINGS.  No stray write, no damaged guard and no
 stale read was found on either build."""
 import os
 import re

@@ -7,7 +7,10 @@ per switch setting as a child process with that environment, for both curve buil
   2. the union of the table's plans holds every MsmKernel and MsmResult enumerator and every loop shape of the kernels behind them: k_msm_rows8w with one row per wave and with
      several (rpw > 1, the last wave partly filled); k_msm_rows8 with one and two byte windows, one chunk and several, and at >= 1024 rows; k_msm_rows_full<8> with one chunk per row and
      several, a chunk of more than 128 columns (MSM_FULL8_COLS: more than one LDS batch) and a ragged last batch; k_msm_buckets on 4- and 32-byte scalars, each chunked;
-     k_msm_pip_* with one group of rows and several; k_msm_direct and k_bullet_msm over both multiple tables, each with one chunk, several, and items per chunk at the cap.
+     k_msm_pip_* with one group of rows and several; k_msm_direct and k_bullet_msm over both multiple tables, each with one chunk, several, and items per chunk at the cap;
+     slab mode (lasso_bullet_round_slab, lasso_msm_dev_slab: world > 1, every rank run by the row): both mappings of k_bullet_msm's columns (wide, half >= world, and narrow), the
+     boundary half == world, one chunk and several in each mapping, both tables, a first round, world == n, more fold weights than one pass of the extra workgroups' loop
+     writes; k_msm_direct behind a scalar stride with one chunk and several, both tables, items per chunk at the cap.
 
 And the shapes of test_hyrax_commit, test_hyrax_commit_u32 and test_hyrax_commit_full_width_wide_windows (tests/test_gpu_kernels.py, default switches) go through the same program:
 the kernel the comments beside them name is the kernel planned.  Move MSM_SMALL_ROWS, the 1024-row bound of k_msm_rows8w or a chunking rule, and the row that lost its kernel fails
@@ -83,6 +86,26 @@ def test_the_table_reaches_every_kernel_result_path_and_loop_shape(planned):
             need(f"{kernel} over the {tab} table, K == 1", any(p["K"] == 1 for p in ps))
             need(f"{kernel} over the {tab} table, K > 1", any(p["K"] > 1 for p in ps))
             need(f"{kernel} over the {tab} table, items per chunk at the cap", any(p["ipc"] == p["ipc_cap"] for p in ps))
+    # slab mode: the rows of lasso_bullet_round_slab and lasso_msm_dev_slab (world > 1)
+    slab = [(r, planned[r.id]["bullet"]) for r in V.TABLE if r.entry == "bullet_round_slab"]
+    assert all(r.shape.world > 1 and p["world"] == r.shape.world and p["n_loc"] * p["world"] == r.shape.rows for r, p in slab)
+    for wide in (True, False):
+        name = "wide" if wide else "narrow"
+        ps = [p for _, p in slab if p["wide"] == wide]
+        need(f"k_bullet_msm in slab mode, {name} mapping, K == 1", any(p["K"] == 1 for p in ps))
+        need(f"k_bullet_msm in slab mode, {name} mapping, K > 1", any(p["K"] > 1 for p in ps))
+    need("k_bullet_msm in slab mode at the boundary half == world (one local column per weight block)", any(p["half"] == p["world"] for _, p in slab))
+    need("k_bullet_msm in slab mode, narrow mapping one round below the boundary (1 < half < world)", any(1 < p["half"] < p["world"] for _, p in slab))
+    need("k_bullet_msm in slab mode with world == n", any(p["n_loc"] == 1 for _, p in slab))
+    need("k_bullet_msm in slab mode over both tables", {p["w8"] for _, p in slab} == {True, False})
+    need("k_bullet_msm in slab mode, a first round in each of one chunk and several", {p["K"] > 1 for r, p in slab if r.shape.form == "first"} == {True, False})
+    need("k_bullet_msm in slab mode, items per chunk at the cap", any(p["ipc"] == p["ipc_cap"] for _, p in slab))
+    need("k_bullet_msm in slab mode, more fold weights than the 512 one pass of the two extra workgroups writes", any(r.shape.form == "fold" and p["weights"] > 512 for r, p in slab))
+    sm = [(r, planned[r.id]["direct"]) for r in V.TABLE if r.entry == "msm_dev_slab"]
+    need("lasso_msm_dev_slab with one chunk and several", {p["K"] > 1 for _, p in sm} == {True, False})
+    need("lasso_msm_dev_slab over both tables", {p["w8"] for _, p in sm} == {True, False})
+    need("lasso_msm_dev_slab with items per chunk at the cap", any(p["ipc"] == p["ipc_cap"] for _, p in sm))
+    need("lasso_msm_dev_slab with world == n and with an odd number of local columns", any(r.shape.world == r.shape.cols for r, _ in sm) and any(r.shape.cols // r.shape.world % 2 for r, _ in sm))
     assert not missing, "no row of tests/msmvariants.py TABLE reaches: " + "; ".join(missing)
 
 

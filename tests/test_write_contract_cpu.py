@@ -3,7 +3,7 @@ oracle's mock, whose device memory is host memory: every re-collected case passe
 contract of the sensitivity cases is reported with the right owner.
 
 The mock is a serial CPU statement of every call, so the cases are limited to parameters of at most MAX_PARAM (2^11): larger shapes run on the device only
-(tests/test_gpu_write_contract.py).  Measured: 312 cases (118 above the limit deselected) in 17 to 42 s, depending on the host's cores."""
+(tests/test_gpu_write_contract.py).  Measured: 359 cases (128 above the limit deselected) in 17 to 42 s, depending on the host's cores."""
 import os
 import time
 
