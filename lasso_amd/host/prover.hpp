@@ -652,6 +652,24 @@ inline ScVec eq_evals_host(const Sc* r, size_t ell) {
   for (size_t j = 0; j < ell; j++) { size *= 2; for (size_t i = size; i-- > 0;) { if (!(i & 1)) continue; Sc sc = ev[i / 2]; ev[i] = sc * r[j]; ev[i - 1] = sc - ev[i]; } }
   return ev;
 }
+// for i in (0..challenges.len()).rev() { poly.bound_poly_var_bot(&challenges[i]) }  (dense_mlpoly.rs:218-225)
+inline Sc bound_bot_all(ScVec z, const ScVec& ch) {
+  for (size_t i = ch.size(); i-- > 0;) { const size_t n = z.size() / 2; for (size_t k = 0; k < n; k++) z[k] = z[2 * k] + ch[i] * (z[2 * k + 1] - z[2 * k]); z.resize(n); }
+  LASSO_REQUIRE(z.size() == 1); return z[0];
+}
+// The n-to-1 reduction of claimed evaluations, prover and verifier alike (CombinedTableEvalProof subtables/mod.rs:285-375, HashLayerProof memory_checking.rs:370-449):
+// the evaluations are absorbed (padded to a power of two first, or as they are: DensePolynomial::new_padded pads them afterwards, :420), ceil_log2 challenges are
+// drawn, the padded vector is folded to the joint claim, which is absorbed.  The opening that follows is at ch || r.
+struct JointClaim { ScVec ch; Sc joint; };
+inline JointClaim joint_claim(ProofTranscript& t, const char* evals_label, const char* challenge_label, const char* joint_label, ScVec evals, bool pad_before_append) {
+  if (pad_before_append) evals.resize(next_pow2(evals.size()), Sc::zero());
+  t.append_scalars(evals_label, evals);
+  JointClaim c; c.ch = t.challenge_vector(challenge_label, ceil_log2(evals.size()));
+  evals.resize(next_pow2(evals.size()), Sc::zero());
+  c.joint = bound_bot_all(std::move(evals), c.ch);
+  t.append_scalar(joint_label, c.joint);
+  return c;
+}
 
 // init * EqPolynomial(r[0..ell)).evals() as plain 4 x u64 values: the running factor rides on the root instead of costing a product per entry afterwards
 inline std::vector<H4> eq_evals_host_scaled(const Sc* r, size_t ell, const Sc& init) {
@@ -1665,40 +1683,73 @@ class Prover {
     P.z2 = a_hat * (c * blind_fin + r_beta) + r_delta;
     return P;
   }
-  // ---- PolyEvalProof::prove (dense_mlpoly.rs:302-359); blinds None unless named
-  // One GPU, the whole polynomial resident: everything stays on the device — the two halves of the eq table (eq_poly.rs:44-52), L*Z (dense_mlpoly.rs:184-207); only
-  // serialize(R) comes back.  Static for the reason dot_product_log_prove is.  matvec_u64 != null: d_poly holds 64-bit integers, Z[i] = F::from(d_poly[i]), and L*Z reads
-  // them as they are (include/lasso_hip_poly.h lasso_matvec_left_u64_dev).  Zr == null: the evaluation is not known yet — it is <L*Z, R>, taken from the vector just
-  // computed (2^right products on the host); *Zr_out receives what the proof is about either way.  blinds (2^left row blinds of the commitment) / blind_Zr, each null
-  // = None: LZ_blind = <L, blinds> on the host (:325-344); C_Zr_out receives Zr * G_1 + blind_Zr * h in wire form, the C_Zr' of :358.
+  // ---- PolyEvalProof::prove (dense_mlpoly.rs:302-359) on one GPU with the polynomial resident, written once; blinds None unless named.  The polynomial is k blocks
+  // of 2^(left - kappa) whole rows each, kappa = ceil_log2(k), read where they lie (a merged polynomial's parts, a caller's vectors: DensePolynomial::merge
+  // dense_mlpoly.rs:251-261 never made, or the one block that is the whole polynomial), and the point is ch || r: kappa challenges, then r.  The L*Z of
+  // dense_mlpoly.rs:184-207 factors through ch:
+  //   L = eq(ch) (x) eq(r[0 .. left - kappa))   =>   L*Z = sum_b eq(ch)[b] * M_b,   M_b = eq(r[0 .. left - kappa)) * Z_b,
+  // so block_pass — the two eq tables (eq_poly.rs:44-52) and one mat-vec per block into M — depends on r alone and can run before ch exists, on either context;
+  // open_combine weights the M_b with eq(ch) (kappa = 0: M is L*Z) and ends in dot_product_log_prove.  Everything stays on the device, only serialize(R) comes back.
+  // A block marked u64 holds 64-bit integers, Z[i] = F::from(block[i]), read as they are through matvec_u64 (include/lasso_hip_poly.h lasso_matvec_left_u64_dev).
   typedef int32_t (*MatvecU64)(lasso_ctx*, const uint64_t*, const lasso_fr*, size_t, size_t, lasso_fr*);
+  struct PolyBlock { const void* d; bool u64; };
+  struct BlockPass { DBuf M, R, Lp; ScVec r_left; size_t blocks = 0, kappa = 0, right = 0; bool ready = false; };   // r_left: r[0 .. left - kappa), the point's share of the row index
+  static BlockPass block_pass(const Dev& d, lasso_ctx* c, void (Dev::*chk)(int32_t, const char*) const, const std::vector<PolyBlock>& blocks, MatvecU64 matvec_u64, size_t nv, const ScVec& r) {
+    BlockPass bp; bp.blocks = blocks.size(); bp.kappa = ceil_log2(bp.blocks);
+    const size_t left = (nv + bp.kappa) / 2; bp.right = nv + bp.kappa - left;
+    LASSO_REQUIRE(bp.blocks >= 1 && r.size() == nv && left >= bp.kappa);   // left >= kappa: no row of the matrix spans two blocks
+    bp.r_left.assign(r.begin(), r.begin() + (left - bp.kappa));
+    const size_t lrows = (size_t)1 << (left - bp.kappa), Rn = (size_t)1 << bp.right;
+    bp.M = DBuf(d, bp.blocks * Rn); bp.R = DBuf(d, Rn); bp.Lp = DBuf(d, lrows);
+    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i + bp.kappa < left; i++) rl.push_back(r[i].abi()); for (size_t i = left - bp.kappa; i < nv; i++) rr.push_back(r[i].abi());
+    (d.*chk)(lasso_eq_evals(c, rl.data(), (uint32_t)rl.size(), bp.Lp.p), "lasso_eq_evals");
+    (d.*chk)(lasso_eq_evals(c, rr.data(), (uint32_t)rr.size(), bp.R.p), "lasso_eq_evals");
+    for (size_t b = 0; b < bp.blocks; b++) {
+      LASSO_REQUIRE(blocks[b].d && (!blocks[b].u64 || matvec_u64));
+      if (blocks[b].u64) (d.*chk)(matvec_u64(c, (const uint64_t*)blocks[b].d, bp.Lp.p, lrows, Rn, bp.M.p + b * Rn), "lasso_matvec_left_u64_dev");
+      else (d.*chk)(lasso_matvec_left_dev(c, (const lasso_fr*)blocks[b].d, bp.Lp.p, lrows, Rn, bp.M.p + b * Rn), "lasso_matvec_left_dev");
+    }
+    bp.ready = true; return bp;
+  }
+  // evals[b] = <M_b, R>, block b's evaluation at r: M comes back and the products are the host's (blocks * 2^right).  Only for callers that do not know them yet
+  static ScVec block_evals(const Dev& d, const BlockPass& bp, const ScVec& r) {
+    const size_t Rn = (size_t)1 << bp.right;
+    std::vector<lasso_fr> m(bp.blocks * Rn); d.chk(lasso_download(d.ctx, m.data(), bp.M.p, m.size() * sizeof(lasso_fr)), "lasso_download");
+    const ScVec R = eq_evals_host(r.data() + (r.size() - bp.right), bp.right);
+    ScVec evals;
+    for (size_t b = 0; b < bp.blocks; b++) { Sc y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(m[b * Rn + i]) * R[i]; evals.push_back(y); }
+    return evals;
+  }
+  // From M and ch to the proof about y = the polynomial at ch || r.  blinds (the 2^left row blinds of the commitment, zero blocks included) / blind_Zr, each null = None:
+  // LZ_blind = <eq(ch || r_left), blinds> on the host (:325-344); C_Zr_out receives y * G_1 + blind_Zr * h in wire form, the C_Zr' of :358
+  static DotProductProofLog open_combine(const Dev& d, ProofTranscript& t, RandomTape& tape, BlockPass& bp, const ScVec& ch, const Sc& y, const PolyCommitmentGens& g,
+                                         const ScVec* blinds = nullptr, const Sc* blind_Zr = nullptr, uint8_t* C_Zr_out = nullptr) {
+    LASSO_REQUIRE(bp.ready && ch.size() == bp.kappa);
+    const size_t Rn = (size_t)1 << bp.right;
+    DBuf d_LZ;
+    if (bp.kappa == 0) d_LZ = std::move(bp.M);
+    else {   // the zero blocks behind bp.blocks contribute nothing
+      DBuf w(d, (size_t)1 << bp.kappa); d_LZ = DBuf(d, Rn);
+      std::vector<lasso_fr> cc; for (auto& x : ch) cc.push_back(x.abi());
+      d.chk(lasso_eq_evals(d.ctx, cc.data(), (uint32_t)cc.size(), w.p), "lasso_eq_evals");
+      d.chk(lasso_matvec_left_dev(d.ctx, bp.M.p, w.p, bp.blocks, Rn, d_LZ.p), "lasso_matvec_left_dev");
+    }
+    std::vector<uint8_t> a_bytes(32 * Rn);
+    d.chk(lasso_fr_to_bytes(d.ctx, bp.R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
+    Sc LZ_blind;
+    if (blinds) { ScVec pt = ch; pt.insert(pt.end(), bp.r_left.begin(), bp.r_left.end()); LZ_blind = left_blind(*blinds, pt.data(), pt.size()); }
+    return dot_product_log_prove(d, t, tape, g, d_LZ, bp.R, a_bytes, y, blinds ? &LZ_blind : nullptr, blind_Zr, C_Zr_out);
+  }
+  // One polynomial, no challenges.  Zr == null: the evaluation is not known yet — it is block_evals'; *Zr_out receives what the proof is about either way
   static DotProductProofLog poly_eval_prove_resident(const Dev& d, ProofTranscript& t, RandomTape& tape, const void* d_poly, MatvecU64 matvec_u64, size_t num_vars, const ScVec& r, const Sc* Zr, Sc* Zr_out,
                                                      const PolyCommitmentGens& g, const ScVec* blinds = nullptr, const Sc* blind_Zr = nullptr, uint8_t* C_Zr_out = nullptr) {
     Trace tr("DensePolyEval.prove", d.ctx);
     t.append_protocol_name("polynomial evaluation proof");
     LASSO_REQUIRE(r.size() == num_vars && d_poly);
-    size_t left = num_vars / 2, right = num_vars - left;
-    const size_t Ln = (size_t)1 << left, Rn = (size_t)1 << right;
-    DBuf d_LZ(d, Rn), d_R(d, Rn);
-    std::vector<uint8_t> a_bytes(32 * Rn);
-    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i < left; i++) rl.push_back(r[i].abi()); for (size_t i = left; i < num_vars; i++) rr.push_back(r[i].abi());
-    DBuf d_L(d, Ln);
-    d.chk(lasso_eq_evals(d.ctx, rl.data(), (uint32_t)left, d_L.p), "lasso_eq_evals");
-    d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)right, d_R.p), "lasso_eq_evals");
-    if (matvec_u64) d.chk(matvec_u64(d.ctx, (const uint64_t*)d_poly, d_L.p, Ln, Rn, d_LZ.p), "lasso_matvec_left_u64_dev");
-    else d.chk(lasso_matvec_left_dev(d.ctx, (const lasso_fr*)d_poly, d_L.p, Ln, Rn, d_LZ.p), "lasso_matvec_left_dev");
-    d.chk(lasso_fr_to_bytes(d.ctx, d_R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    Sc y;
-    if (Zr) y = *Zr;
-    else {
-      std::vector<lasso_fr> lz(Rn); d.chk(lasso_download(d.ctx, lz.data(), d_LZ.p, Rn * sizeof(lasso_fr)), "lasso_download");
-      const ScVec R = eq_evals_host(r.data() + left, right);
-      y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(lz[i]) * R[i];
-    }
+    BlockPass bp = block_pass(d, d.ctx, &Dev::chk, {{d_poly, matvec_u64 != nullptr}}, matvec_u64, num_vars, r);
+    const Sc y = Zr ? *Zr : block_evals(d, bp, r)[0];
     if (Zr_out) *Zr_out = y;
-    Sc LZ_blind;
-    if (blinds) LZ_blind = left_blind(*blinds, r.data(), left);
-    return dot_product_log_prove(d, t, tape, g, d_LZ, d_R, a_bytes, y, blinds ? &LZ_blind : nullptr, blind_Zr, C_Zr_out);
+    return open_combine(d, t, tape, bp, ScVec(), y, g, blinds, blind_Zr, C_Zr_out);
   }
   // <EqPolynomial(point[0 .. left)).evals(), blinds>: the blind of L * Z under row blinds (dense_mlpoly.rs:330-333)
   static Sc left_blind(const ScVec& blinds, const Sc* point, size_t left) {
@@ -1707,60 +1758,13 @@ class Prover {
     Sc acc = Sc::zero(); for (size_t i = 0; i < L.size(); i++) acc += L[i] * blinds[i];
     return acc;
   }
-  // ---- CombinedTableEvalProof::prove (subtables/mod.rs:285-313) of DensePolynomial::merge (dense_mlpoly.rs:251-261) of a caller's k vectors of 2^nv values each, the
-  // merge never made: vector b is block b of the merged matrix (2^(left - kappa) whole rows, kappa = log2 next_pow2(k)), so prep_open's factorisation below applies with
-  // the blocks read where they lie, each in its own form (a 64-bit block through matvec_u64).  polys_pass is everything that depends on r alone: the M_b, the right-half
-  // table and evals[b] = <M_b, R> (k * 2^right products on the host); polys_eval_prove draws the challenges afterwards and ends where every opening does.
-  struct PolyBlock { const void* d; bool u64; };
-  struct PolysPass { DBuf M, R; ScVec evals, r_left; size_t kappa = 0, right = 0; };   // r_left: r[0 .. left - kappa), the point's share of the row index
-  static PolysPass polys_pass(const Dev& d, const std::vector<PolyBlock>& blocks, MatvecU64 matvec_u64, size_t nv, const ScVec& r) {
-    PolysPass ps; const size_t k = blocks.size();
-    ps.kappa = ceil_log2(k);
-    const size_t left = (nv + ps.kappa) / 2; ps.right = nv + ps.kappa - left;
-    LASSO_REQUIRE(k >= 1 && r.size() == nv && left >= ps.kappa);   // left >= kappa: no row of the merged matrix spans two vectors
-    ps.r_left.assign(r.begin(), r.begin() + (left - ps.kappa));
-    const size_t lrows = (size_t)1 << (left - ps.kappa), Rn = (size_t)1 << ps.right;
-    ps.M = DBuf(d, k * Rn); ps.R = DBuf(d, Rn);
-    DBuf Lp(d, lrows);
-    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i + ps.kappa < left; i++) rl.push_back(r[i].abi()); for (size_t i = left - ps.kappa; i < nv; i++) rr.push_back(r[i].abi());
-    d.chk(lasso_eq_evals(d.ctx, rl.data(), (uint32_t)rl.size(), Lp.p), "lasso_eq_evals");
-    d.chk(lasso_eq_evals(d.ctx, rr.data(), (uint32_t)rr.size(), ps.R.p), "lasso_eq_evals");
-    for (size_t b = 0; b < k; b++) {
-      LASSO_REQUIRE(blocks[b].d && (!blocks[b].u64 || matvec_u64));
-      if (blocks[b].u64) d.chk(matvec_u64(d.ctx, (const uint64_t*)blocks[b].d, Lp.p, lrows, Rn, ps.M.p + b * Rn), "lasso_matvec_left_u64_dev");
-      else d.chk(lasso_matvec_left_dev(d.ctx, (const lasso_fr*)blocks[b].d, Lp.p, lrows, Rn, ps.M.p + b * Rn), "lasso_matvec_left_dev");
-    }
-    std::vector<lasso_fr> m(k * Rn); d.chk(lasso_download(d.ctx, m.data(), ps.M.p, k * Rn * sizeof(lasso_fr)), "lasso_download");
-    const ScVec R = eq_evals_host(r.data() + (left - ps.kappa), ps.right);
-    for (size_t b = 0; b < k; b++) { Sc y = Sc::zero(); for (size_t i = 0; i < Rn; i++) y += Sc::from_abi(m[b * Rn + i]) * R[i]; ps.evals.push_back(y); }
-    return ps;
-  }
-  // blinds (null = None): the 2^left row blinds of the merged commitment, zero blocks included; the left half of ch || r is eq(ch) (x) eq(r[0 .. left - kappa))
-  static DotProductProofLog polys_eval_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, PolysPass& ps, const PolyCommitmentGens& g, const ScVec* blinds = nullptr) {
-    const size_t k = ps.evals.size(), K = (size_t)1 << ps.kappa, Rn = (size_t)1 << ps.right;
+  // ---- CombinedTableEvalProof::prove (subtables/mod.rs:285-313) of the merge of a caller's k vectors, over the block pass of those vectors at r and their evaluations there
+  static DotProductProofLog polys_eval_prove(const Dev& d, ProofTranscript& t, RandomTape& tape, BlockPass& bp, const ScVec& evals, const PolyCommitmentGens& g, const ScVec* blinds = nullptr) {
     t.append_protocol_name("Lasso CombinedTableEvalProof");
-    ScVec evals = ps.evals; evals.resize(K, Sc::zero());
-    t.append_scalars("evals_ops_val", evals);
-    const ScVec ch = t.challenge_vector("challenge_combine_n_to_one", ps.kappa);
-    size_t len = K;
-    for (size_t i = ch.size(); i-- > 0;) { len /= 2; for (size_t j = 0; j < len; j++) evals[j] = evals[2 * j] + ch[i] * (evals[2 * j + 1] - evals[2 * j]); }   // bound_poly_var_bot
-    const Sc joint = evals[0];
-    t.append_scalar("joint_claim_eval", joint);
+    const JointClaim jc = joint_claim(t, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", evals, true);
     Trace tr("DensePolyEval.prove", d.ctx);
-    t.append_protocol_name("polynomial evaluation proof");   // PolyEvalProof::prove at ch || r: L * Z = sum_b eq(ch)[b] * M_b, the zero blocks behind k contribute nothing
-    DBuf d_LZ;
-    if (ps.kappa == 0) d_LZ = std::move(ps.M);
-    else {
-      DBuf w(d, K); d_LZ = DBuf(d, Rn);
-      std::vector<lasso_fr> cc; for (auto& c : ch) cc.push_back(c.abi());
-      d.chk(lasso_eq_evals(d.ctx, cc.data(), (uint32_t)cc.size(), w.p), "lasso_eq_evals");
-      d.chk(lasso_matvec_left_dev(d.ctx, ps.M.p, w.p, k, Rn, d_LZ.p), "lasso_matvec_left_dev");
-    }
-    std::vector<uint8_t> a_bytes(32 * Rn);
-    d.chk(lasso_fr_to_bytes(d.ctx, ps.R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    Sc LZ_blind;
-    if (blinds) { ScVec pt = ch; pt.insert(pt.end(), ps.r_left.begin(), ps.r_left.end()); LZ_blind = left_blind(*blinds, pt.data(), pt.size()); }
-    return dot_product_log_prove(d, t, tape, g, d_LZ, ps.R, a_bytes, joint, blinds ? &LZ_blind : nullptr);
+    t.append_protocol_name("polynomial evaluation proof");
+    return open_combine(d, t, tape, bp, jc.ch, jc.joint, g, blinds);
   }
   DotProductProofLog poly_eval_prove(const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const Sc& Zr, const PolyCommitmentGens& g) {
     if (this->P == 1 && d_poly) return poly_eval_prove_resident(d, t, tape, d_poly, nullptr, num_vars, r, &Zr, nullptr, g);
@@ -1811,62 +1815,31 @@ class Prover {
     }
     return dot_product_log_prove(g, d_LZ, d_R, a_bytes, Zr);
   }
-  // ---- openings prepared ahead of the transcript.  joint_open's point is (ch, r): k challenges ch drawn when the opening starts, r known earlier
-  // (the grand-product argument's random point).  The L*Z of PolyEvalProof::prove (dense_mlpoly.rs:184-207, :336-340) factors through ch:
-  //   L = eq(ch) (x) eq(r[0 .. left-k))   =>   L*Z = sum_b eq(ch)[b] * M_b,   M_b = eq(r[0 .. left-k)) * Z_b   (Z_b = block b of 2^(left-k) rows),
-  // so the pass over the whole polynomial (the M_b) and the right-half table depend on r only.  They are computed on the side context (own
-  // stream) while the main context sits in a latency-bound phase — the second grand-product argument, or the previous opening's bullet rounds —
-  // and at opening time a 2^k-row mat-vec combines them.
-  struct OpenPrep { DBuf M, R; size_t k = 0, left = 0, right = 0; bool ready = false; };
-  OpenPrep prep_open(const lasso_fr* d_poly, size_t k, const ScVec& r) {
-    OpenPrep pr; const size_t nv = k + r.size();
-    pr.k = k; pr.left = nv / 2; pr.right = nv - pr.left;
-    if (P != 1 || pr.left < k || !sw::side_stream()) return pr;
-    lasso_ctx* sc = d.side();
-    const size_t lrows = (size_t)1 << (pr.left - k), Rn = (size_t)1 << pr.right, nb = (size_t)1 << k;
-    pr.M = DBuf(d, nb * Rn); pr.R = DBuf(d, Rn);
-    DBuf Lp(d, lrows);
-    std::vector<lasso_fr> rl, rr; for (size_t i = 0; i + k < pr.left; i++) rl.push_back(r[i].abi()); for (size_t i = pr.left - k; i < r.size(); i++) rr.push_back(r[i].abi());
-    d.chk_side(lasso_eq_evals(sc, rl.data(), (uint32_t)rl.size(), Lp.p), "lasso_eq_evals");
-    d.chk_side(lasso_eq_evals(sc, rr.data(), (uint32_t)rr.size(), pr.R.p), "lasso_eq_evals");
-    for (size_t b = 0; b < nb; b++) d.chk_side(lasso_matvec_left_dev(sc, d_poly + b * lrows * Rn, Lp.p, lrows, Rn, pr.M.p + b * Rn), "lasso_matvec_left_dev");
-    side_keep.push_back(std::move(Lp));
-    pr.ready = true; return pr;
+  // ---- openings prepared ahead of the transcript.  joint_open's point is (ch, r): k challenges ch drawn when the opening starts, r known earlier (the grand-product
+  // argument's random point).  The block pass over the polynomial's 2^k blocks runs on the side context (own stream) while the main context sits in a latency-bound
+  // phase — the second grand-product argument, or the previous opening's bullet rounds — and at opening time open_combine's 2^k-row mat-vec combines them.
+  BlockPass prep_open(const lasso_fr* d_poly, size_t k, const ScVec& r) {
+    if (P != 1 || (k + r.size()) / 2 < k || !sw::side_stream()) return BlockPass();
+    std::vector<PolyBlock> blocks;
+    for (size_t b = 0; b < ((size_t)1 << k); b++) blocks.push_back({d_poly + (b << r.size()), false});   // block b: 2^(left - k) rows of 2^right values
+    BlockPass bp = block_pass(d, d.side(), &Dev::chk_side, blocks, nullptr, r.size(), r);
+    side_keep.push_back(std::move(bp.Lp));
+    return bp;
   }
-  void side_sync() { if (!side_keep.empty() || true) { d.chk_side(lasso_sync(d.side()), "lasso_sync"); side_keep.clear(); } }
-  DotProductProofLog poly_eval_prove_prepped(OpenPrep& pr, const ScVec& ch, const Sc& Zr, const PolyCommitmentGens& g) {
+  void side_sync() { d.chk_side(lasso_sync(d.side()), "lasso_sync"); side_keep.clear(); }
+  DotProductProofLog poly_eval_prove_prepped(BlockPass& bp, const ScVec& ch, const Sc& Zr, const PolyCommitmentGens& g) {
     Trace tr("DensePolyEval.prove", d.ctx);
     t.append_protocol_name("polynomial evaluation proof");
-    LASSO_REQUIRE(pr.ready && ch.size() == pr.k);
     side_sync();
-    const size_t Rn = (size_t)1 << pr.right, nb = (size_t)1 << pr.k;
-    DBuf d_LZ;
-    if (pr.k == 0) d_LZ = std::move(pr.M);
-    else {
-      DBuf w(d, nb); d_LZ = DBuf(d, Rn);
-      std::vector<lasso_fr> cc; for (auto& c : ch) cc.push_back(c.abi());
-      d.chk(lasso_eq_evals(d.ctx, cc.data(), (uint32_t)cc.size(), w.p), "lasso_eq_evals");
-      d.chk(lasso_matvec_left_dev(d.ctx, pr.M.p, w.p, nb, Rn, d_LZ.p), "lasso_matvec_left_dev");
-    }
-    std::vector<uint8_t> a_bytes(32 * Rn);
-    d.chk(lasso_fr_to_bytes(d.ctx, pr.R.p, Rn, a_bytes.data()), "lasso_fr_to_bytes");
-    return dot_product_log_prove(g, d_LZ, pr.R, a_bytes, Zr);
+    return open_combine(d, t, tape, bp, ch, Zr, g);
   }
   // ---- CombinedTableEvalProof::prove (subtables/mod.rs:285-313) / the two n-to-1 reductions of HashLayerProof (memory_checking.rs:370-449)
-  DotProductProofLog joint_open(const char* evals_label, const char* challenge_label, const char* joint_label, ScVec evals, bool pad_before_append,
-                                const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const PolyCommitmentGens& g, OpenPrep* prep = nullptr) {
-    if (pad_before_append) evals.resize(next_pow2(evals.size()), Sc::zero());
-    t.append_scalars(evals_label, evals);
-    ScVec ch = t.challenge_vector(challenge_label, ceil_log2(evals.size()));
-    evals.resize(next_pow2(evals.size()), Sc::zero());     // DensePolynomial::new_padded for the unpadded case (:420)
-    size_t len = evals.size();
-    for (size_t i = ch.size(); i-- > 0;) { len /= 2; for (size_t k = 0; k < len; k++) evals[k] = evals[2 * k] + ch[i] * (evals[2 * k + 1] - evals[2 * k]); }   // bound_poly_var_bot
-    LASSO_REQUIRE(len == 1);
-    Sc joint = evals[0];
-    ScVec r_joint = ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
-    t.append_scalar(joint_label, joint);
-    if (prep && prep->ready) { LASSO_REQUIRE(prep->k == ch.size() && prep->k + r.size() == num_vars); return poly_eval_prove_prepped(*prep, ch, joint, g); }
-    return poly_eval_prove(d_poly, num_vars, r_joint, joint, g);
+  DotProductProofLog joint_open(const char* evals_label, const char* challenge_label, const char* joint_label, const ScVec& evals, bool pad_before_append,
+                                const lasso_fr* d_poly, size_t num_vars, const ScVec& r, const PolyCommitmentGens& g, BlockPass* prep = nullptr) {
+    const JointClaim jc = joint_claim(t, evals_label, challenge_label, joint_label, evals, pad_before_append);
+    if (prep && prep->ready) { LASSO_REQUIRE(prep->kappa == jc.ch.size() && prep->kappa + r.size() == num_vars); return poly_eval_prove_prepped(*prep, jc.ch, jc.joint, g); }
+    ScVec r_joint = jc.ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
+    return poly_eval_prove(d_poly, num_vars, r_joint, jc.joint, g);
   }
 
   // ---- SparsePolynomialEvaluationProof::prove (surge.rs:119-211)
@@ -2116,7 +2089,7 @@ class Prover {
     const size_t k_derefs = ceil_log2(next_pow2(alpha)), k_ops = ceil_log2(next_pow2(2 * C)), k_mem = ceil_log2(next_pow2(C));
     std::vector<const lasso_fr*> at_ops(Eptr);
     if (!dense.compact) { for (size_t i = 0; i < C; i++) at_ops.push_back(dense.dim(i)); for (size_t i = 0; i < C; i++) at_ops.push_back(dense.read(i)); }
-    OpenPrep prep_derefs, prep_ops, prep_mem;
+    BlockPass prep_derefs, prep_ops, prep_mem;
     const bool side = P == 1 && !!sw::side_stream() && !dense.compact;   // compact form: dim / read exist as field elements one at a time, on the main context
     if (side) {
       lasso_ctx* sc = d.side();

@@ -97,17 +97,20 @@ struct lasso_host_poly_gens {
 static thread_local std::string g_err;
 #define GUARD(...) try { __VA_ARGS__ } catch (const std::exception& e) { g_err = e.what(); return -1; } catch (...) { g_err = "unknown error"; return -1; }
 static int32_t emit(const std::vector<uint8_t>& b, uint8_t* out, size_t cap, size_t* len) { if (len) *len = b.size(); if (!out || b.size() > cap) { g_err = "output buffer too small"; return -2; } memcpy(out, b.data(), b.size()); return 0; }
-// every lasso_host_*_stats: the row's counters (c1 only where the row has two), whether the device library has the extension, and the reset
-static int32_t ext_stats(const char* who, lasso_host* h, Ext e, uint64_t* c0, uint64_t* c1, int32_t* available, int32_t reset) {
+// `n` scalars of the caller's, memory form, any representative -> Sc
+static ScVec scalars_in(const lasso_fr* v, size_t n) { ScVec out; out.reserve(n); for (size_t i = 0; i < n; i++) out.push_back(Sc::from_abi(v[i])); return out; }
+// every lasso_host_*_stats: a pair of this host's counters (c1 only where the call reports two) and the reset; e != EXT_COUNT: whether the device library has that extension
+static int32_t pair_stats(const char* who, lasso_host* h, uint64_t (lasso_host::*pair)[2], Ext e, uint64_t* c0, uint64_t* c1, int32_t* available, int32_t reset) {
   GUARD(
     if (!h) throw Error(std::string(who) + ": null host");
-    uint64_t* c = h->ext_count[e];
+    uint64_t* c = pair ? h->*pair : h->ext_count[e];
     if (c0) *c0 = c[0];
     if (c1) *c1 = c[1];
     if (available) *available = EXTS[e].available() ? 1 : 0;
     if (reset) c[0] = c[1] = 0;
     return 0;)
 }
+static int32_t ext_stats(const char* who, lasso_host* h, Ext e, uint64_t* c0, uint64_t* c1, int32_t* available, int32_t reset) { return pair_stats(who, h, nullptr, e, c0, c1, available, reset); }
 
 extern "C" {
 const char* lasso_host_last_error(void) { return g_err.c_str(); }
@@ -271,25 +274,32 @@ static void check_custom_gens(const Strategy& S, const SparsePolyCommitmentGens&
   const size_t nv = ceil_log2(next_pow2(S.num_memories() * next_pow2(s)));
   if (G.gens_derefs.n != ((size_t)1 << (nv - nv / 2))) throw Error("custom strategy: num_memories does not match the generators (gens_derefs was made for another number of memories or lookups)");
 }
-static std::vector<uint8_t> run_prover(lasso_host* h, const Strategy& S, DensifiedRepresentation& D, const SparsePolyCommitmentGens& G, ProofTranscript& t, RandomTape& tape, const ScVec& rv) {
+// lasso_host_prove / lasso_host_prove_cb behind their transcripts, lasso_host_verify / lasso_host_verify_cb behind theirs
+static int32_t run_prover(lasso_host* h, const Strategy& S, DensifiedRepresentation& D, const SparsePolyCommitmentGens& G, ProofTranscript& t, RandomTape& tape, const lasso_fr* r, size_t r_len,
+                          uint8_t* out, size_t cap, size_t* len) {
   std::vector<uint8_t> bytes;
   {
     if (S.custom() && (S.C() != D.C || S.M() != D.m)) throw Error("custom strategy: c / log_m do not match the densified representation");
     check_custom_gens(S, G, D.s);
     Prover P(h->dev, S, D, G, t, tape);
-    try { P.prove(rv); } catch (...) { h->dev.abort_all(); throw; }
+    try { P.prove(scalars_in(r, r_len)); } catch (...) { h->dev.abort_all(); throw; }
     bytes.swap(P.proof_bytes);
   }
-  return bytes;
+  return emit(bytes, out, cap, len);
+}
+static void run_verifier(lasso_host* h, const Strategy& S, const SparsePolyCommitmentGens& G, ProofTranscript& t, size_t s, size_t log_m, const lasso_fr* r, size_t r_len,
+                         const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
+  check_custom_gens(S, G, s);
+  Verifier V(h->dev, S, G, t, h->wire_decoder(), h->points_msm(), h->tables_mle());
+  *ok = V.verify(proof, proof_len, commitment, commitment_len, s, log_m, scalars_in(r, r_len)) ? 1 : 0;
+  HostClock::dump();
 }
 int32_t lasso_host_prove(lasso_host* h, lasso_host_dense* d, lasso_host_gens* g, const lasso_strategy* st, const lasso_fr* r, size_t r_len, const char* tl, const char* pl,
                          uint8_t* out, size_t cap, size_t* len) {
   GUARD(
     Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tl); RandomTape tape(pl);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    std::vector<uint8_t> bytes = run_prover(h, S, *d->d, *g->g, t, tape, rv);
-    return emit(bytes, out, cap, len);)
+    return run_prover(h, S, *d->d, *g->g, t, tape, r, r_len, out, cap, len);)
 }
 // ---- live transcripts (include/lasso_prover.h lasso_transcript_vtbl)
 struct lasso_merlin { Merlin m; explicit lasso_merlin(const char* label) : m(label) {} };
@@ -314,9 +324,7 @@ int32_t lasso_host_prove_cb(lasso_host* h, lasso_host_dense* d, lasso_host_gens*
     if (!h || !d || !g || !st || !r || !tv || !pv) throw Error("lasso_host_prove_cb: null argument");
     Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    std::vector<uint8_t> bytes = run_prover(h, S, *d->d, *g->g, t, tape, rv);
-    return emit(bytes, out, cap, len);)
+    return run_prover(h, S, *d->d, *g->g, t, tape, r, r_len, out, cap, len);)
 }
 int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_strategy* st, size_t s, const lasso_fr* r, size_t r_len, const lasso_transcript_vtbl* tv, void* tu,
                              const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
@@ -324,11 +332,7 @@ int32_t lasso_host_verify_cb(lasso_host* h, lasso_host_gens* g, const lasso_stra
     if (!h || !g || !st || !r || !proof || !commitment || !ok || !tv) throw Error("lasso_host_verify_cb: null argument");
     Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tv, tu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm(), h->tables_mle());
-    *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
-    HostClock::dump();
+    run_verifier(h, S, *g->g, t, s, st->log_m, r, r_len, proof, proof_len, commitment, commitment_len, ok);
     return 0;)
 }
 int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strategy* st, size_t s, const lasso_fr* r, size_t r_len, const char* tl,
@@ -337,11 +341,7 @@ int32_t lasso_host_verify(lasso_host* h, lasso_host_gens* g, const lasso_strateg
     if (!h || !g || !st || !r || !proof || !commitment || !ok) throw Error("lasso_host_verify: null argument");
     Strategy S = Strategy::from_abi(st);
     ProofTranscript t(tl);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    check_custom_gens(S, *g->g, s);
-    Verifier V(h->dev, S, *g->g, t, h->wire_decoder(), h->points_msm(), h->tables_mle());
-    *ok = V.verify(proof, proof_len, commitment, commitment_len, s, st->log_m, rv) ? 1 : 0;
-    HostClock::dump();
+    run_verifier(h, S, *g->g, t, s, st->log_m, r, r_len, proof, proof_len, commitment, commitment_len, ok);
     return 0;)
 }
 // Test support: Prover::prove_cubic_batched (sumcheck.rs:27-135 with C = EqPolynomial(rand).evals(), grand_product.rs:122-128) on caller-supplied
@@ -361,7 +361,7 @@ int32_t lasso_host_debug_cubic_batched(lasso_host* h, lasso_host_dense* dn, lass
       h->dev.chk(lasso_upload(h->dev.ctx, bufs.back().p, (c < k ? A + c * n : B + (c - k) * n), n * sizeof(lasso_fr)), "lasso_upload");
       (c < k ? pa : pb).push_back(bufs.back().p);
     }
-    ScVec rv, cv; for (size_t i = 0; i < ell; i++) rv.push_back(Sc::from_abi(rand[i])); for (size_t i = 0; i < k; i++) cv.push_back(Sc::from_abi(coeffs[i]));
+    ScVec rv = scalars_in(rand, ell), cv = scalars_in(coeffs, k);
     {   // read per call: the tests drive the HOST rounds (Prover::host_cubic_rounds: the tree tops' layers) through the same scripted points
       if (sw::debug_cubic_host()) {
         std::vector<ScVec> ha(k, ScVec(n)), hb(k, ScVec(n));
@@ -430,7 +430,7 @@ int32_t lasso_host_tables_mle(lasso_host* h, const lasso_strategy* st, const las
     if (!h || !st || !out || (!point && point_len) || (where != 0 && where != 1)) throw Error("lasso_host_tables_mle: null argument, or `where` is neither 0 (host) nor 1 (device)");
     const Strategy S = Strategy::from_abi(st);
     if (point_len != S.abi.log_m) throw Error("lasso_host_tables_mle: the point must have log_m coordinates");
-    ScVec pt; for (size_t i = 0; i < point_len; i++) pt.push_back(Sc::from_abi(point[i]));
+    const ScVec pt = scalars_in(point, point_len);
     const size_t n = S.num_subtables();
     if (S.custom() && where == 1) {
       if (!lasso_tables_mle) throw ext_unavailable("lasso_host_tables_mle", EXT_MLE);
@@ -574,12 +574,15 @@ static void poly_vec_check(const std::string& w, const void* values, int32_t for
   if (on_device != 0 && on_device != 1) throw Error(w + ": `on_device` is neither 0 (host) nor 1 (device)");
   if ((uintptr_t)values & (on_device ? 15 : 7)) throw Error(w + ": the values pointer is misaligned for its form (host memory: 8 bytes, device memory: 16 bytes)");
 }
+// slab mode's refusal, of the calls that take one vector and of those that take several
+static const char* const POLY_SLAB = ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there";
+static const char* const POLYS_SLAB = ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vectors are not offered there";
 static void poly_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s) {
   const std::string w(who);
   if (!h || !g || !g->g) throw Error(w + ": null argument");
   if (g->owner != h) throw Error(w + ": the generators belong to another host");
   poly_vec_check(w, values, form, on_device);
-  if (h->dev.comm.sharded()) throw Error(w + ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+  if (h->dev.comm.sharded()) throw Error(w + POLY_SLAB);
   if (s == 0 || (s & (s - 1))) throw Error(w + ": the number of values must be a power of two");
   if (s != ((size_t)1 << g->num_vars)) throw Error(w + ": the generators were made for 2^" + std::to_string(g->num_vars) + " values, got " + std::to_string(s));
 }
@@ -603,7 +606,125 @@ static void poly_gens_check(const char* who, lasso_host* h, size_t num_vars, con
   const std::string w(who);
   if (!h || !out) throw Error(w + ": null argument");
   if (num_vars < 1 || num_vars > 30) throw Error(w + ": num_vars must be 1 .. 30");
-  if (h->dev.comm.sharded()) throw Error(w + ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
+  if (h->dev.comm.sharded()) throw Error(w + POLY_SLAB);
+}
+// what the verify calls refuse before they read anything: `rest` = the call's other pointers are all there; k == SIZE_MAX: one vector at a point of num_vars coordinates,
+// otherwise k evaluations at a point of r_len coordinates
+static void verify_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, bool rest, size_t r_len, size_t k = SIZE_MAX) {
+  const std::string w(who);
+  if (!h || !g || !g->g || !rest) throw Error(w + ": null argument");
+  if (g->owner != h) throw Error(w + ": the generators belong to another host");
+  if (h->dev.comm.sharded()) throw Error(w + (k == SIZE_MAX ? POLY_SLAB : POLYS_SLAB));
+  if (k == SIZE_MAX) { if (r_len != g->num_vars) throw Error(w + ": the point must have num_vars coordinates"); return; }
+  if (k == 0) throw Error(w + ": no vectors (k = 0)");
+  if (r_len + ceil_log2(k) != g->num_vars) throw Error(w + ": the generators were made for " + std::to_string(g->num_vars) + " variables, but " + std::to_string(k) + " evaluations at a point of " +
+                                                       std::to_string(r_len) + " coordinates are an opening in " + std::to_string(r_len + ceil_log2(k)));
+}
+// an opening and the commitment it is about, each read to its last byte
+static WireDotProductProofLog read_opening(const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, std::vector<WirePoint>& comm) {
+  ProofReader pr(proof, proof_len);
+  const WireDotProductProofLog P = read_dpl(pr);
+  if (!pr.done()) throw Error("proof bytes: trailing data");
+  ProofReader cr(commitment, commitment_len);
+  comm = cr.pts_vec();
+  if (!cr.done()) throw Error("commitment bytes: trailing data");
+  return P;
+}
+// ---- commitments, plain and hiding (include/lasso_prover_blind.h: the hiding form is composed of the device entries the plain one uses and of slab mode's two)
+static void blinds_check(const std::string& w, const void* blinds) {
+  if ((uintptr_t)blinds & 7) throw Error(w + ": the blinds pointer is misaligned (host memory: 8 bytes)");
+}
+// tape.random_vector("poly_blinds", count) (dense_mlpoly.rs:166-170) into the caller's array
+static ScVec blinds_draw(const lasso_transcript_vtbl* pv, void* pu, size_t count, lasso_fr* out) {
+  RandomTape tape(pv, pu);
+  const ScVec b = tape.random_vector("poly_blinds", count);
+  for (size_t i = 0; i < count; i++) out[i] = (b[i] * Sc::one()).abi();
+  return b;
+}
+// rows[i] += blinds[i] * h on the host: `rows` wire rows are decoded as the verifier would decode them, the sums compressed in one batch
+static void blind_rows_host(lasso_host* h, const PolyCommitmentGens& g, const Sc* blinds, size_t rows, uint8_t* wire) {
+  const std::vector<WirePoint> pts = decode_points(h->dev, h->wire_decoder(), wire, rows, "commitment rows");
+  std::vector<Pt> sum(rows);
+  for (size_t i = 0; i < rows; i++) { const Pt b = g.hmul.mul(blinds[i]); sum[i] = pts[i].infinity ? b : pts[i].p + b; }
+  std::vector<uint8_t> out; compress_batch(sum, out);
+  memcpy(wire, out.data(), 32 * rows);
+  h->blind_count[1] += rows;
+}
+// `rows` whole rows of R values of one vector as wire bytes at `wire`: row i = <Z_i, G>, + blinds[i] * h where there are blinds (commitments.rs:84-93).  hb: the one-point
+// base [h], made by the first vector that is blinded on the device and destroyed by the caller
+static void commit_rows(lasso_host* h, const PolyCommitmentGens& g, const PolyOperand& o, size_t s, size_t rows, size_t R, const Sc* blinds, lasso_bases** hb, uint8_t* wire) {
+  const Dev& d = h->dev;
+  if (o.u64) {   // read as 8-byte integers; the populated bits bound the scalars: the width of the MSM's windows, and below 2^32 the 4-byte route.  The rows come back in wire form
+    uint64_t bits = 0;
+    d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
+    d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed_u64");
+    h->ext_count[EXT_POLY][0] += s;
+    if (blinds) blind_rows_host(h, g, blinds, rows, wire);
+    return;
+  }
+  if (!blinds) { const PolyCommitment c = hyrax_commit_rows(d, (const lasso_fr*)o.d, rows, R, g); memcpy(wire, c.compressed.data(), 32 * rows); return; }
+  // field elements: data rows and blind rows as the kernels' own points, side by side, added and compressed by slab mode's reduction
+  const size_t rb = lasso_point_row_bytes();
+  struct Bytes { const Dev& d; void* p; ~Bytes() { try { if (p) d.free(p); } catch (...) {} } } parts{d, d.alloc_bytes(2 * rows * rb)};
+  int32_t rc = lasso_hyrax_commit_rows_dev(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, parts.p);
+  if (rc == LASSO_ERR_UNSUPPORTED) {   // a device library without row sums on the device: wire rows, blinded on the host
+    d.chk(lasso_hyrax_commit_compressed(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed");
+    blind_rows_host(h, g, blinds, rows, wire);
+    return;
+  }
+  d.chk(rc, "lasso_hyrax_commit_rows_dev");
+  if (!*hb) d.chk(lasso_bases_create(d.ctx, &g.affine[g.n + 1], 1, hb), "lasso_bases_create");
+  DBuf d_bl(d, rows);
+  std::vector<lasso_fr> bl(rows); for (size_t i = 0; i < rows; i++) bl[i] = blinds[i].abi();
+  d.chk(lasso_upload(d.ctx, d_bl.p, bl.data(), rows * sizeof(lasso_fr)), "lasso_upload");
+  d.chk(lasso_hyrax_commit_rows_dev(d.ctx, d_bl.p, rows, 1, *hb, (uint8_t*)parts.p + rows * rb), "lasso_hyrax_commit_rows_dev");
+  d.chk(lasso_points_reduce_compress(d.ctx, parts.p, 2, rows, wire), "lasso_points_reduce_compress");
+  h->blind_count[0] += rows;
+}
+struct BlindBase { const Dev& d; lasso_bases* b = nullptr; explicit BlindBase(const Dev& d_) : d(d_) {} ~BlindBase() { if (b) lasso_bases_destroy(d.ctx, b); } };
+// DensePolynomial::merge(vecs[0 .. k)).commit(gens, blinds) in wire form, the merge never made: L rows of R values, vector b in the rows [b * rows_per, (b + 1) * rows_per)
+// (one vector: k = 1, rows_per = L).  blinds: null = None, else L of them, one draw for the whole merge
+static std::vector<uint8_t> commit_vectors(lasso_host* h, const PolyCommitmentGens& g, const lasso_host_poly_vec* vecs, size_t k, size_t s, size_t L, size_t R, size_t rows_per, const ScVec* blinds) {
+  std::vector<uint8_t> rows(32 * L);
+  BlindBase hb(h->dev);
+  for (size_t b = 0; b < k; b++) {   // one vector at a time: an uploaded one is released before the next
+    PolyOperand o; poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, o);
+    try { commit_rows(h, g, o, s, rows_per, R, blinds ? blinds->data() + b * rows_per : nullptr, &hb.b, rows.data() + 32 * b * rows_per); } catch (...) { h->dev.abort_all(); throw; }
+  }
+  if (k * rows_per < L && blinds) {   // the zero blocks behind k commit to blinds[i] * h, row by row
+    std::vector<Pt> tail; for (size_t i = k * rows_per; i < L; i++) tail.push_back(g.hmul.mul((*blinds)[i]));
+    std::vector<uint8_t> tb; compress_batch(tail, tb);
+    memcpy(rows.data() + 32 * k * rows_per, tb.data(), tb.size());
+    h->blind_count[1] += tail.size();
+  } else if (k * rows_per < L) {      // without blinds, to the identity
+    uint8_t id[32]; compress_one(Pt::identity(), id);
+    for (size_t i = k * rows_per; i < L; i++) memcpy(rows.data() + 32 * i, id, 32);
+  }
+  ProofWriter w; w.pts_vec(rows);
+  return w.b;
+}
+// lasso_host_poly_open_blinded, and lasso_host_poly_open (no blinds, no C_Zr) in its own name
+static int32_t poly_open(const char* who, lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len,
+                         const lasso_fr* blinds, const lasso_fr* blind_Zr, const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu,
+                         lasso_fr* Zr, uint8_t* C_Zr, uint8_t* proof, size_t cap, size_t* len) {
+  const std::string w(who);
+  poly_check(who, h, g, values, form, on_device, s);
+  if (!r || !tv || !pv) throw Error(w + ": null argument");
+  if (r_len != g->num_vars) throw Error(w + ": the point must have num_vars coordinates");
+  blinds_check(w, blinds); blinds_check(w, blind_Zr);
+  ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+  const ScVec rv = scalars_in(r, r_len), bl = scalars_in(blinds, blinds ? (size_t)1 << (g->num_vars / 2) : 0);
+  Sc bz; if (blind_Zr) bz = Sc::from_abi(*blind_Zr);
+  PolyOperand o; poly_operand(h, values, form, on_device, s, o);
+  Sc y; DotProductProofLog P; uint8_t cy[32];
+  try {
+    P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g, blinds ? &bl : nullptr, blind_Zr ? &bz : nullptr, cy);
+  } catch (...) { h->dev.abort_all(); throw; }
+  if (o.u64) h->ext_count[EXT_POLY][1] += s;
+  if (Zr) *Zr = (y * Sc::one()).abi();
+  if (C_Zr) memcpy(C_Zr, cy, 32);
+  ProofWriter pw; P.write(pw);
+  return emit(pw.b, proof, cap, len);
 }
 extern "C" {
 int32_t lasso_host_poly_gens_new(lasso_host* h, const char* label, size_t num_vars, lasso_host_poly_gens** out) {
@@ -626,18 +747,9 @@ void lasso_host_poly_gens_free(lasso_host_poly_gens* g) { delete g; }
 int32_t lasso_host_poly_commit(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, uint8_t* out, size_t cap, size_t* len) {
   GUARD(
     poly_check("lasso_host_poly_commit", h, g, values, form, on_device, s);
-    const Dev& d = h->dev; const size_t nv = g->num_vars, L = (size_t)1 << (nv / 2), R = (size_t)1 << (nv - nv / 2);
-    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
-    PolyCommitment c;
-    if (o.u64) {   // the populated bits bound the scalars: the width of the MSM's windows, and below 2^32 the 4-byte route
-      uint64_t bits = 0;
-      d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
-      c.rows = L; c.compressed.resize(32 * L);
-      d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, L, R, g->g->bases, c.compressed.data()), "lasso_hyrax_commit_compressed_u64");
-      h->ext_count[EXT_POLY][0] += s;
-    } else c = hyrax_commit(d, (const lasso_fr*)o.d, nv, *g->g);
-    ProofWriter w; w.pts_vec(c.compressed);
-    return emit(w.b, out, cap, len);)
+    const size_t nv = g->num_vars, L = (size_t)1 << (nv / 2), R = (size_t)1 << (nv - nv / 2);
+    const lasso_host_poly_vec v = {values, form, on_device};
+    return emit(commit_vectors(h, *g->g, &v, 1, s, L, R, L, nullptr), out, cap, len);)
 }
 int32_t lasso_host_poly_commitment_append(const lasso_transcript_vtbl* tv, void* tu, const char* label, const uint8_t* commitment, size_t len) {
   GUARD(
@@ -652,36 +764,16 @@ int32_t lasso_host_poly_commitment_append(const lasso_transcript_vtbl* tv, void*
 }
 int32_t lasso_host_poly_open(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len,
                              const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, lasso_fr* Zr, uint8_t* proof, size_t cap, size_t* len) {
-  GUARD(
-    poly_check("lasso_host_poly_open", h, g, values, form, on_device, s);
-    if (!r || !tv || !pv) throw Error("lasso_host_poly_open: null argument");
-    if (r_len != g->num_vars) throw Error("lasso_host_poly_open: the point must have num_vars coordinates");
-    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
-    Sc y; DotProductProofLog P;
-    try { P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g); } catch (...) { h->dev.abort_all(); throw; }
-    if (o.u64) h->ext_count[EXT_POLY][1] += s;
-    if (Zr) *Zr = (y * Sc::one()).abi();
-    ProofWriter w; P.write(w);
-    return emit(w.b, proof, cap, len);)
+  GUARD(return poly_open("lasso_host_poly_open", h, g, values, form, on_device, s, r, r_len, nullptr, nullptr, tv, tu, pv, pu, Zr, nullptr, proof, cap, len);)
 }
 int32_t lasso_host_poly_verify(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const lasso_fr* Zr, const lasso_transcript_vtbl* tv, void* tu,
                                const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
   GUARD(
-    if (!h || !g || !g->g || !r || !Zr || !tv || !proof || !commitment || !ok) throw Error("lasso_host_poly_verify: null argument");
-    if (g->owner != h) throw Error("lasso_host_poly_verify: the generators belong to another host");
-    if (h->dev.comm.sharded()) throw Error("lasso_host_poly_verify: a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
-    if (r_len != g->num_vars) throw Error("lasso_host_poly_verify: the point must have num_vars coordinates");
-    ProofReader pr(proof, proof_len);
-    const WireDotProductProofLog P = read_dpl(pr);
-    if (!pr.done()) throw Error("proof bytes: trailing data");
-    ProofReader cr(commitment, commitment_len);
-    const std::vector<WirePoint> comm = cr.pts_vec();
-    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    verify_check("lasso_host_poly_verify", h, g, r && Zr && tv && proof && commitment && ok, r_len);
+    std::vector<WirePoint> comm;
+    const WireDotProductProofLog P = read_opening(proof, proof_len, commitment, commitment_len, comm);
     ProofTranscript t(tv, tu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    *ok = Verifier::poly_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, rv, Sc::from_abi(*Zr), comm) ? 1 : 0;
+    *ok = Verifier::poly_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, scalars_in(r, r_len), Sc::from_abi(*Zr), comm) ? 1 : 0;
     return 0;)
 }
 int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint64_t* u64_open_elements, int32_t* available, int32_t reset) { return ext_stats("lasso_host_poly_stats", h, EXT_POLY, u64_commit_elements, u64_open_elements, available, reset); }
@@ -689,7 +781,6 @@ int32_t lasso_host_poly_stats(lasso_host* h, uint64_t* u64_commit_elements, uint
 }  // extern "C"
 // The merge of k vectors of s = 2^nv values as a matrix: 2^left rows of 2^right values, vector b in the rows [b * rows_per, (b + 1) * rows_per)
 struct PolysShape { size_t nv = 0, kappa = 0, left = 0, right = 0, rows_per = 0; };
-static const char* const POLYS_SLAB = ": a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vectors are not offered there";
 // every refusal of the calls that take vectors, before anything is uploaded or launched.  g == null: a call without generators; r_len == SIZE_MAX: a call without a point
 static PolysShape polys_check(const char* who, lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, size_t r_len) {
   const std::string w(who);
@@ -710,145 +801,70 @@ static PolysShape polys_check(const char* who, lasso_host* h, lasso_host_poly_ge
   for (size_t b = 0; b < k; b++) poly_vec_check(w + ": vector " + std::to_string(b), vecs[b].values, vecs[b].form, vecs[b].on_device);
   return sh;
 }
-// the M_b pass over the k vectors where the device reads them; host vectors are uploaded for its duration
-static Prover::PolysPass polys_pass(lasso_host* h, const lasso_host_poly_vec* vecs, size_t k, size_t s, const PolysShape& sh, const ScVec& rv, size_t* u64_vectors) {
+// the block pass over the k vectors where the device reads them, and evals[b] = MLE(vecs[b])(r), fully reduced; host vectors are uploaded for its duration
+static Prover::BlockPass polys_pass(lasso_host* h, const lasso_host_poly_vec* vecs, size_t k, size_t s, const PolysShape& sh, const ScVec& rv, ScVec& ev, lasso_fr* evals, size_t* u64_vectors) {
   std::vector<PolyOperand> ops(k); std::vector<Prover::PolyBlock> blocks(k);
   size_t wide = 0;
   for (size_t b = 0; b < k; b++) { poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, ops[b]); blocks[b] = {ops[b].d, ops[b].u64}; wide += ops[b].u64 ? 1 : 0; }
   if (u64_vectors) *u64_vectors = wide;
-  try { return Prover::polys_pass(h->dev, blocks, lasso_matvec_left_u64_dev, sh.nv, rv); } catch (...) { h->dev.abort_all(); throw; }
+  try {
+    Prover::BlockPass bp = Prover::block_pass(h->dev, h->dev.ctx, &Dev::chk, blocks, lasso_matvec_left_u64_dev, sh.nv, rv);
+    ev = Prover::block_evals(h->dev, bp, rv);
+    for (size_t b = 0; b < k; b++) evals[b] = (ev[b] * Sc::one()).abi();
+    return bp;
+  } catch (...) { h->dev.abort_all(); throw; }
+}
+// lasso_host_polys_open_blinded, and lasso_host_polys_open (blinds == null) in its own name
+static int32_t polys_open(const char* who, lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len, const lasso_fr* blinds,
+                          const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, lasso_fr* evals, uint8_t* proof, size_t cap, size_t* len) {
+  if (!g || !g->g || !r || !tv || !pv || !evals) throw Error(std::string(who) + ": null argument");
+  const PolysShape sh = polys_check(who, h, g, vecs, k, s, r_len);
+  blinds_check(who, blinds);
+  ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
+  const ScVec rv = scalars_in(r, r_len), bl = scalars_in(blinds, blinds ? (size_t)1 << sh.left : 0);
+  size_t wide = 0; ScVec ev;
+  Prover::BlockPass bp = polys_pass(h, vecs, k, s, sh, rv, ev, evals, &wide);
+  DotProductProofLog P;
+  try { P = Prover::polys_eval_prove(h->dev, t, tape, bp, ev, *g->g, blinds ? &bl : nullptr); } catch (...) { h->dev.abort_all(); throw; }
+  h->ext_count[EXT_POLY][1] += wide * s; h->polys_count[1] += k;
+  ProofWriter w; P.write(w);
+  return emit(w.b, proof, cap, len);
 }
 extern "C" {
 int32_t lasso_host_polys_commit(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, uint8_t* out, size_t cap, size_t* len) {
   GUARD(
     if (!g || !g->g) throw Error("lasso_host_polys_commit: null argument");
     const PolysShape sh = polys_check("lasso_host_polys_commit", h, g, vecs, k, s, SIZE_MAX);
-    const Dev& d = h->dev; const size_t L = (size_t)1 << sh.left, R = (size_t)1 << sh.right;
-    std::vector<uint8_t> rows(32 * L);
-    for (size_t b = 0; b < k; b++) {   // one vector at a time: an uploaded one is released before the next
-      PolyOperand o; poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, o);
-      uint8_t* at = rows.data() + 32 * b * sh.rows_per;
-      if (o.u64) {
-        uint64_t bits = 0;
-        d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
-        d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, sh.rows_per, R, g->g->bases, at), "lasso_hyrax_commit_compressed_u64");
-        h->ext_count[EXT_POLY][0] += s;
-      } else { const PolyCommitment c = hyrax_commit_rows(d, (const lasso_fr*)o.d, sh.rows_per, R, *g->g); memcpy(at, c.compressed.data(), 32 * sh.rows_per); }
-    }
-    uint8_t id[32]; compress_one(Pt::identity(), id);   // the zero blocks behind k commit to the identity, row by row
-    for (size_t i = k * sh.rows_per; i < L; i++) memcpy(rows.data() + 32 * i, id, 32);
+    const std::vector<uint8_t> bytes = commit_vectors(h, *g->g, vecs, k, s, (size_t)1 << sh.left, (size_t)1 << sh.right, sh.rows_per, nullptr);
     h->polys_count[0] += k;
-    ProofWriter w; w.pts_vec(rows);
-    return emit(w.b, out, cap, len);)
+    return emit(bytes, out, cap, len);)
 }
 int32_t lasso_host_polys_open(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len,
                               const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu, lasso_fr* evals, uint8_t* proof, size_t cap, size_t* len) {
-  GUARD(
-    if (!g || !g->g || !r || !tv || !pv || !evals) throw Error("lasso_host_polys_open: null argument");
-    const PolysShape sh = polys_check("lasso_host_polys_open", h, g, vecs, k, s, r_len);
-    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    size_t wide = 0;
-    Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, &wide);
-    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
-    DotProductProofLog P;
-    try { P = Prover::polys_eval_prove(h->dev, t, tape, ps, *g->g); } catch (...) { h->dev.abort_all(); throw; }
-    h->ext_count[EXT_POLY][1] += wide * s; h->polys_count[1] += k;
-    ProofWriter w; P.write(w);
-    return emit(w.b, proof, cap, len);)
+  GUARD(return polys_open("lasso_host_polys_open", h, g, vecs, k, s, r, r_len, nullptr, tv, tu, pv, pu, evals, proof, cap, len);)
 }
 int32_t lasso_host_polys_verify(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const lasso_fr* evals, size_t k, const lasso_transcript_vtbl* tv, void* tu,
                                 const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
   GUARD(
-    if (!h || !g || !g->g || (!r && r_len) || !evals || !tv || !proof || !commitment || !ok) throw Error("lasso_host_polys_verify: null argument");
-    if (g->owner != h) throw Error("lasso_host_polys_verify: the generators belong to another host");
-    if (h->dev.comm.sharded()) throw Error(std::string("lasso_host_polys_verify") + POLYS_SLAB);
-    if (k == 0) throw Error("lasso_host_polys_verify: no vectors (k = 0)");
-    if (r_len + ceil_log2(k) != g->num_vars) throw Error("lasso_host_polys_verify: the generators were made for " + std::to_string(g->num_vars) + " variables, but " + std::to_string(k) + " evaluations at a point of " +
-                                                         std::to_string(r_len) + " coordinates are an opening in " + std::to_string(r_len + ceil_log2(k)));
-    ProofReader pr(proof, proof_len);
-    const WireDotProductProofLog P = read_dpl(pr);
-    if (!pr.done()) throw Error("proof bytes: trailing data");
-    ProofReader cr(commitment, commitment_len);
-    const std::vector<WirePoint> comm = cr.pts_vec();
-    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    verify_check("lasso_host_polys_verify", h, g, (r || !r_len) && evals && tv && proof && commitment && ok, r_len, k);
+    std::vector<WirePoint> comm;
+    const WireDotProductProofLog P = read_opening(proof, proof_len, commitment, commitment_len, comm);
     ProofTranscript t(tv, tu);
-    ScVec rv, ev; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i])); for (size_t b = 0; b < k; b++) ev.push_back(Sc::from_abi(evals[b]));
-    *ok = Verifier::combined_table_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, rv, ev, comm) ? 1 : 0;
+    *ok = Verifier::combined_table_eval_verify_plain(h->dev, t, h->points_msm(), P, *g->g, scalars_in(r, r_len), scalars_in(evals, k), comm) ? 1 : 0;
     return 0;)
 }
 int32_t lasso_host_polys_evaluate(lasso_host* h, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len, lasso_fr* evals) {
   GUARD(
     if ((!r && r_len) || !evals) throw Error("lasso_host_polys_evaluate: null argument");
     const PolysShape sh = polys_check("lasso_host_polys_evaluate", h, nullptr, vecs, k, s, r_len);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    const Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, nullptr);
-    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
+    ScVec ev;
+    (void)polys_pass(h, vecs, k, s, sh, scalars_in(r, r_len), ev, evals, nullptr);
     return 0;)
 }
 int32_t lasso_host_polys_stats(lasso_host* h, uint64_t* vectors_committed, uint64_t* vectors_opened, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_polys_stats: null host");
-    if (vectors_committed) *vectors_committed = h->polys_count[0];
-    if (vectors_opened) *vectors_opened = h->polys_count[1];
-    if (reset) h->polys_count[0] = h->polys_count[1] = 0;
-    return 0;)
+  return pair_stats("lasso_host_polys_stats", h, &lasso_host::polys_count, EXT_COUNT, vectors_committed, vectors_opened, nullptr, reset);
 }
-// ---- include/lasso_prover_blind.h: the hiding form of the two headers above, composed of the device entries they use and of slab mode's two
-}  // extern "C"
-// `count` scalars of the caller's, memory form, any representative -> Sc; and back, fully reduced
-static ScVec blinds_in(const lasso_fr* b, size_t count) { ScVec v; v.reserve(count); for (size_t i = 0; i < count; i++) v.push_back(Sc::from_abi(b[i])); return v; }
-static void blinds_check(const std::string& w, const void* blinds) {
-  if ((uintptr_t)blinds & 7) throw Error(w + ": the blinds pointer is misaligned (host memory: 8 bytes)");
-}
-// tape.random_vector("poly_blinds", count) (dense_mlpoly.rs:166-170) into the caller's array
-static ScVec blinds_draw(const lasso_transcript_vtbl* pv, void* pu, size_t count, lasso_fr* out) {
-  RandomTape tape(pv, pu);
-  const ScVec b = tape.random_vector("poly_blinds", count);
-  for (size_t i = 0; i < count; i++) out[i] = (b[i] * Sc::one()).abi();
-  return b;
-}
-// rows[i] += blinds[i] * h on the host: `rows` wire rows are decoded as the verifier would decode them, the sums compressed in one batch
-static void blind_rows_host(lasso_host* h, const PolyCommitmentGens& g, const Sc* blinds, size_t rows, uint8_t* wire) {
-  const std::vector<WirePoint> pts = decode_points(h->dev, h->wire_decoder(), wire, rows, "commitment rows");
-  std::vector<Pt> sum(rows);
-  for (size_t i = 0; i < rows; i++) { const Pt b = g.hmul.mul(blinds[i]); sum[i] = pts[i].infinity ? b : pts[i].p + b; }
-  std::vector<uint8_t> out; compress_batch(sum, out);
-  memcpy(wire, out.data(), 32 * rows);
-  h->blind_count[1] += rows;
-}
-// `rows` whole rows of R values of one vector, blinded, as wire bytes at `wire`: row i = <Z_i, G> + blinds[i] * h (commitments.rs:84-93).  hb: the one-point base [h], made by
-// the first vector that takes the device route and destroyed by the caller
-static void blind_commit_rows(lasso_host* h, const PolyCommitmentGens& g, const PolyOperand& o, size_t s, size_t rows, size_t R, const Sc* blinds, lasso_bases** hb, uint8_t* wire) {
-  const Dev& d = h->dev;
-  if (o.u64) {   // read as 8-byte integers; the rows come back in wire form
-    uint64_t bits = 0;
-    d.chk(lasso_u64_or(d.ctx, (const uint64_t*)o.d, s, &bits), "lasso_u64_or");
-    d.chk(lasso_hyrax_commit_compressed_u64(d.ctx, (const uint64_t*)o.d, bits, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed_u64");
-    h->ext_count[EXT_POLY][0] += s;
-    blind_rows_host(h, g, blinds, rows, wire);
-    return;
-  }
-  // field elements: data rows and blind rows as the kernels' own points, side by side, added and compressed by slab mode's reduction
-  const size_t rb = lasso_point_row_bytes();
-  struct Bytes { const Dev& d; void* p; ~Bytes() { try { if (p) d.free(p); } catch (...) {} } } parts{d, d.alloc_bytes(2 * rows * rb)};
-  int32_t rc = lasso_hyrax_commit_rows_dev(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, parts.p);
-  if (rc == LASSO_ERR_UNSUPPORTED) {   // a device library without row sums on the device: wire rows, blinded on the host
-    d.chk(lasso_hyrax_commit_compressed(d.ctx, (const lasso_fr*)o.d, rows, R, g.bases, wire), "lasso_hyrax_commit_compressed");
-    blind_rows_host(h, g, blinds, rows, wire);
-    return;
-  }
-  d.chk(rc, "lasso_hyrax_commit_rows_dev");
-  if (!*hb) d.chk(lasso_bases_create(d.ctx, &g.affine[g.n + 1], 1, hb), "lasso_bases_create");
-  DBuf d_bl(d, rows);
-  std::vector<lasso_fr> bl(rows); for (size_t i = 0; i < rows; i++) bl[i] = blinds[i].abi();
-  d.chk(lasso_upload(d.ctx, d_bl.p, bl.data(), rows * sizeof(lasso_fr)), "lasso_upload");
-  d.chk(lasso_hyrax_commit_rows_dev(d.ctx, d_bl.p, rows, 1, *hb, (uint8_t*)parts.p + rows * rb), "lasso_hyrax_commit_rows_dev");
-  d.chk(lasso_points_reduce_compress(d.ctx, parts.p, 2, rows, wire), "lasso_points_reduce_compress");
-  h->blind_count[0] += rows;
-}
-struct BlindBase { const Dev& d; lasso_bases* b = nullptr; explicit BlindBase(const Dev& d_) : d(d_) {} ~BlindBase() { if (b) lasso_bases_destroy(d.ctx, b); } };
-extern "C" {
+// ---- include/lasso_prover_blind.h: the hiding form of the two headers above
 int32_t lasso_host_poly_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s,
                                        const lasso_transcript_vtbl* pv, void* pu, lasso_fr* blinds_out, uint8_t* out, size_t cap, size_t* len) {
   GUARD(
@@ -857,59 +873,26 @@ int32_t lasso_host_poly_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, c
     blinds_check("lasso_host_poly_commit_blinded", blinds_out);
     const size_t nv = g->num_vars, L = (size_t)1 << (nv / 2), R = (size_t)1 << (nv - nv / 2);
     const ScVec blinds = blinds_draw(pv, pu, L, blinds_out);
-    std::vector<uint8_t> rows(32 * L);
-    {
-      PolyOperand o; poly_operand(h, values, form, on_device, s, o);
-      BlindBase hb(h->dev);
-      try { blind_commit_rows(h, *g->g, o, s, L, R, blinds.data(), &hb.b, rows.data()); } catch (...) { h->dev.abort_all(); throw; }
-    }
-    ProofWriter w; w.pts_vec(rows);
-    return emit(w.b, out, cap, len);)
+    const lasso_host_poly_vec v = {values, form, on_device};
+    return emit(commit_vectors(h, *g->g, &v, 1, s, L, R, L, &blinds), out, cap, len);)
 }
 int32_t lasso_host_poly_open_blinded(lasso_host* h, lasso_host_poly_gens* g, const void* values, int32_t form, int32_t on_device, size_t s, const lasso_fr* r, size_t r_len,
                                      const lasso_fr* blinds, const lasso_fr* blind_Zr, const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu,
                                      lasso_fr* Zr, uint8_t C_Zr[32], uint8_t* proof, size_t cap, size_t* len) {
-  GUARD(
-    poly_check("lasso_host_poly_open_blinded", h, g, values, form, on_device, s);
-    if (!r || !tv || !pv) throw Error("lasso_host_poly_open_blinded: null argument");
-    if (r_len != g->num_vars) throw Error("lasso_host_poly_open_blinded: the point must have num_vars coordinates");
-    blinds_check("lasso_host_poly_open_blinded", blinds); blinds_check("lasso_host_poly_open_blinded", blind_Zr);
-    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    ScVec bl; Sc bz;
-    if (blinds) bl = blinds_in(blinds, (size_t)1 << (g->num_vars / 2));
-    if (blind_Zr) bz = Sc::from_abi(*blind_Zr);
-    PolyOperand o; poly_operand(h, values, form, on_device, s, o);
-    Sc y; DotProductProofLog P; uint8_t cy[32];
-    try {
-      P = Prover::poly_eval_prove_resident(h->dev, t, tape, o.d, o.u64 ? lasso_matvec_left_u64_dev : nullptr, g->num_vars, rv, nullptr, &y, *g->g, blinds ? &bl : nullptr, blind_Zr ? &bz : nullptr, cy);
-    } catch (...) { h->dev.abort_all(); throw; }
-    if (o.u64) h->ext_count[EXT_POLY][1] += s;
-    if (Zr) *Zr = (y * Sc::one()).abi();
-    if (C_Zr) memcpy(C_Zr, cy, 32);
-    ProofWriter w; P.write(w);
-    return emit(w.b, proof, cap, len);)
+  GUARD(return poly_open("lasso_host_poly_open_blinded", h, g, values, form, on_device, s, r, r_len, blinds, blind_Zr, tv, tu, pv, pu, Zr, C_Zr, proof, cap, len);)
 }
 int32_t lasso_host_poly_verify_committed(lasso_host* h, lasso_host_poly_gens* g, const lasso_fr* r, size_t r_len, const uint8_t C_Zr[32], const lasso_transcript_vtbl* tv, void* tu,
                                          const uint8_t* proof, size_t proof_len, const uint8_t* commitment, size_t commitment_len, int32_t* ok) {
   GUARD(
-    if (!h || !g || !g->g || !r || !C_Zr || !tv || !proof || !commitment || !ok) throw Error("lasso_host_poly_verify_committed: null argument");
-    if (g->owner != h) throw Error("lasso_host_poly_verify_committed: the generators belong to another host");
-    if (h->dev.comm.sharded()) throw Error("lasso_host_poly_verify_committed: a slab-mode host (world > 1) holds one residue class of every polynomial per rank; commitments to and openings of a caller's vector are not offered there");
-    if (r_len != g->num_vars) throw Error("lasso_host_poly_verify_committed: the point must have num_vars coordinates");
-    ProofReader pr(proof, proof_len);
-    const WireDotProductProofLog P = read_dpl(pr);
-    if (!pr.done()) throw Error("proof bytes: trailing data");
-    ProofReader cr(commitment, commitment_len);
-    const std::vector<WirePoint> comm = cr.pts_vec();
-    if (!cr.done()) throw Error("commitment bytes: trailing data");
+    verify_check("lasso_host_poly_verify_committed", h, g, r && C_Zr && tv && proof && commitment && ok, r_len);
+    std::vector<WirePoint> comm;
+    const WireDotProductProofLog P = read_opening(proof, proof_len, commitment, commitment_len, comm);
     WirePoint cz;
     if (!decompress_point(C_Zr, cz.p, cz.infinity)) throw Error("C_Zr bytes: invalid point encoding");
     if (cz.infinity) cz.p = Pt::identity();
     compress_affine_pt(cz.p, cz.infinity, cz.bytes);
     ProofTranscript t(tv, tu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    *ok = Verifier::poly_eval_verify(h->dev, t, h->points_msm(), P, *g->g, rv, cz, comm) ? 1 : 0;
+    *ok = Verifier::poly_eval_verify(h->dev, t, h->points_msm(), P, *g->g, scalars_in(r, r_len), cz, comm) ? 1 : 0;
     return 0;)
 }
 int32_t lasso_host_polys_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s,
@@ -921,48 +904,17 @@ int32_t lasso_host_polys_commit_blinded(lasso_host* h, lasso_host_poly_gens* g, 
     blinds_check("lasso_host_polys_commit_blinded", blinds_out);
     const size_t L = (size_t)1 << sh.left, R = (size_t)1 << sh.right;
     const ScVec blinds = blinds_draw(pv, pu, L, blinds_out);   // one draw for the whole merge, as merge(polys).commit(gens, Some(tape)) makes it
-    std::vector<uint8_t> rows(32 * L);
-    BlindBase hb(h->dev);
-    for (size_t b = 0; b < k; b++) {   // one vector at a time: an uploaded one is released before the next
-      PolyOperand o; poly_operand(h, vecs[b].values, vecs[b].form, vecs[b].on_device, s, o);
-      try { blind_commit_rows(h, *g->g, o, s, sh.rows_per, R, blinds.data() + b * sh.rows_per, &hb.b, rows.data() + 32 * b * sh.rows_per); } catch (...) { h->dev.abort_all(); throw; }
-    }
-    if (k * sh.rows_per < L) {   // the zero blocks behind k commit to blinds[i] * h, row by row
-      std::vector<Pt> tail; for (size_t i = k * sh.rows_per; i < L; i++) tail.push_back(g->g->hmul.mul(blinds[i]));
-      std::vector<uint8_t> tb; compress_batch(tail, tb);
-      memcpy(rows.data() + 32 * k * sh.rows_per, tb.data(), tb.size());
-      h->blind_count[1] += tail.size();
-    }
+    const std::vector<uint8_t> bytes = commit_vectors(h, *g->g, vecs, k, s, L, R, sh.rows_per, &blinds);
     h->polys_count[0] += k;
-    ProofWriter w; w.pts_vec(rows);
-    return emit(w.b, out, cap, len);)
+    return emit(bytes, out, cap, len);)
 }
 int32_t lasso_host_polys_open_blinded(lasso_host* h, lasso_host_poly_gens* g, const lasso_host_poly_vec* vecs, size_t k, size_t s, const lasso_fr* r, size_t r_len,
                                       const lasso_fr* blinds, const lasso_transcript_vtbl* tv, void* tu, const lasso_transcript_vtbl* pv, void* pu,
                                       lasso_fr* evals, uint8_t* proof, size_t cap, size_t* len) {
-  GUARD(
-    if (!g || !g->g || !r || !tv || !pv || !evals) throw Error("lasso_host_polys_open_blinded: null argument");
-    const PolysShape sh = polys_check("lasso_host_polys_open_blinded", h, g, vecs, k, s, r_len);
-    blinds_check("lasso_host_polys_open_blinded", blinds);
-    ProofTranscript t(tv, tu); RandomTape tape(pv, pu);
-    ScVec rv; for (size_t i = 0; i < r_len; i++) rv.push_back(Sc::from_abi(r[i]));
-    ScVec bl; if (blinds) bl = blinds_in(blinds, (size_t)1 << sh.left);
-    size_t wide = 0;
-    Prover::PolysPass ps = polys_pass(h, vecs, k, s, sh, rv, &wide);
-    for (size_t b = 0; b < k; b++) evals[b] = (ps.evals[b] * Sc::one()).abi();
-    DotProductProofLog P;
-    try { P = Prover::polys_eval_prove(h->dev, t, tape, ps, *g->g, blinds ? &bl : nullptr); } catch (...) { h->dev.abort_all(); throw; }
-    h->ext_count[EXT_POLY][1] += wide * s; h->polys_count[1] += k;
-    ProofWriter w; P.write(w);
-    return emit(w.b, proof, cap, len);)
+  GUARD(return polys_open("lasso_host_polys_open_blinded", h, g, vecs, k, s, r, r_len, blinds, tv, tu, pv, pu, evals, proof, cap, len);)
 }
 int32_t lasso_host_blind_stats(lasso_host* h, uint64_t* rows_device, uint64_t* rows_host, int32_t reset) {
-  GUARD(
-    if (!h) throw Error("lasso_host_blind_stats: null host");
-    if (rows_device) *rows_device = h->blind_count[0];
-    if (rows_host) *rows_host = h->blind_count[1];
-    if (reset) h->blind_count[0] = h->blind_count[1] = 0;
-    return 0;)
+  return pair_stats("lasso_host_blind_stats", h, &lasso_host::blind_count, EXT_COUNT, rows_device, rows_host, nullptr, reset);
 }
 int32_t lasso_host_strategy_check(const lasso_strategy* st) {
   GUARD(const Strategy S = Strategy::from_abi(st); (void)S; return 0;)

@@ -336,9 +336,8 @@ class Verifier {
     return Pt::from_abi(out);
   }
   static void wire(const Pt& p, uint8_t out[32]) { compress_one(p, out); }
-  // bullet.rs:158-257 inside dot_product.rs:251-296 inside dense_mlpoly.rs:361-400 (verify_plain: the claimed evaluation is committed with blind 0)
-  bool poly_eval_verify_plain(const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) { return poly_eval_verify_plain(d, t, points_msm, p, g, r, Zr, comm); }
  public:
+  // bullet.rs:158-257 inside dot_product.rs:251-296 inside dense_mlpoly.rs:361-400 (verify_plain: the claimed evaluation is committed with blind 0)
   static bool poly_eval_verify_plain(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& p, const PolyCommitmentGens& g, const ScVec& r, const Sc& Zr, const std::vector<WirePoint>& comm) {
     WirePoint C_Zr; C_Zr.p = g.Qmul.mul(Zr);   // Zr.commit(&0, &gens.gens.gens_1) = Zr * G[0] + 0 * h
     wire(C_Zr.p, C_Zr.bytes);
@@ -388,31 +387,17 @@ class Verifier {
   static bool combined_table_eval_verify_plain(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const WireDotProductProofLog& proof, const PolyCommitmentGens& g, const ScVec& r,
                                                const ScVec& evals_in, const std::vector<WirePoint>& comm) {
     t.append_protocol_name("Lasso CombinedTableEvalProof");
-    ScVec evals = evals_in; evals.resize(next_pow2(evals.size()), Sc::zero());
-    t.append_scalars("evals_ops_val", evals);
-    const ScVec ch = t.challenge_vector("challenge_combine_n_to_one", ceil_log2(evals.size()));
-    const Sc joint = bound_bot_all(evals, ch);
-    ScVec r_joint = ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
-    t.append_scalar("joint_claim_eval", joint);
-    return poly_eval_verify_plain(d, t, points_msm, proof, g, r_joint, joint, comm);
+    return joint_verify(d, t, points_msm, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", evals_in, true, proof, g, r, comm);
+  }
+  // the n-to-1 reduction the prover made (joint_claim, prover.hpp), then the opening at ch || r to the joint claim
+  static bool joint_verify(const Dev& d, ProofTranscript& t, const PointsMsm& points_msm, const char* evals_label, const char* challenge_label, const char* joint_label, const ScVec& evals,
+                           bool pad_before_append, const WireDotProductProofLog& proof, const PolyCommitmentGens& g, const ScVec& r, const std::vector<WirePoint>& comm) {
+    const JointClaim jc = joint_claim(t, evals_label, challenge_label, joint_label, evals, pad_before_append);
+    ScVec r_joint = jc.ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
+    return poly_eval_verify_plain(d, t, points_msm, proof, g, r_joint, jc.joint, comm);
   }
  private:
-  // subtables/mod.rs:315-375
-  bool combined_table_eval_verify(const WireDotProductProofLog& proof, const ScVec& r, const ScVec& evals_in, const std::vector<WirePoint>& comm) {
-    t.append_protocol_name("Lasso CombinedTableEvalProof");
-    ScVec evals = evals_in; evals.resize(next_pow2(evals.size()), Sc::zero());
-    t.append_scalars("evals_ops_val", evals);
-    const ScVec ch = t.challenge_vector("challenge_combine_n_to_one", ceil_log2(evals.size()));
-    const Sc joint = bound_bot_all(evals, ch);
-    ScVec r_joint = ch; r_joint.insert(r_joint.end(), r.begin(), r.end());
-    t.append_scalar("joint_claim_eval", joint);
-    return poly_eval_verify_plain(proof, gens.gens_derefs, r_joint, joint, comm);
-  }
-  // for i in (0..challenges.len()).rev() { poly.bound_poly_var_bot(&challenges[i]) }  (dense_mlpoly.rs:218-225)
-  static Sc bound_bot_all(ScVec z, const ScVec& ch) {
-    for (size_t i = ch.size(); i-- > 0;) { const size_t n = z.size() / 2; for (size_t k = 0; k < n; k++) z[k] = z[2 * k] + ch[i] * (z[2 * k + 1] - z[2 * k]); z.resize(n); }
-    LASSO_REQUIRE(z.size() == 1); return z[0];
-  }
+  bool combined_table_eval_verify(const WireDotProductProofLog& proof, const ScVec& r, const ScVec& evals, const std::vector<WirePoint>& comm) { return combined_table_eval_verify_plain(d, t, points_msm, proof, gens.gens_derefs, r, evals, comm); }
 
  public:
   Verifier(const Dev& d_, const Strategy& S_, const SparsePolyCommitmentGens& g_, ProofTranscript& t_, const WireDecoder& w_ = WireDecoder(), const PointsMsm& m_ = PointsMsm(), const TablesMle& e_ = TablesMle()) : d(d_), S(S_), gens(g_), t(t_), decoder(w_), points_msm(m_), tables_mle(e_) {}
@@ -487,20 +472,8 @@ class Verifier {
     t.append_protocol_name("Lasso HashLayerProof");
     if (!combined_table_eval_verify(P.open_derefs, rand_ops, P.eval_derefs_hash, P.comm_derefs)) return false;
     ScVec evals_ops = P.eval_dim; evals_ops.insert(evals_ops.end(), P.eval_read.begin(), P.eval_read.end());
-    evals_ops.resize(next_pow2(evals_ops.size()), Sc::zero());
-    t.append_scalars("claim_evals_ops", evals_ops);
-    const ScVec ch_ops = t.challenge_vector("challenge_combine_n_to_one", ceil_log2(evals_ops.size()));
-    const Sc joint_ops = bound_bot_all(evals_ops, ch_ops);
-    ScVec r_joint_ops = ch_ops; r_joint_ops.insert(r_joint_ops.end(), rand_ops.begin(), rand_ops.end());
-    t.append_scalar("joint_claim_eval_ops", joint_ops);
-    if (!poly_eval_verify_plain(P.open_ops, gens.gens_combined_l_variate, r_joint_ops, joint_ops, comm_l)) return false;
-    t.append_scalars("claim_evals_mem", P.eval_final);
-    ScVec fin = P.eval_final; fin.resize(next_pow2(fin.size()), Sc::zero());   // DensePolynomial::new_padded
-    const ScVec ch_mem = t.challenge_vector("challenge_combine_two_to_one", ceil_log2(P.eval_final.size()));
-    const Sc joint_mem = bound_bot_all(fin, ch_mem);
-    ScVec r_joint_mem = ch_mem; r_joint_mem.insert(r_joint_mem.end(), rand_mem.begin(), rand_mem.end());
-    t.append_scalar("joint_claim_eval_mem", joint_mem);
-    if (!poly_eval_verify_plain(P.open_mem, gens.gens_combined_log_m_variate, r_joint_mem, joint_mem, comm_m)) return false;
+    if (!joint_verify(d, t, points_msm, "claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops", evals_ops, true, P.open_ops, gens.gens_combined_l_variate, rand_ops, comm_l)) return false;
+    if (!joint_verify(d, t, points_msm, "claim_evals_mem", "challenge_combine_two_to_one", "joint_claim_eval_mem", P.eval_final, false, P.open_mem, gens.gens_combined_log_m_variate, rand_mem, comm_m)) return false;
     // check_reed_solomon_fingerprints :462-523 with h(a, v, t) = t*gamma^2 + v*gamma + a - tau
     Sc init_addr = Sc::zero();   // IdentityPolynomial::evaluate identity_poly.rs:14-20
     for (size_t i = 0; i < rand_mem.size(); i++) init_addr += Sc::from_u64((uint64_t)1 << (rand_mem.size() - i - 1)) * rand_mem[i];
